@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the tl.infercnv hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 With N > 1 and no WORLD_SIZE in the environment the script re-executes itself as
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` (one rank per
@@ -34,9 +34,12 @@ One "step" = one pass of the whole hot path over one batch of synthetic cells th
           (dist.shard_bounds; 125 000 cells per GPU at N = 8): strong scaling.  Every 5000-cell chunk is generated
           from its own seed, so the data do not depend on N.
 
-Prints ONE JSON line on rank 0: value = cells/s of the whole job (HBM-resident input), plus
+Prints ONE JSON line on rank 0: value = cells/s of the whole job (HBM-resident input), ms_per_step = the
+milliseconds of one timed step (--steps of them after --warmup untimed ones), plus
   roofline     - the smoothing kernel: algorithmic bytes (4*G + 4*W per cell) / its average HIP-event duration
-                 (events recorded by the library on the launch stream), against the 8 TB/s HBM peak
+                 (events recorded by the library on the launch stream during the timed steps), against the 8 TB/s
+                 HBM peak
+A plain run stops there.  With ``--full`` the line also carries the figures that take runs of their own:
   cpu_baseline - the numpy oracle (a port of the reference algorithm, oracle/) on this box's host cores on a
                  bounded sample of the same workload (rank 0, N = 1 only)
   e2e          - the public cnv.tl.infercnv(adata) from HOST memory to a host CSR X_cnv (PCIe-inclusive, rank 0).
@@ -49,6 +52,11 @@ Prints ONE JSON line on rank 0: value = cells/s of the whole job (HBM-resident i
                  own roofline: config 4 (CSR window 250), CSR window 100, config 3's 1 M cells on one GPU, the round-3
                  form of the step (float64 column sums + in-place threshold, no CSR), config 5 (distances + Ward at
                  200 000 x 5 000 when HBM allows).
+  (N > 1)      - value_allreduce_means: the float64 all-reduce form of the means, timed after the two exact forms.
+
+``--dump-outputs DIR``: after the timed steps, X_cnv of the last step as float64 .npy files in DIR (a seeded sample
+of its rows, per-row sums and entry counts, chr_pos; see dump_outputs).  The inputs are generated from fixed seeds, so
+two builds run with the same arguments can be compared output for output.
 
 ``--dry-run-one-gpu`` (never a measurement: prints "dry_run": true): all N ranks share cuda:0 and the collectives
 go through gloo -- exercises the launcher, the sharding and the N > 1 code paths on a one-GPU box.
@@ -180,12 +188,19 @@ def _physical_cores():
         return os.cpu_count() or 1
 
 
-def _cpu_pool_rate(workers, window, step, cells_per_worker, reps):
+def _cpu_pool(workers):
+    """Process pool of the CPU baseline.  The workers are spawned, not forked: this process has the GPU open, and
+    forked children would inherit its device handles."""
+    import multiprocessing
     from concurrent.futures import ProcessPoolExecutor
 
+    return ProcessPoolExecutor(max_workers=workers, mp_context=multiprocessing.get_context("spawn"))
+
+
+def _cpu_pool_rate(workers, window, step, cells_per_worker, reps):
     tasks = [(100 + i, cells_per_worker, window, step, reps) for i in range(workers)]
     t0 = time.perf_counter()
-    with ProcessPoolExecutor(max_workers=workers) as pool:
+    with _cpu_pool(workers) as pool:
         busy = list(pool.map(_cpu_worker, tasks))
     wall = time.perf_counter() - t0
     n = cells_per_worker * workers * reps
@@ -210,8 +225,6 @@ def _cpu_chunk_worker(args):
 
 
 def cpu_baseline(window=100, step=10, cells_per_worker=400, reps=2, slice_cells=100_000, chunk=CHUNK):
-    from concurrent.futures import ProcessPoolExecutor
-
     logical = os.cpu_count() or 1
     physical = min(_physical_cores(), logical)
     # the reference's structure -- ProcessPoolExecutor over 5000-row chunks of a 100 000-cell slice (20
@@ -219,7 +232,7 @@ def cpu_baseline(window=100, step=10, cells_per_worker=400, reps=2, slice_cells=
     # pool), the clock runs over the slowest chunk's compute time and, separately, over the wall time of the pool
     n_tasks = slice_cells // chunk
     t0 = time.perf_counter()
-    with ProcessPoolExecutor(max_workers=min(physical, n_tasks)) as pool:
+    with _cpu_pool(min(physical, n_tasks)) as pool:
         busy = list(pool.map(_cpu_chunk_worker, [(300 + i, chunk, window, step) for i in range(n_tasks)]))
     wall = time.perf_counter() - t0
     spec = {
@@ -240,7 +253,7 @@ def cpu_baseline(window=100, step=10, cells_per_worker=400, reps=2, slice_cells=
     n_cfg3 = CONFIG3_CELLS // chunk
     workers = max(1, min(physical, n_cfg3))
     t0 = time.perf_counter()
-    with ProcessPoolExecutor(max_workers=workers) as pool:
+    with _cpu_pool(workers) as pool:
         busy3 = list(pool.map(_cpu_chunk_worker, [(700 + i, chunk, window, step) for i in range(n_cfg3)]))
     wall3 = time.perf_counter() - t0
     slots = [0.0] * workers
@@ -439,10 +452,11 @@ def pmc_traffic(key, cells):
 
 def hbm_step(torch, icd, _engine, plan, dm, n_local, fmt, window, step, chunksize, steps, warmup, dist=None,
              bounds=None, row0=0, n_total=None, no_refmean=False, nnz_row=G, traffic_key=None, pack=False,
-             means="allreduce"):
+             means="allreduce", keep_last=None):
     """Time `steps` passes of the per-rank hot path (dist.run_shard) over the resident rows of `dm`; returns (seconds,
-    roofline dict).  means = "blocks": the reference's own bits with the ranks' passes CONCURRENT -- the float32 chain by
-    integer blocks (dist.reference_means_blocks: float64 totals, one all-gather, block records, a scan that travels);
+    roofline dict); the last step's return value is appended to the list `keep_last` if one is given.
+    means = "blocks": the reference's own bits with the ranks' passes CONCURRENT -- the float32 chain by integer blocks
+    (dist.reference_means_blocks: float64 totals, one all-gather, block records, a scan that travels);
     "chained": the reference's own bits -- icv_colchain accumulators handed from rank to rank,
     pipelined over column groups (dist.reference_means_chained), the same computation as the N = 1 public call;
     "allreduce": float64 column sums + ONE all-reduce (correctly rounded means, concurrent)."""
@@ -482,9 +496,11 @@ def hbm_step(torch, icd, _engine, plan, dm, n_local, fmt, window, step, chunksiz
     _engine.profile_begin(plan)
     t0 = time.perf_counter()
     for _ in range(steps):
-        one_step()
+        last = one_step()
     fence()
     dt = time.perf_counter() - t0
+    if keep_last is not None:
+        keep_last.append(last)
     smooth_ms = [r.smooth_ms for r in _engine.profile_collect(plan)]
     assert len(smooth_ms) == steps
     # dense 4*G + 4*W = 87 208 B/cell at window 100 / step 10; CSR 8*nnz_row + 8 + 4*W
@@ -918,6 +934,56 @@ def _summary(result):
     return out
 
 
+# ----------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path returned in its last step, to compare two builds output for output
+# ----------------------------------------------------------------------------------------------------------
+DUMP_ROWS_BYTES = 32 << 20     # dense float64 rows of X_cnv: every row if they fit, else a seeded sample
+DUMP_ROW_STATS = 1_000_000     # per-row sums / entry counts: every row up to this many, else a seeded sample
+
+
+def dump_outputs(out_dir, x_cnv, chr_pos, suffix="", share=1):
+    """Write X_cnv of the last timed step to `out_dir` as float64 .npy files (at most 48 MB / `share`):
+      x_cnv_rows       dense rows (float64) of the rows in x_cnv_row_index
+      x_cnv_row_index  sorted row indices: every row, or a sample drawn with a fixed seed
+      x_cnv_row_sum    sum of every row (a fixed-seed sample of DUMP_ROW_STATS rows above that many)
+      x_cnv_row_nnz    stored entries of the same rows
+      chr_pos          first window of every chromosome, in the plan's chromosome order
+    x_cnv: the PackedCsr of the public call / run_shard(pack=True), or the dense device x_res of run_shard(pack=False)
+    (whose entries below the threshold are zero, so "stored" = non-zero).  `suffix` tells the files of ranks apart;
+    `share` (the number of ranks) divides the budget between them."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    if hasattr(x_cnv, "to_scipy"):
+        m = x_cnv.to_scipy()
+        n, w = m.shape
+        dense_rows = lambda rows: m[rows].toarray()  # noqa: E731
+        row_sum = np.asarray(m.sum(axis=1), dtype=np.float64).ravel()
+        row_nnz = np.diff(m.indptr).astype(np.float64)
+    else:
+        a = x_cnv.cpu().numpy()
+        n, w = a.shape
+        dense_rows = lambda rows: a[rows].astype(np.float64)  # noqa: E731
+        row_sum = a.sum(axis=1, dtype=np.float64)
+        row_nnz = np.count_nonzero(a, axis=1).astype(np.float64)
+    rng = np.random.default_rng(20_000)
+
+    def sample(k):
+        return np.arange(n) if k >= n else np.sort(rng.choice(n, k, replace=False))
+
+    rows = sample(max(1, DUMP_ROWS_BYTES // share // (8 * max(w, 1))))
+    stat_rows = sample(DUMP_ROW_STATS // share)
+    arrays = {
+        "x_cnv_rows": dense_rows(rows), "x_cnv_row_index": rows,
+        "x_cnv_row_sum": row_sum[stat_rows], "x_cnv_row_nnz": row_nnz[stat_rows],
+        "chr_pos": np.array([int(p) for p in chr_pos.values()]),
+    }
+    if len(stat_rows) < n:
+        arrays["x_cnv_row_stats_index"] = stat_rows
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -940,10 +1006,15 @@ def main():
     ap.add_argument("--format", choices=["dense", "csr"], default="dense",
                     help="csr = BASELINE config 4 style input (not the default bench line)")
     ap.add_argument("--density", type=float, default=0.07)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--extra", default="", help="comma-separated subset of the extra legs (default: all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: stages, cpu_baseline, e2e, extra and (N > 1) the all-reduce "
+                         "form of the means (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write X_cnv of the last timed step to DIR as .npy files (a seeded sample; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) without the cpu_baseline leg")
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) without the e2e legs")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) without the extra legs")
+    ap.add_argument("--extra", default="", help="(--full) comma-separated subset of the extra legs (default: all)")
     ap.add_argument("--no-refmean", action="store_true", help="exclude the reference-mean pass from the step")
     ap.add_argument("--engine-step", action="store_true",
                     help="N = 1: time the engine-level step of N > 1 (float64 sums + in-place threshold) instead of "
@@ -1029,7 +1100,8 @@ def main():
         traffic_key = f"csr_w{args.window}"
 
     stages = None
-    if n_gpus == 1 and not args.engine_step:
+    rank_path = n_gpus > 1 or args.engine_step
+    if not rank_path:
         # the headline: ONE call of the public function per step on the resident matrix (reference=None: the default)
         from infercnvpy_amd._compat import SimpleAnnData
         from infercnvpy_amd.tl import _infercnv as T
@@ -1041,12 +1113,15 @@ def main():
             kw["reference"] = (_engine.column_sums(dm)[0] / n_local).float().cpu().numpy()
         dt, roof, nnz_out = api_step(torch, _engine, ad, args.steps, args.warmup, args.format, args.window, args.step,
                                      nnz_row=nnz_row, traffic_key=traffic_key, **kw)
-        api_plan = T._cached_plan(var["chromosome"].to_numpy(), var["start"].to_numpy(), args.window, args.step,
-                                  ("chrX", "chrY"), torch.cuda.current_device())
-        mt = ("colchain_dense",) if args.format == "dense" else (("colchain_csrq", "csr_tile_bounds16") if traffic_key else None)
-        stages = stage_times(torch, _engine, api_plan, dm, n_local, args.chunksize, args.format, nnz_row=nnz_row,
-                             mean_traffic=mt)
-        stages["x_cnv_nnz_public_call"] = nnz_out
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, ad.obsm["X_cnv"], ad.uns["cnv"]["chr_pos"])
+        if args.full:
+            api_plan = T._cached_plan(var["chromosome"].to_numpy(), var["start"].to_numpy(), args.window, args.step,
+                                      ("chrX", "chrY"), torch.cuda.current_device())
+            mt = ("colchain_dense",) if args.format == "dense" else (("colchain_csrq", "csr_tile_bounds16") if traffic_key else None)
+            stages = stage_times(torch, _engine, api_plan, dm, n_local, args.chunksize, args.format, nnz_row=nnz_row,
+                                 mean_traffic=mt)
+            stages["x_cnv_nnz_public_call"] = nnz_out
         ad = None
     else:
         # N > 1 (or --engine-step): the per-rank code path, dist.run_shard, with the thresholds applied while X_cnv is
@@ -1061,22 +1136,30 @@ def main():
         # (the block form has run under process groups on ONE GPU only: if it fails on every rank of a real multi-GPU job
         # the line still carries the two older forms, and says so)
         first_error = None
+        # (the exact forms give the same X_cnv: the dump is that of whichever ran last)
+        last = [] if args.dump_outputs else None
         try:
             dt, roof = hbm_step(torch, icd, _engine, plan, dm, n_local, args.format, args.window, args.step,
-                                args.chunksize, args.steps, args.warmup, means=first, **common)
+                                args.chunksize, args.steps, args.warmup, means=first, keep_last=last, **common)
         except Exception as e:  # pragma: no cover
             first_error = repr(e)[:300]
             torch.cuda.synchronize()
         dt_ch, roof_ch = hbm_step(torch, icd, _engine, plan, dm, n_local, args.format, args.window, args.step,
-                                  args.chunksize, args.steps, args.warmup, means="chained", **common)
+                                  args.chunksize, args.steps, args.warmup, means="chained", keep_last=last, **common)
         if first_error is not None:
             dt, roof = dt_ch, roof_ch
-        dt_ar, roof_ar = hbm_step(torch, icd, _engine, plan, dm, n_local, args.format, args.window, args.step,
-                                  args.chunksize, args.steps, args.warmup, means="allreduce", **common)
+        if last:
+            out = last[-1][1] if isinstance(last[-1], tuple) else last[-1].out  # PackedCsr | x_res thresholded in place
+            dump_outputs(args.dump_outputs, out, plan.chr_pos, suffix=f".rank{rank}" if world > 1 else "", share=world)
+            del last, out
+        dt_ar = None
+        if args.full:
+            dt_ar, roof_ar = hbm_step(torch, icd, _engine, plan, dm, n_local, args.format, args.window, args.step,
+                                      args.chunksize, args.steps, args.warmup, means="allreduce", **common)
     if dist is not None:
-        t = torch.tensor([dt, dt_ar, dt_ch], dtype=torch.float64, device="cpu" if dry else "cuda")
+        t = torch.tensor([dt, dt_ar or 0.0, dt_ch], dtype=torch.float64, device="cpu" if dry else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_ar, dt_ch = float(t[0].item()), float(t[1].item()), float(t[2].item())
+        dt, dt_ar, dt_ch = float(t[0].item()), float(t[1].item()) if args.full else None, float(t[2].item())
 
     def host_barrier(tag):
         """Ranks meet through the rendezvous store (CPU only): no collective kernel spins on the idle GPUs while rank
@@ -1093,7 +1176,7 @@ def main():
     # count -- the blocks pay two concurrent passes + a scan (~2.2 passes of a rank's rows), the chained accumulators
     # (T + R - 1) / T passes with T = 2: 1.5 at R = 2, 2.5 at R = 4, 4.5 at R = 8 (dist.reference_means_exact picks alike)
     value_form, dt_blocks = None, None
-    if stages is None and dist is not None and args.format == "dense" and not args.engine_step:
+    if rank_path and dist is not None and args.format == "dense" and not args.engine_step:
         if first_error is None:
             dt_blocks = dt
             value_form = "blocks"
@@ -1111,7 +1194,6 @@ def main():
     else:
         name = ("custom (not a BASELINE configuration): " +
                 ("dense fp32" if args.format == "dense" else f"CSR fp32 density {args.density}"))
-    rank_path = stages is None
     result = {
         "metric": (f"cells/sec through tl.infercnv (window={args.window}), input resident in HBM" if not rank_path else
                    f"cells/sec through the tl.infercnv hot path (window={args.window}) as dist.run_shard on every rank "
@@ -1138,7 +1220,7 @@ def main():
                         + (" (precomputed, excluded from the step)" if args.no_refmean else " (in the step)")
                         + ("; step = one cnv.tl.infercnv(adata) call, adata.X a CUDA tensor, X_cnv returned as device "
                            "CSR float64 (reference-order means, smoothing, noise threshold + CSR pack)"
-                           if stages is not None else
+                           if not rank_path else
                            "; step = reference-order column means (numpy's own bits: the float32 chain by integer "
                            "blocks, dist.reference_means_blocks -- float64 totals + one all-gather + block records on "
                            "every rank at once, then a scan over the records from rank to rank) + smoothing + thresholds "
@@ -1164,8 +1246,9 @@ def main():
         "roofline": roof,
     }
     if rank_path:
-        result["value_allreduce_means"] = n_total / (dt_ar / args.steps)
-        result["ms_per_step_allreduce_means"] = dt_ar / args.steps * 1e3
+        if dt_ar is not None:
+            result["value_allreduce_means"] = n_total / (dt_ar / args.steps)
+            result["ms_per_step_allreduce_means"] = dt_ar / args.steps * 1e3
         result["value_chained_means"] = n_total / (dt_ch / args.steps)
         result["ms_per_step_chained_means"] = dt_ch / args.steps * 1e3
         if dt_blocks is not None:
@@ -1186,11 +1269,13 @@ def main():
             "value_blocks_means": "the float32 chain by integer blocks (dist.reference_means_blocks), dense shards",
             "value_chained_means": "the same bits with the icv_colchain accumulators handed from rank to rank, pipelined "
                                    "over 2 column groups (dist.reference_means_chained; rounds 4-5: the ranks take turns)",
-            "value_allreduce_means": "float64 column sums + one all-reduce (dist.reference_means): correctly rounded "
-                                     "means, concurrent over the ranks, ~1e-3 of the X_cnv entries next to the noise "
-                                     "threshold may differ from the reference (tl.infercnv(mean_order='float64'))",
-            "smooth_kernel_ms_allreduce_run": roof_ar["kernel_ms"],
         }
+        if dt_ar is not None:
+            result["forms"]["value_allreduce_means"] = (
+                "float64 column sums + one all-reduce (dist.reference_means): correctly rounded means, concurrent over "
+                "the ranks, ~1e-3 of the X_cnv entries next to the noise threshold may differ from the reference "
+                "(tl.infercnv(mean_order='float64'))")
+            result["forms"]["smooth_kernel_ms_allreduce_run"] = roof_ar["kernel_ms"]
         if first_error is not None:
             result["forms"]["value"] = "THE BLOCK FORM FAILED (" + first_error + "): value = value_chained_means"
     if stages is not None:
@@ -1201,7 +1286,7 @@ def main():
                                   "exercise only, the numbers mean nothing")
     del X, dm
     torch.cuda.empty_cache()
-    if rank == 0 and n_gpus == 1 and args.format == "dense":
+    if args.full and rank == 0 and n_gpus == 1 and args.format == "dense":
         if not args.no_cpu_baseline:
             try:
                 result["cpu_baseline"] = cpu_baseline(window=args.window, step=args.step)
@@ -1218,7 +1303,7 @@ def main():
             leg3 = result["extra"].get("config3_cells_on_one_gpu")
             if isinstance(leg3, dict) and "scale_n1" in leg3:
                 result["scale_n1"] = leg3.pop("scale_n1")
-    if n_gpus > 1 and not args.no_e2e and args.format == "dense":
+    if args.full and n_gpus > 1 and not args.no_e2e and args.format == "dense":
         # the public API over all GPUs of the job, from host memory: rank 0 drives every GPU from one process while
         # the other ranks have released their HBM and wait
         torch.cuda.synchronize()

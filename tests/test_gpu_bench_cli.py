@@ -29,7 +29,8 @@ def _run_bench(*args, timeout=900):
 
 @pytest.mark.parametrize("n_ranks", [2, 8])
 def test_n_rank_command_line_dry_run(n_ranks):
-    rec, lines, err = _run_bench("--gpus", str(n_ranks), "--dry-run-one-gpu", "--steps", "2", "--warmup", "1", "--no-e2e")
+    rec, lines, err = _run_bench("--gpus", str(n_ranks), "--dry-run-one-gpu", "--steps", "2", "--warmup", "1", "--full",
+                                 "--no-e2e")
     assert rec["dry_run"] is True
     assert rec["n_gpus"] == n_ranks and rec["steps"] == 2 and rec["warmup"] == 1
     assert rec["unit"] == "cells/s" and rec["higher_is_better"] is True
@@ -52,10 +53,53 @@ def test_n_rank_command_line_dry_run(n_ranks):
 def test_one_gpu_line_ends_with_json_and_warns_once():
     """N = 1 at a reduced size: the JSON line is the last line of stdout, the digest is its last key, and the
     reference's "Using mean of all cells" warning appears once in the process output, not once per call."""
-    rec, lines, err = _run_bench("--steps", "3", "--warmup", "1", "--cells", "20000", "--no-cpu-baseline", "--no-e2e",
-                                 "--no-extra")
+    rec, lines, err = _run_bench("--steps", "3", "--warmup", "1", "--cells", "20000", "--full", "--no-cpu-baseline",
+                                 "--no-e2e", "--no-extra")
     assert rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["value"] > 0
     assert rec["roofline"]["kernel_ms"] > 0 and "stages" in rec
     assert list(rec)[-1] == "summary"
     assert err.count("Using mean of all cells as reference") <= 1
     assert "bench-summary " in err
+
+
+def _dump(d):
+    import numpy as np
+
+    files = sorted(os.listdir(d))
+    assert files and all(f.endswith(".npy") for f in files), files
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+    arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    return arrays
+
+
+def test_plain_line_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain N = 1 run times the headline step only (no legs of --full in the line), and --dump-outputs writes the
+    last step's X_cnv; a second run with the same arguments writes the same arrays, and the N-rank path (2 ranks on one
+    GPU) writes the same rows of X_cnv, shard by shard."""
+    import numpy as np
+
+    runs = []
+    for k in range(2):
+        rec, _, _ = _run_bench("--steps", "3", "--warmup", "1", "--cells", "20000", "--dump-outputs",
+                               str(tmp_path / f"n1_{k}"))
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert rec["unit"] == "cells/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+        assert not {"stages", "cpu_baseline", "e2e", "extra", "scale_n1"} & set(rec)
+        runs.append(_dump(tmp_path / f"n1_{k}"))
+    a, b = runs
+    assert set(a) == set(b) >= {"x_cnv_rows", "x_cnv_row_index", "x_cnv_row_sum", "x_cnv_row_nnz", "chr_pos"}
+    for name in a:
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    assert a["x_cnv_row_sum"].shape == (20000,) and a["x_cnv_rows"].shape[0] == a["x_cnv_row_index"].shape[0]
+    assert np.all(np.diff(a["x_cnv_row_index"]) > 0) and a["x_cnv_row_nnz"].sum() > 0
+
+    rec, _, _ = _run_bench("--gpus", "2", "--dry-run-one-gpu", "--steps", "2", "--warmup", "1", "--cells", "20000",
+                           "--dump-outputs", str(tmp_path / "n2"))
+    assert "value_allreduce_means" not in rec and "e2e" not in rec
+    c = _dump(tmp_path / "n2")
+    np.testing.assert_array_equal(np.concatenate([c["x_cnv_row_nnz.rank0"], c["x_cnv_row_nnz.rank1"]]),
+                                  a["x_cnv_row_nnz"])
+    np.testing.assert_array_equal(np.concatenate([c["x_cnv_row_sum.rank0"], c["x_cnv_row_sum.rank1"]]),
+                                  a["x_cnv_row_sum"])
+    np.testing.assert_array_equal(c["chr_pos.rank0"], a["chr_pos"])

@@ -26,7 +26,7 @@ cp $O/bench_1m_leg.json $P/${ROUND}_bench_1m_leg.json
 python - $O/clocks_1m_leg.txt > $P/${ROUND}_clocks_1m_leg.txt <<'PY'
 import re, sys
 lines = [l for l in open(sys.argv[1]) if l.strip()]
-print(f"rocm-smi --showclocks --showpower every 0.25 s over bench.py --steps 300 --extra config3_cells_on_one_gpu ({len(lines)} samples)")
+print(f"rocm-smi --showclocks --showpower every 0.25 s over bench.py --full --steps 300 --extra config3_cells_on_one_gpu ({len(lines)} samples)")
 for l in lines[::max(1, len(lines) // 60)]:
     print(l.strip()[:200])
 PY

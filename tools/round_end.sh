@@ -13,9 +13,9 @@ if [ "${1:-}" != "quick" ]; then
   timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -4 | tee $O/pytest.txt
   timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1 | tee $O/smoke.txt
 fi
-( time timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err ) 2> $O/bench_n1.time; tail -c 300 $O/bench_n1.json; tail -3 $O/bench_n1.time
-timeout 300 python bench.py --gpus 2 --dry-run-one-gpu --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/bench_dry_run_2ranks_one_gpu.json
-timeout 600 python bench.py --gpus 8 --dry-run-one-gpu --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/bench_dry_run_8ranks_one_gpu.json
+( time timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err ) 2> $O/bench_n1.time; tail -c 300 $O/bench_n1.json; tail -3 $O/bench_n1.time
+timeout 300 python bench.py --gpus 2 --dry-run-one-gpu --full --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/bench_dry_run_2ranks_one_gpu.json
+timeout 600 python bench.py --gpus 8 --dry-run-one-gpu --full --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/bench_dry_run_8ranks_one_gpu.json
 stats() {  # name, bench.py arguments...
   name=$1; shift
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/_s_$name -o bench -- python $REPO/bench.py "$@" > $O/bench_${name}_traced.json 2> $O/rocprof_$name.log)
@@ -23,12 +23,12 @@ stats() {  # name, bench.py arguments...
   rm -rf $O/_s_$name
   head -6 $O/kernel_stats_$name.csv | cut -c1-150
 }
-BASE="--no-cpu-baseline --no-e2e --no-extra"
+BASE="--full --no-cpu-baseline --no-e2e --no-extra"
 stats dense_w100 --steps 20 --warmup 3 $BASE
 stats csr_w250 --format csr --cells 500000 --window 250 --steps 5 --warmup 2 $BASE
 stats csr_w100 --format csr --cells 200000 --window 100 --steps 5 --warmup 2 $BASE
-stats config5 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --extra config5
-stats gene_values_scores --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --extra scores_and_gene_values
+stats config5 --steps 2 --warmup 1 --full --no-cpu-baseline --no-e2e --extra config5
+stats gene_values_scores --steps 3 --warmup 1 --full --no-cpu-baseline --no-e2e --extra scores_and_gene_values
 pmc() {  # label, bench.py arguments...
   label=$1; shift
   for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE"; do
@@ -51,7 +51,7 @@ pmc_hbm() {  # label, bench.py arguments...: HBM traffic only (two passes)
     rm -rf $O/_p
   done
 }
-pmc_hbm gene_values_100000_cells --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --extra scores_and_gene_values
+pmc_hbm gene_values_100000_cells --steps 2 --warmup 1 --full --no-cpu-baseline --no-e2e --extra scores_and_gene_values
 # round 6: the CSR means over the density, the chain by integer blocks (one rank's share), the HBM write ceiling, clocks and
 # power over the sustained 1 M-cell leg
 timeout 400 python tools/time_csr_means.py 2>/dev/null | tee $O/csr_means_density.txt
@@ -61,7 +61,7 @@ timeout 200 python tools/time_gene_kernel.py 2>/dev/null | tail -1 | tee $O/gene
 BENCH_E2E_LEGS=1m timeout 400 python tools/host_issue_after_e2e.py 2>/dev/null | grep -v "amdgpu.ids" | tail -12 > $O/host_issue_after_e2e.txt; tail -8 $O/host_issue_after_e2e.txt | cut -c1-200
 ( while true; do rocm-smi --showclocks --showpower 2>/dev/null | grep -E "sclk|mclk|Power \(W\)|Average Graphics" | tr -s " " | tr "\n" ";"; echo; sleep 0.25; done > $O/clocks_1m_leg.txt ) &
 CLK=$!
-timeout 600 python bench.py --steps 300 --warmup 5 --no-cpu-baseline --no-e2e --extra config3_cells_on_one_gpu > $O/bench_1m_leg.json 2> $O/bench_1m_leg.err
+timeout 600 python bench.py --steps 300 --warmup 5 --full --no-cpu-baseline --no-e2e --extra config3_cells_on_one_gpu > $O/bench_1m_leg.json 2> $O/bench_1m_leg.err
 kill $CLK 2>/dev/null
 tail -1 $O/bench_1m_leg.err | cut -c1-600
 # round 5: k_smooth_se at three densities, the host-side packing of the sparse upload, fuzzers and the soak on the final tree
