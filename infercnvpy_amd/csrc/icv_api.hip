@@ -956,8 +956,8 @@ int colchain_dense(const icv_matrix* m, const int32_t* rows, int64_t n_sel, T* a
     const kern_t kern = rows ? (kern_t)icv::k_colchain<T, true> : (kern_t)icv::k_colchain<T, false>;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 icv::kChLdsFull));
-    hipLaunchKernelGGL(kern, dim3(L.grid), dim3(icv::kChThreads), L.lds_bytes, st, (const T*)m->values, m->ld,
-                       m->n_cols, L.n_lines, L.lds_bytes, rows, n_dma, tail, acc);
+    hipLaunchKernelGGL(kern, dim3(L.dense_grid), dim3(icv::kChThreads), L.lds_bytes, st, (const T*)m->values, m->ld,
+                       m->n_cols, L.n_units, L.lds_bytes, rows, n_dma, tail, acc);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }

@@ -5,7 +5,7 @@
 // mean is the same chain over `fl(x * fl(1/n))` (csc_matvecs of the transposed matrix walks the rows in order).  A
 // float32 chain is not associative, so the only parallelism an exact reproduction has is ACROSS columns:
 //
-//   k_colchain<T>: one 1024-thread workgroup per tile of 512 bytes of a row (128 float32 / 64 float64 columns).
+//   k_colchain<T>: one 1024-thread workgroup per tile of 64..512 bytes of a row (up to 128 float32 / 64 float64 columns).
 //     15 loader wavefronts copy the tile's row segments HBM -> LDS with LDS-DMA (`global_load_lds_dwordx4`: no staging
 //     registers, no ds_write), kChDepth rounds of 30 rows ahead -- the LDS ring IS the set of bytes in flight (135 KB
 //     per CU); ONE chain wavefront (lane = 2 float32 columns / 1 float64 column) adds the landed rows in order with
@@ -44,23 +44,53 @@ template <> struct ChainLane<float> { typedef chain_f2 type; };
 template <> struct ChainLane<double> { typedef double type; };
 
 // LDS-DMA: 16 bytes per lane from `src` (per lane) to lds_base + 16 * lane (wave-uniform base, LDS byte address)
+// (ICV_CH_DMA_NT=0: without the non-temporal hint -- a tuning build)
+#ifndef ICV_CH_DMA_NT
+#define ICV_CH_DMA_NT 1
+#endif
 __device__ __forceinline__ void lds_dma16(const void* src, unsigned lds_base) {
     unsigned keep;
     asm volatile(
+#if ICV_CH_DMA_NT
         "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+#else
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+#endif
         : "=&s"(keep)
         : "v"(src), "s"(lds_base)
         : "memory");
 }
 
-// Geometry of a tile of NL cache lines: LDS-DMA lanes per row, rows per 1 KB load, rows per round, bytes per ring slot
-// (u = loads per loader wavefront and round: 2 with the whole LDS of a CU, 1 with half of it)
+// Geometry of a tile of NH 64-byte units of a row: LDS-DMA lanes per row, rows per 1 KB load, rows per round, bytes per
+// ring slot (u = loads per loader wavefront and round: 2 with the whole LDS of a CU, 1 with half of it)
 struct ChainGeom {
     int lpr, rpl, round_rows, row_bytes, slot_bytes;
-    __host__ __device__ ChainGeom(int nl, int u)
-        : lpr(8 * nl), rpl(64 / (8 * nl)), round_rows(u * kChLoaders * (64 / (8 * nl))), row_bytes(128 * nl),
-          slot_bytes(u * kChLoaders * (64 / (8 * nl)) * 128 * nl) {}
+    __host__ __device__ ChainGeom(int nh, int u)
+        : lpr(4 * nh), rpl(64 / (4 * nh)), round_rows(u * kChLoaders * (64 / (4 * nh))), row_bytes(64 * nh),
+          slot_bytes(u * kChLoaders * (64 / (4 * nh)) * 64 * nh) {}
 };
+
+// The dense split of k_colchain: tile t of `grid` owns the 64-byte units [unit0, unit0 + nh) of every row.  With the
+// whole LDS of a CU (u = 2: at most one tile per CU) the units are dealt one by one, so that no tile holds more than one
+// unit above the others (20 000 float32 columns = 1 250 units over 256 CUs: 4 or 5 each, where whole cache lines gave
+// 2 or 3 -- the tiles of three lines set the kernel's time); with half of it (u = 1: more than four lines per CU) in whole
+// cache lines (two units), so that every tile's rows per round stay a multiple of the chain's ten.
+__host__ __device__ inline void chain_tile_units(int t, int grid, int n_units, int u, int& unit0, int& nh) {
+    const int gsz = u == 2 ? 1 : 2;
+    const int n_groups = (n_units + gsz - 1) / gsz;
+    const int g0 = (int)((int64_t)t * n_groups / grid), g1 = (int)((int64_t)(t + 1) * n_groups / grid);
+    unit0 = g0 * gsz;
+    nh = (g1 - g0) * gsz;
+}
+// tile of workgroup b: the dispatcher deals workgroups round robin over the 8 XCDs, so b, b + 8, ... share an L2.
+// Neighbouring tiles share the cache line a unit boundary cuts; taking them on one XCD fetches that line into ONE L2.
+// (A bijection whenever grid % 8 == 0; otherwise the identity.  Placement is a speed matter only.)
+#ifndef ICV_CH_XCD_REMAP
+#define ICV_CH_XCD_REMAP 1
+#endif
+__device__ __forceinline__ int chain_tile_of_block(int b, int grid) {
+    return ICV_CH_XCD_REMAP && grid % 8 == 0 ? (b & 7) * (grid >> 3) + (b >> 3) : b;
+}
 
 // wait until at most n of this wavefront's LDS-DMA loads are outstanding (n wave-uniform, <= 15: the ring depth)
 __device__ __forceinline__ void chain_wait_vmcnt(int n) {
@@ -73,7 +103,7 @@ __device__ __forceinline__ void chain_wait_vmcnt(int n) {
     }
 }
 
-// The chain wavefront's loop for a tile of NL lines, RR rows per round (= ring slot); lane = 8 bytes of the row (2 float32 /
+// The chain wavefront's loop for a tile of NH 64-byte units, RR rows per round (= ring slot); lane = 8 bytes of the row (2 float32 /
 // 1 float64 columns).  Hand-scheduled in chunks of ten rows (the asm operand limit is 30): the ten 8-byte LDS reads of
 // the NEXT ten rows are issued, then the ten dependent adds of the current ten run in their shadow, one lgkmcnt wait per
 // chunk; plain ds_read_b64 (the compiler's merged ds_read2st64_b64 costs four times the LDS cycles).  A lone wavefront
@@ -106,12 +136,12 @@ __device__ __forceinline__ void chain_wait_vmcnt(int n) {
 // FLAGS = false: a workgroup barrier hands every round over (the loaders of k_colchain run in lock step with it).
 // FLAGS = true (k_colchain_csr): ready[slot] == k + 1 says round k is in its slot, *consumed = k + 1 gives it back --
 // LDS words polled with workgroup-scope acquire loads, so that the producers work ahead of each other.
-template <typename T, int NL, int RR, bool FLAGS = false>
+template <typename T, int NH, int RR, bool FLAGS = false>
 __device__ __forceinline__ void chain_rounds(const unsigned char* smem, int n_slots, int64_t n_rounds, int64_t n_sel,
                                              int lane, typename ChainLane<T>::type& a, int* ready = nullptr,
                                              int* consumed = nullptr) {
     typedef typename ChainLane<T>::type lane_t;
-    constexpr int RB = 128 * NL, SLOT = RR * RB;
+    constexpr int RB = 64 * NH, SLOT = RR * RB;
     constexpr int NCH = RR / 10;
     static_assert(RR % 10 == 0, "round rows");
     int slot_i = 0;
@@ -146,17 +176,21 @@ __device__ __forceinline__ void chain_rounds(const unsigned char* smem, int n_sl
             ICV_CH_ADDS(OP, a, va);                                     \
         }                                                               \
     }
+#define ICV_CH_BODY_NH(OP)                                 \
+    if constexpr (NH == 1) { ICV_CH_BODY("64", OP) }       \
+    else if constexpr (NH == 2) { ICV_CH_BODY("128", OP) } \
+    else if constexpr (NH == 3) { ICV_CH_BODY("192", OP) } \
+    else if constexpr (NH == 4) { ICV_CH_BODY("256", OP) } \
+    else if constexpr (NH == 5) { ICV_CH_BODY("320", OP) } \
+    else if constexpr (NH == 6) { ICV_CH_BODY("384", OP) } \
+    else if constexpr (NH == 7) { ICV_CH_BODY("448", OP) } \
+    else { ICV_CH_BODY("512", OP) }
             if constexpr (sizeof(T) == 4) {
-                if constexpr (NL == 1) { ICV_CH_BODY("128", "v_pk_add_f32") }
-                else if constexpr (NL == 2) { ICV_CH_BODY("256", "v_pk_add_f32") }
-                else if constexpr (NL == 3) { ICV_CH_BODY("384", "v_pk_add_f32") }
-                else { ICV_CH_BODY("512", "v_pk_add_f32") }
+                ICV_CH_BODY_NH("v_pk_add_f32")
             } else {
-                if constexpr (NL == 1) { ICV_CH_BODY("128", "v_add_f64") }
-                else if constexpr (NL == 2) { ICV_CH_BODY("256", "v_add_f64") }
-                else if constexpr (NL == 3) { ICV_CH_BODY("384", "v_add_f64") }
-                else { ICV_CH_BODY("512", "v_add_f64") }
+                ICV_CH_BODY_NH("v_add_f64")
             }
+#undef ICV_CH_BODY_NH
 #undef ICV_CH_BODY
         } else {
             for (int i = 0; i < (int)left; ++i) chain_add(a, slot[i * (RB / 8)]);
@@ -221,14 +255,14 @@ __device__ __forceinline__ void chain_rounds_var(const unsigned char* smem, int 
 }
 
 // acc[c] (matrix dtype, in/out: a call continues the chain of the previous one) += rows sel[0..n_sel) of the dense
-// row-major matrix x (sel == nullptr: rows 0..n_sel), in that order.  Workgroup b of gridDim.x owns the cache lines
-// [b * n_lines / grid, (b + 1) * n_lines / grid) of every row (1..4 lines: the caller sizes the grid); `lds_bytes` of
-// dynamic LDS (kChLdsFull / kChLdsHalf) are the ring.
+// row-major matrix x (sel == nullptr: rows 0..n_sel), in that order.  Workgroup b of gridDim.x owns the 64-byte units
+// chain_tile_units(chain_tile_of_block(b)) of every row (1..8 units: the caller sizes the grid, ChainLaunch); `lds_bytes`
+// of dynamic LDS (kChLdsFull / kChLdsHalf) are the ring.
 // tail_row >= 0: the one row whose 16-byte segment loads could run past the end of the buffer (its last row, when the
 // row stride is not a multiple of 16 bytes): it is added last by the chain wavefront with guarded loads.  Without a row
 // list the caller excludes it from n_sel; with one the kernel looks whether the (ascending) list ends with it.
 template <typename T, bool LIST>
-__global__ void __launch_bounds__(kChThreads) k_colchain(const T* __restrict__ x, int64_t ld, int n_cols, int n_lines,
+__global__ void __launch_bounds__(kChThreads) k_colchain(const T* __restrict__ x, int64_t ld, int n_cols, int n_units,
                                                          int lds_bytes, const int32_t* __restrict__ sel, int64_t n_sel,
                                                          int64_t tail_row, T* __restrict__ acc) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -241,11 +275,11 @@ __global__ void __launch_bounds__(kChThreads) k_colchain(const T* __restrict__ x
     constexpr int CPL = 8 / (int)sizeof(T);   // columns per chain lane
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
-    const int line0 = (int)((int64_t)blockIdx.x * n_lines / gridDim.x);
-    const int nl = (int)((int64_t)(blockIdx.x + 1) * n_lines / gridDim.x) - line0;
-    const int c0 = line0 * (128 / (int)sizeof(T));
     const int u = lds_bytes > kChLdsHalf ? 2 : 1;  // (uniform over the grid)
-    const ChainGeom g(nl, u);
+    int unit0, nh;
+    chain_tile_units(chain_tile_of_block((int)blockIdx.x, (int)gridDim.x), (int)gridDim.x, n_units, u, unit0, nh);
+    const int c0 = unit0 * (64 / (int)sizeof(T));
+    const ChainGeom g(nh, u);
     const int n_slots = lds_bytes / g.slot_bytes;
     int depth = n_slots - 1;  // rounds in flight
     if (depth * u > 15) depth = 15 / u;
@@ -270,7 +304,7 @@ __global__ void __launch_bounds__(kChThreads) k_colchain(const T* __restrict__ x
                     const int64_t r0 = round * g.round_rows + (j * kChLoaders + wave) * g.rpl;
                     int32_t rs = 0;
 #pragma unroll
-                    for (int i = 0; i < 8; ++i)
+                    for (int i = 0; i < 16; ++i)  // (rows per load: up to 16, a tile of one 64-byte unit)
                         if (i < g.rpl) {
                             const int64_t ri = r0 + i < n_sel ? r0 + i : n_sel - 1;
                             const int32_t v = sel[ri];
@@ -315,17 +349,27 @@ __global__ void __launch_bounds__(kChThreads) k_colchain(const T* __restrict__ x
             a = col < n_cols ? acc[col] : 0.0;
         }
         const int rl = lane * 8 < g.row_bytes ? lane : 0;  // idle lanes read lane 0's bytes (never stored)
-        constexpr int L = kChLoaders;  // rows per round = loads per round (u x 15) x rows per load (64 / lanes per row)
+        // rows per round = loads per round (u x 15) x rows per load (64 / (4 x units)); a multiple of ten for every nh
+        // of u = 2 and every even nh of u = 1 (chain_tile_units)
+        constexpr int L = kChLoaders;
         if (u == 2) {
-            if (nl == 1) chain_rounds<T, 1, 2 * L * 8>(smem, n_slots, n_rounds, n_sel, rl, a);
-            else if (nl == 2) chain_rounds<T, 2, 2 * L * 4>(smem, n_slots, n_rounds, n_sel, rl, a);
-            else if (nl == 3) chain_rounds<T, 3, 2 * L * 2>(smem, n_slots, n_rounds, n_sel, rl, a);
-            else chain_rounds<T, 4, 2 * L * 2>(smem, n_slots, n_rounds, n_sel, rl, a);
+            switch (nh) {
+                case 1: chain_rounds<T, 1, 2 * L * 16>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                case 2: chain_rounds<T, 2, 2 * L * 8>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                case 3: chain_rounds<T, 3, 2 * L * 5>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                case 4: chain_rounds<T, 4, 2 * L * 4>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                case 5: chain_rounds<T, 5, 2 * L * 3>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                case 6: chain_rounds<T, 6, 2 * L * 2>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                case 7: chain_rounds<T, 7, 2 * L * 2>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                default: chain_rounds<T, 8, 2 * L * 2>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+            }
         } else {
-            if (nl == 1) chain_rounds<T, 1, L * 8>(smem, n_slots, n_rounds, n_sel, rl, a);
-            else if (nl == 2) chain_rounds<T, 2, L * 4>(smem, n_slots, n_rounds, n_sel, rl, a);
-            else if (nl == 3) chain_rounds<T, 3, L * 2>(smem, n_slots, n_rounds, n_sel, rl, a);
-            else chain_rounds<T, 4, L * 2>(smem, n_slots, n_rounds, n_sel, rl, a);
+            switch (nh) {
+                case 2: chain_rounds<T, 2, L * 8>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                case 4: chain_rounds<T, 4, L * 4>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                case 6: chain_rounds<T, 6, L * 2>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+                default: chain_rounds<T, 8, L * 2>(smem, n_slots, n_rounds, n_sel, rl, a); break;
+            }
         }
         if (tail_row >= 0) {
             const T* xr = x + tail_row * ld;
@@ -347,11 +391,15 @@ __global__ void __launch_bounds__(kChThreads) k_colchain(const T* __restrict__ x
     }
 }
 
-// grid and LDS of k_colchain for n_cols columns of `esz` bytes on a device with n_cu compute units
+// grid and LDS of k_colchain for n_cols columns of `esz` bytes on a device with n_cu compute units.  The CSR kernels
+// split the row in whole cache lines (`n_lines`, tile t = [t * n_lines / grid, (t + 1) * n_lines / grid)); the dense
+// kernel in 64-byte units (`dense_grid`, chain_tile_units): with the whole LDS up to one tile per CU, so that 625 lines
+// over 256 CUs become 4 or 5 units per tile instead of 2 or 3 lines.
 struct ChainLaunch {
-    int n_lines, grid, lds_bytes;
+    int n_lines, grid, lds_bytes, n_units, dense_grid;
     ChainLaunch(int n_cols, int esz, int n_cu) {
         n_lines = (int)(((int64_t)n_cols * esz + 127) / 128);
+        n_units = (int)(((int64_t)n_cols * esz + 63) / 64);
         if (n_lines <= kChMaxLines * n_cu) {
             grid = n_lines < n_cu ? n_lines : n_cu;  // one workgroup per CU, the whole LDS each
             lds_bytes = kChLdsFull;
@@ -360,6 +408,8 @@ struct ChainLaunch {
             lds_bytes = grid <= n_cu ? kChLdsFull : kChLdsHalf;
         }
         if (grid < 1) grid = 1;
+        dense_grid = lds_bytes == kChLdsFull ? (n_units < n_cu ? n_units : n_cu) : grid;
+        if (dense_grid < 1) dense_grid = 1;
     }
 };
 
