@@ -470,6 +470,25 @@ int icv_csr_check(const int64_t *indptr, const int32_t *indices, int64_t n_rows,
 int icv_csr_densify(const void *data, int32_t dtype, const int64_t *indptr, const int32_t *indices, const int64_t *rows,
                     int64_t n_sel, int32_t n_cols, float *out, int64_t ldo, void *stream);
 
+/* ---- tl.pca (reference tl/__init__.py:33-75): the two passes over X_cnv ---------------------------------------------
+ * icv_gram_f64: G (n_cols x n_cols, row stride ldg) = X^T X of the rows `m` describes (dense or CSR, float32 or
+ * float64; the row range is the matrix's, as everywhere), summed in float64 with v_mfma_f64_16x16x4_f64; accumulate != 0
+ * adds to G, 0 overwrites it.  G comes out bitwise symmetric.  `panel`: caller-owned device scratch of at least
+ * (n_rows rounded up to 32) x panel_ld elements of panel_dtype, panel_ld >= n_cols rounded up to 64: the rows are
+ * densified into it first.  A float32 panel rounds the values to float32: choose it only for float32-exact values
+ * (float32 input, or X_cnv's float64 widenings of float32 numbers); products of float32 numbers are exact in float64.
+ * The cells are summed in blocks of ICV_GRAM_BLOCK rows, each block's partial tile is added to G in row order with no
+ * atomics: two calls give the same bits, and G summed over several calls equals one call over all rows bit for bit
+ * when every call but the last covers a multiple of ICV_GRAM_BLOCK rows.  No synchronisation.
+ * icv_project: out[q * ldo + c] = sum over row q's entries (stored order; a dense row's nonzero elements in column
+ * order, so both formats give the same bits) of x * v[col * k + c], float64, minus shift[c] when `shift` is not NULL;
+ * written as out_dtype (ICV_F32 / ICV_F64).  v: n_cols x k row-major float64 (device), shift: k float64 (device). */
+#define ICV_GRAM_BLOCK 8192
+int icv_gram_f64(const icv_matrix *m, int32_t panel_dtype, void *panel, int64_t panel_ld, double *g, int64_t ldg,
+                 int32_t accumulate, void *stream);
+int icv_project(const icv_matrix *m, const double *v, int32_t k, const double *shift, int32_t out_dtype, void *out,
+                int64_t ldo, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -1414,3 +1414,108 @@ def profile_collect(plan: GenePlan, max_records=4096):
     n = C.c_int32(0)
     _lib.check(_lib.load().icv_profile_collect(plan.handle, arr, max_records, C.byref(n)))
     return [arr[i] for i in range(n.value)]
+
+
+# ---- tl.pca: X^T X and X V on the device (icv_gram_f64 / icv_project) -------------------------------------------------
+class _PcaInput:
+    """The matrix tl.pca reads, as DeviceMatrix row slabs: a PackedCsr is read where it lies, a host CSR sends indptr /
+    indices / stored values once, a CUDA tensor is used as it is, a host dense array is uploaded slab by slab.
+    ``f32_exact``: the stored values are float32 numbers (a float32 Gram panel holds them without rounding)."""
+
+    def __init__(self, x):
+        torch = _torch()
+        self.host_dense = None
+        if isinstance(x, PackedCsr):
+            ip = x.indptr.cpu().numpy()
+            self.dm = DeviceMatrix(indptr=x.indptr, indices=x.indices, data=x.data, shape=x.shape, indptr_host=ip,
+                                   validate=False)
+            self.f32_exact = True  # X_cnv's values are float32 numbers widened to float64
+        elif isinstance(x, torch.Tensor):
+            if x.dim() != 2:
+                raise ValueError("tl.pca: X must be 2-D")
+            t = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float64)
+            self.dm = DeviceMatrix(dense=t.cuda().contiguous())
+            self.f32_exact = t.dtype == torch.float32
+        elif sp.issparse(x):
+            x = x.tocsr()
+            if x.data.dtype not in (np.float32, np.float64):
+                x = x.astype(np.float64)
+            self.dm = to_device_matrix(x)
+            self.f32_exact = x.data.dtype == np.float32
+        else:
+            a = np.asarray(x)
+            if a.ndim != 2:
+                raise ValueError("tl.pca: X must be 2-D")
+            if a.dtype not in (np.float32, np.float64):
+                a = a.astype(np.float64)
+            self.host_dense, self.dm = np.ascontiguousarray(a), None
+            self.f32_exact = a.dtype == np.float32
+        self.shape = tuple(self.host_dense.shape if self.dm is None else self.dm.shape)
+
+    def slabs(self, rows):
+        """(row0, c_struct) of consecutive slabs of at most `rows` rows."""
+        torch = _torch()
+        n = self.shape[0]
+        for r0 in range(0, n, rows):
+            r1 = min(n, r0 + rows)
+            if self.dm is not None:
+                yield r0, self.dm, self.dm.c_struct(r0, r1)
+            else:
+                dm = DeviceMatrix(dense=torch.from_numpy(self.host_dense[r0:r1]).cuda())
+                yield r0, dm, dm.c_struct()
+
+
+def _gram_rows(inp, esz_panel, ld):
+    """Panel height: a multiple of ICV_GRAM_BLOCK (the Gram's bits do not depend on it) within a quarter of free HBM."""
+    blk = _lib.ICV_GRAM_BLOCK
+    n = inp.shape[0]
+    row_bytes = ld * esz_panel + (inp.shape[1] * inp.host_dense.itemsize if inp.dm is None else 0)
+    fit = max(1, int(free_hbm_bytes() // 4 // (row_bytes * blk)))
+    return min(fit, max(1, -(-n // blk))) * blk
+
+
+def gram(x, zero_center=False):
+    """(G, colsum): the float64 ``W x W`` Gram matrix X^T X (host numpy, bitwise symmetric) and, when ``zero_center``,
+    the float64 column sums (host numpy; None otherwise).  ``x``: PackedCsr, host CSR, host dense or CUDA tensor."""
+    torch = _torch()
+    lib = _lib.load()
+    inp = x if isinstance(x, _PcaInput) else _PcaInput(x)
+    n, w = inp.shape
+    if n < 1 or w < 1:
+        raise ValueError(f"gram: empty matrix of shape {inp.shape}")
+    ld = -(-w // 64) * 64
+    pdt = torch.float32 if inp.f32_exact else torch.float64
+    esz = 4 if inp.f32_exact else 8
+    rows = _gram_rows(inp, esz, ld)
+    g = torch.empty((w, w), dtype=torch.float64, device="cuda")
+    sums = torch.zeros((1, w), dtype=torch.float64, device="cuda") if zero_center else None
+    panel = torch.empty((min(rows, -(-n // 32) * 32) * ld,), dtype=pdt, device="cuda")
+    code = _lib.ICV_F32 if inp.f32_exact else _lib.ICV_F64
+    for r0, dm, m in inp.slabs(rows):
+        _lib.check(lib.icv_gram_f64(C.byref(m), code, _ptr(panel), ld, _ptr(g), w, 0 if r0 == 0 else 1,
+                                    _stream_ptr(torch)))
+        if zero_center:
+            column_sums(dm, sums=sums, row0=r0 if inp.dm is not None else 0,
+                        row1=(r0 + m.n_rows) if inp.dm is not None else None)
+    return g.cpu().numpy(), (sums[0].cpu().numpy() if zero_center else None)
+
+
+def project(x, V, shift=None, dtype=np.float32):
+    """X V - shift (host numpy ``n x k`` of ``dtype``): ``V`` host float64 ``W x k``, ``shift`` host float64 k-vector
+    or None; float64 sums in stored-entry order (icv_project)."""
+    torch = _torch()
+    lib = _lib.load()
+    inp = x if isinstance(x, _PcaInput) else _PcaInput(x)
+    n, w = inp.shape
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    k = V.shape[1]
+    v_d = torch.from_numpy(V).cuda()
+    s_d = torch.from_numpy(np.ascontiguousarray(shift, dtype=np.float64)).cuda() if shift is not None else None
+    tdt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+    out = torch.empty((n, k), dtype=tdt, device="cuda")
+    rows = n if inp.dm is not None else max(1, int(free_hbm_bytes() // 4 // max(1, w * inp.host_dense.itemsize)))
+    for r0, _dm, m in inp.slabs(max(rows, 1)):
+        _lib.check(lib.icv_project(C.byref(m), _ptr(v_d), k, _ptr(s_d),
+                                   _lib.ICV_F32 if tdt == torch.float32 else _lib.ICV_F64, _ptr(out[r0:]), k,
+                                   _stream_ptr(torch)))
+    return out.cpu().numpy()

@@ -32,6 +32,7 @@
 #include "icv_kernel_gene.hpp"
 #include "icv_kernel_blocks.hpp"
 #include "icv_corr.hpp"
+#include "icv_pca.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -2639,6 +2640,89 @@ int icv_csr_densify(const void* data, int32_t dtype, const int64_t* indptr, cons
     else
         hipLaunchKernelGGL(icv::k_csr_densify<double>, grid, block, 0, st, static_cast<const double*>(data), indptr,
                            indices, rows, n_sel, out, ldo);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+static_assert(icv::kPcaKB == ICV_GRAM_BLOCK, "the header's block size is the kernel's");
+
+int icv_gram_f64(const icv_matrix* m, int32_t panel_dtype, void* panel, int64_t panel_ld, double* g, int64_t ldg,
+                 int32_t accumulate, void* stream) {
+    if (!m || !g || m->n_rows < 0 || m->n_cols < 1 || ldg < m->n_cols || (panel_dtype != ICV_F32 && panel_dtype != ICV_F64) ||
+        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR))
+        return fail(ICV_ERR_INVALID, "bad gram_f64 arguments");
+    const int n = m->n_cols, n_t = (n + icv::kPcaT - 1) / icv::kPcaT, n_tri = n_t * (n_t + 1) / 2;
+    if (m->n_rows > 0 && (!panel || panel_ld < (int64_t)n_t * icv::kPcaT))
+        return fail(ICV_ERR_INVALID, "gram_f64: the panel needs a row stride of at least n_cols rounded up to 64");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m->n_rows == 0) {
+        if (!accumulate) hipLaunchKernelGGL(icv::k_gram_reduce, dim3((unsigned)n_tri), dim3(256), 0, st, nullptr, 0, n_t,
+                                            n, g, ldg, 0);
+        HIP_TRY(hipGetLastError());
+        return ICV_OK;
+    }
+    const int64_t rows = m->n_rows, n_pad = (rows + icv::kPcaKC - 1) / icv::kPcaKC * icv::kPcaKC;
+    const size_t esz = panel_dtype == ICV_F32 ? 4 : 8;
+    HIP_TRY(hipMemsetAsync(panel, 0, (size_t)n_pad * panel_ld * esz, st));
+    const dim3 rgrid((unsigned)((rows + 3) / 4)), rblock(256);
+#define ICV_PANEL(T, P)                                                                                                \
+    if (m->format == ICV_CSR)                                                                                          \
+        hipLaunchKernelGGL((icv::k_pca_panel_csr<T, P>), rgrid, rblock, 0, st, (const T*)m->values, m->indptr,       \
+                           m->indices, rows, (P*)panel, panel_ld);                                                     \
+    else                                                                                                               \
+        hipLaunchKernelGGL((icv::k_pca_panel_dense<T, P>), rgrid, rblock, 0, st, (const T*)m->values, m->ld, rows, n, \
+                           (P*)panel, panel_ld);
+    if (m->dtype == ICV_F32 && panel_dtype == ICV_F32) { ICV_PANEL(float, float) }
+    else if (m->dtype == ICV_F32) { ICV_PANEL(float, double) }
+    else if (panel_dtype == ICV_F32) { ICV_PANEL(double, float) }
+    else { ICV_PANEL(double, double) }
+#undef ICV_PANEL
+    HIP_TRY(hipGetLastError());
+    // partial tiles of up to 256 MB per launch pair; the reduction adds them to G in block order either way
+    const int64_t n_blocks = (n_pad + icv::kPcaKB - 1) / icv::kPcaKB;
+    const size_t tile_bytes = (size_t)n_tri * icv::kPcaT * icv::kPcaT * sizeof(double);
+    int64_t per = (int64_t)((256ull << 20) / tile_bytes);
+    per = per < 1 ? 1 : (per > n_blocks ? n_blocks : per);
+    AsyncBuf part_b;
+    HIP_TRY(part_b.alloc((size_t)per * tile_bytes, st));
+    for (int64_t b0 = 0; b0 < n_blocks; b0 += per) {
+        const int64_t nb = per < n_blocks - b0 ? per : n_blocks - b0;
+        const int64_t c0 = b0 * icv::kPcaKB;
+        const int64_t np = n_pad - c0 < nb * icv::kPcaKB ? n_pad - c0 : nb * icv::kPcaKB;
+        const dim3 grid((unsigned)n_tri, (unsigned)nb);
+        if (panel_dtype == ICV_F32)
+            hipLaunchKernelGGL(icv::k_gram_f64<float>, grid, dim3(256), 0, st, (const float*)panel + c0 * panel_ld,
+                               panel_ld, np, n_t, part_b.as<double>());
+        else
+            hipLaunchKernelGGL(icv::k_gram_f64<double>, grid, dim3(256), 0, st, (const double*)panel + c0 * panel_ld,
+                               panel_ld, np, n_t, part_b.as<double>());
+        hipLaunchKernelGGL(icv::k_gram_reduce, dim3((unsigned)n_tri), dim3(256), 0, st, part_b.as<double>(), (int)nb,
+                           n_t, n, g, ldg, (accumulate || b0 > 0) ? 1 : 0);
+    }
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_project(const icv_matrix* m, const double* v, int32_t k, const double* shift, int32_t out_dtype, void* out,
+                int64_t ldo, void* stream) {
+    if (!m || !v || !out || k < 1 || ldo < k || m->n_rows < 0 || (out_dtype != ICV_F32 && out_dtype != ICV_F64) ||
+        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR))
+        return fail(ICV_ERR_INVALID, "bad project arguments");
+    if (m->n_rows == 0) return ICV_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((m->n_rows + 3) / 4)), block(256);
+#define ICV_PROJ(T, O)                                                                                                 \
+    if (m->format == ICV_CSR)                                                                                          \
+        hipLaunchKernelGGL((icv::k_csr_project<T, O>), grid, block, 0, st, (const T*)m->values, m->indptr, m->indices, \
+                           m->n_rows, v, k, shift, (O*)out, ldo);                                                      \
+    else                                                                                                               \
+        hipLaunchKernelGGL((icv::k_dense_project<T, O>), grid, block, 0, st, (const T*)m->values, m->ld, m->n_rows,   \
+                           m->n_cols, v, k, shift, (O*)out, ldo);
+    if (m->dtype == ICV_F32 && out_dtype == ICV_F32) { ICV_PROJ(float, float) }
+    else if (m->dtype == ICV_F32) { ICV_PROJ(float, double) }
+    else if (out_dtype == ICV_F32) { ICV_PROJ(double, float) }
+    else { ICV_PROJ(double, double) }
+#undef ICV_PROJ
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
