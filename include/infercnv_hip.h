@@ -489,6 +489,43 @@ int icv_gram_f64(const icv_matrix *m, int32_t panel_dtype, void *panel, int64_t 
 int icv_project(const icv_matrix *m, const double *v, int32_t k, const double *shift, int32_t out_dtype, void *out,
                 int64_t ldo, void *stream);
 
+/* ---- pp.neighbors (reference pp/__init__.py:8-43; csrc/icv_knn.hpp) ------------------------------------
+ * The EXACT k - 1 nearest other rows of every row of x (n x d float32, row stride ld; 2 <= k <= min(n, 64),
+ * 1 <= d <= 256, n up to 2^30 by the index types):
+ *   d2(i, j) = float64 sum over the columns, in order, no fused multiply-add, of (double(x_ic) - double(x_jc))^2;
+ *   row i's neighbours are the j != i with the smallest (d2, j), listed in that order in knn_idx[i * (k - 1) + r]
+ *   (int32) with knn_dist = float32(sqrt(d2)).  A pure function of x.
+ * Stages: column-centred float32 copies; an fp32 MFMA sweep that keeps, per row and column part, the k - 1 + 8 smallest
+ * LOWER BOUNDS of d2 (the n x n matrix is never stored); float64 re-ranking of those candidates; a certificate per
+ * row (every cell that is not a candidate is provably farther than the (k-1)-th neighbour); the rows that fail it go
+ * through an exact kernel against all n cells.  *n_exact (host, optional) = number of such rows: correctness does
+ * not depend on it, speed does.  stage_ms (host, optional): float[4] = milliseconds of centring, sweep, re-ranking,
+ * exact kernel.  The call synchronises the stream once (it reads the count of uncertified rows).
+ * workspace: caller-owned device buffer of icv_knn_workspace(n, d, k) bytes, linear in n: per cell 4 DP (the centred
+ * copy, DP = d rounded up to 64 / 128 / 256) + 4 (norm) + parts * (8 (k + 7) + 8) (candidates and bounds; parts = 1
+ * above 131 072 cells, up to 16 for small n) + 4 (row list), n rounded up to 128. */
+int icv_knn_workspace(int64_t n, int32_t d, int32_t k, int64_t *bytes);
+int icv_knn(const float *x, int64_t n, int32_t d, int64_t ld, int32_t k, void *workspace, int32_t *knn_idx,
+            float *knn_dist, int32_t *n_exact, float *stage_ms, void *stream);
+/* UMAP's smooth_knn_dist + membership strengths on the stored float32 distances of icv_knn (rows ascending), float64,
+ * one lane per row: rho[i] = smallest positive distance (0: none); sigma[i] by the bisection of DESIGN.md 4.9 rule 5
+ * with its floor (the mean over ALL distances is summed in a fixed order: rows in order per thread of one workgroup,
+ * then a tree); weights[i * (k - 1) + r] = 1 where dist - rho <= 0, else exp(-(dist - rho) / sigma).
+ * 8 (n + 1) bytes of temporary device memory (stream-ordered).  No synchronisation. */
+int icv_knn_fuzzy(const float *knn_dist, int64_t n, int32_t k, double *rho, double *sigma, double *weights,
+                  void *stream);
+/* C = A + A^T - A o A^T (A = the weights at the columns knn_idx) as canonical CSR, float32, entries that round to 0
+ * not stored.  Two calls around icv_row_offsets: _count writes row_nnz[n] (integer atomics), _fill writes
+ * indices / data for the nnz = indptr[n] entries (any fill order, then every row sorted by column: the result does
+ * not depend on scheduling).  _fill: 4 n + 8 nnz bytes of temporary device memory.  No synchronisation. */
+int icv_knn_symmetrize_count(const int32_t *knn_idx, const double *weights, int64_t n, int32_t k, int64_t *row_nnz,
+                             void *stream);
+int icv_knn_symmetrize_fill(const int32_t *knn_idx, const double *weights, int64_t n, int32_t k,
+                            const int64_t *indptr, int64_t nnz, int32_t *indices, float *data, void *stream);
+/* every CSR row's (column, value) pairs by ascending column (distinct columns per row; out of place) */
+int icv_knn_sort_rows(const int64_t *indptr, int64_t n, const int32_t *cols_in, const float *vals_in, int32_t *cols,
+                      float *vals, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -1,7 +1,7 @@
 """Minimal AnnData stand-in.
 
 ``anndata`` is not a dependency of this package: the tool functions only touch the attributes
-``X, layers, obs, var, var_names, obsm, uns, shape`` and work with a real ``anndata.AnnData`` as well
+``X, layers, obs, var, var_names, obsm, obsp, uns, shape`` and work with a real ``anndata.AnnData`` as well
 as with this container (used by ``bench.py``, ``__graft_entry__.smoke()`` and the tests, where anndata
 is not installed).
 """
@@ -11,7 +11,7 @@ import pandas as pd
 
 
 class SimpleAnnData:
-    def __init__(self, X, obs=None, var=None, layers=None, obsm=None, uns=None):
+    def __init__(self, X, obs=None, var=None, layers=None, obsm=None, uns=None, obsp=None):
         self.X = X
         n_obs, n_var = X.shape
         self.obs = obs if obs is not None else pd.DataFrame(index=[str(i) for i in range(n_obs)])
@@ -19,6 +19,7 @@ class SimpleAnnData:
         self.layers = dict(layers or {})
         self.obsm = dict(obsm or {})
         self.uns = dict(uns or {})
+        self.obsp = dict(obsp or {})
 
     @property
     def shape(self):

@@ -1519,3 +1519,82 @@ def project(x, V, shift=None, dtype=np.float32):
                                    _lib.ICV_F32 if tdt == torch.float32 else _lib.ICV_F64, _ptr(out[r0:]), k,
                                    _stream_ptr(torch)))
     return out.cpu().numpy()
+
+
+# ---- pp.neighbors: exact kNN and UMAP's fuzzy graph on the device (icv_knn*) -------------------------------------------
+def knn(x, n_neighbors, stage_ms=None):
+    """(knn_indices, knn_distances, n_exact): the ``n_neighbors - 1`` exact nearest neighbours of every row of the
+    device float32 matrix ``x`` (DESIGN.md 4.9 rules 1-3) as device tensors n x (k - 1) (int32, nearest first /
+    float32), and the number of rows the certificate sent to the exact kernel.  ``stage_ms``: a list that receives the
+    milliseconds of (centring, candidate sweep, re-rank, exact fallback)."""
+    torch = _torch()
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and (x.stride(1) == 1 or x.shape[1] <= 1)
+    n, d = x.shape
+    k = int(n_neighbors)
+    need = C.c_int64(0)
+    _lib.check(lib.icv_knn_workspace(n, d, k, C.byref(need)))
+    with torch.cuda.device(x.device):
+        ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+        idx = torch.empty((n, k - 1), dtype=torch.int32, device="cuda")
+        dist = torch.empty((n, k - 1), dtype=torch.float32, device="cuda")
+        n_exact = C.c_int32(0)
+        ms = (C.c_float * 4)() if stage_ms is not None else None
+        _lib.check(lib.icv_knn(_ptr(x), n, d, x.stride(0), k, _ptr(ws), _ptr(idx), _ptr(dist), C.byref(n_exact), ms,
+                               _stream_ptr(torch)))
+    if stage_ms is not None:
+        stage_ms[:] = [float(v) for v in ms]
+    return idx, dist, int(n_exact.value)
+
+
+def knn_fuzzy(knn_dist, n_neighbors):
+    """(rho, sigma, weights) of rule 5 for the device distances of :func:`knn`: float64 device tensors n, n and
+    n x (k - 1)."""
+    torch = _torch()
+    lib = _lib.load()
+    n, km1 = knn_dist.shape
+    assert knn_dist.is_cuda and knn_dist.dtype == torch.float32 and knn_dist.is_contiguous() and km1 == n_neighbors - 1
+    with torch.cuda.device(knn_dist.device):
+        rho = torch.empty(n, dtype=torch.float64, device="cuda")
+        sigma = torch.empty(n, dtype=torch.float64, device="cuda")
+        w = torch.empty((n, km1), dtype=torch.float64, device="cuda")
+        _lib.check(lib.icv_knn_fuzzy(_ptr(knn_dist), n, int(n_neighbors), _ptr(rho), _ptr(sigma), _ptr(w),
+                                     _stream_ptr(torch)))
+    return rho, sigma, w
+
+
+def knn_symmetrize(knn_idx, weights, n_neighbors):
+    """C = A + A^T - A o A^T of the membership strengths as canonical CSR, float32, no stored zeros: device tensors
+    (indptr int64, indices int32, data float32)."""
+    torch = _torch()
+    lib = _lib.load()
+    n, km1 = knn_idx.shape
+    k = int(n_neighbors)
+    assert knn_idx.is_cuda and knn_idx.dtype == torch.int32 and knn_idx.is_contiguous() and km1 == k - 1
+    assert weights.dtype == torch.float64 and weights.is_contiguous() and tuple(weights.shape) == (n, km1)
+    with torch.cuda.device(knn_idx.device):
+        st = _stream_ptr(torch)
+        counts = torch.empty(n, dtype=torch.int64, device="cuda")
+        _lib.check(lib.icv_knn_symmetrize_count(_ptr(knn_idx), _ptr(weights), n, k, _ptr(counts), st))
+        indptr = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+        _lib.check(lib.icv_row_offsets(_ptr(counts), n, _ptr(indptr), st))
+        nnz = int(indptr[-1].item())
+        indices = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
+        data = torch.empty(max(nnz, 1), dtype=torch.float32, device="cuda")
+        _lib.check(lib.icv_knn_symmetrize_fill(_ptr(knn_idx), _ptr(weights), n, k, _ptr(indptr), nnz, _ptr(indices),
+                                               _ptr(data), st))
+    return indptr, indices[:nnz], data[:nnz]
+
+
+def knn_sorted_rows(knn_idx, knn_dist):
+    """The rows of (knn_idx, knn_dist) reordered by ascending column: the indices / data of the distances CSR."""
+    torch = _torch()
+    lib = _lib.load()
+    n, km1 = knn_idx.shape
+    with torch.cuda.device(knn_idx.device):
+        indptr = torch.arange(n + 1, dtype=torch.int64, device="cuda") * km1
+        cols = torch.empty_like(knn_idx)
+        vals = torch.empty_like(knn_dist)
+        _lib.check(lib.icv_knn_sort_rows(_ptr(indptr), n, _ptr(knn_idx), _ptr(knn_dist), _ptr(cols), _ptr(vals),
+                                         _stream_ptr(torch)))
+    return indptr, cols.reshape(-1), vals.reshape(-1)

@@ -37,6 +37,8 @@ EXPORTS = (
     "icv_ward_create", "icv_ward_destroy", "icv_ward_merge", "icv_ward_gather", "icv_ward_scatter", "icv_ward_scan", "icv_ward_pack_nn",
     "icv_ward_unpack_nn", "icv_ward_pairs", "icv_ward_round_pairs", "icv_ward_finish", "icv_row_abs_sum", "icv_csr_row_abs_sum", "icv_group_sums", "icv_csr_check", "icv_csr_densify", "icv_gram_f64", "icv_project", "icv_host_dense_row_nnz", "icv_host_dense_pack", "icv_host_dense_pack_fused", "icv_csr_scatter_dense", "icv_last_error", "icv_version",
     "icv_device_count", "icv_developer_knobs_reload",
+    "icv_knn_workspace", "icv_knn", "icv_knn_fuzzy", "icv_knn_symmetrize_count", "icv_knn_symmetrize_fill",
+    "icv_knn_sort_rows",
 )
 
 
@@ -154,6 +156,12 @@ def load():
     lib.icv_host_dense_pack.argtypes = [vp, i32, i64, i64, i64, vp, vp, vp, i32]
     lib.icv_host_dense_pack_fused.argtypes = [vp, i32, i64, i64, i64, vp, vp, vp, i64, i32, vp]
     lib.icv_csr_scatter_dense.argtypes = [vp, i32, vp, vp, i64, i32, vp, i64, vp]
+    lib.icv_knn_workspace.argtypes = [i64, i32, i32, P(i64)]
+    lib.icv_knn.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, P(i32), P(C.c_float), vp]
+    lib.icv_knn_fuzzy.argtypes = [vp, i64, i32, vp, vp, vp, vp]
+    lib.icv_knn_symmetrize_count.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.icv_knn_symmetrize_fill.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp, vp]
+    lib.icv_knn_sort_rows.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

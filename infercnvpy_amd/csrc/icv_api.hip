@@ -33,6 +33,7 @@
 #include "icv_kernel_blocks.hpp"
 #include "icv_corr.hpp"
 #include "icv_pca.hpp"
+#include "icv_knn.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -3175,6 +3176,188 @@ int icv_group_sums(const double* values, const int32_t* group, int64_t n, int32_
     if (n_groups == 0) return ICV_OK;
     hipLaunchKernelGGL(icv::k_group_sums, dim3((unsigned)n_groups), dim3(1024), 0, static_cast<hipStream_t>(stream),
                        values, group, n, sums, counts);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+}  // extern "C"
+
+// ---- pp.neighbors (csrc/icv_knn.hpp) ---------------------------------------------------------------------------------
+namespace {
+struct KnnGeom {
+    int dp, nk, L, parts, n_slabs;
+    int64_t n_pad, chunk, rows_per;
+    size_t off_partial, off_mu, off_flags, off_z, off_snorm, off_cand, off_bound, off_redo, bytes;
+    KnnGeom(int64_t n, int d, int k) {
+        dp = d <= 64 ? 64 : d <= 128 ? 128 : 256;
+        nk = dp / 8;
+        L = k - 1 + icv::kKnnSlack;
+        n_pad = (n + icv::kKnnRows - 1) / icv::kKnnRows * icv::kKnnRows;
+        const int64_t gx = n_pad / icv::kKnnRows;
+        int64_t want = 2048 / gx;
+        want = want < 1 ? 1 : want > icv::kKnnMaxParts ? icv::kKnnMaxParts : want;
+        chunk = ((n_pad + want - 1) / want + 31) / 32 * 32;
+        parts = (int)((n_pad + chunk - 1) / chunk);
+        rows_per = (n + 1023) / 1024;
+        if (rows_per < 64) rows_per = 64;
+        n_slabs = (int)((n + rows_per - 1) / rows_per);
+        size_t o = 0;
+        auto seg = [&](size_t b) {
+            const size_t at = o;
+            o += (b + 255) / 256 * 256;
+            return at;
+        };
+        off_partial = seg((size_t)n_slabs * d * 8);
+        off_mu = seg(256 * 4);
+        off_flags = seg(16);
+        off_z = seg((size_t)n_pad * dp * 4);
+        off_snorm = seg((size_t)n_pad * 4);
+        off_cand = seg((size_t)n * parts * 2 * L * 4);
+        off_bound = seg((size_t)n * parts * 2 * 4);
+        off_redo = seg((size_t)n * 4);
+        bytes = o;
+    }
+};
+int knn_args_ok(int64_t n, int32_t d, int32_t k) {
+    return n >= 2 && n <= (int64_t)1 << 30 && d >= 1 && d <= 256 && k >= 2 && k <= 64 && k <= n;
+}
+}  // namespace
+
+extern "C" {
+
+int icv_knn_workspace(int64_t n, int32_t d, int32_t k, int64_t* bytes) {
+    if (!bytes || !knn_args_ok(n, d, k)) return fail(ICV_ERR_INVALID, "bad knn_workspace arguments");
+    *bytes = (int64_t)KnnGeom(n, d, k).bytes;
+    return ICV_OK;
+}
+
+int icv_knn(const float* x, int64_t n, int32_t d, int64_t ld, int32_t k, void* workspace, int32_t* knn_idx,
+            float* knn_dist, int32_t* n_exact, float* stage_ms, void* stream) {
+    if (!x || !workspace || !knn_idx || !knn_dist || !knn_args_ok(n, d, k) || ld < d)
+        return fail(ICV_ERR_INVALID, "bad knn arguments (2 <= k <= min(n, 64), 1 <= d <= 256)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const KnnGeom G(n, d, k);
+    char* ws = static_cast<char*>(workspace);
+    double* partial = reinterpret_cast<double*>(ws + G.off_partial);
+    float* mu = reinterpret_cast<float*>(ws + G.off_mu);
+    unsigned* maxbits = reinterpret_cast<unsigned*>(ws + G.off_flags);
+    unsigned* n_redo = maxbits + 1;
+    float* z = reinterpret_cast<float*>(ws + G.off_z);
+    float* snorm = reinterpret_cast<float*>(ws + G.off_snorm);
+    int32_t* cand = reinterpret_cast<int32_t*>(ws + G.off_cand);
+    float* bound = reinterpret_cast<float*>(ws + G.off_bound);
+    int32_t* redo = reinterpret_cast<int32_t*>(ws + G.off_redo);
+    const int km1 = k - 1;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int i = 0; i < 5; ++i)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } ev_guard{ev};
+    auto mark = [&](int i) -> hipError_t {
+        if (!stage_ms) return hipSuccess;
+        hipError_t e = hipEventCreate(&ev[i]);
+        return e != hipSuccess ? e : hipEventRecord(ev[i], st);
+    };
+
+    HIP_TRY(mark(0));
+    hipLaunchKernelGGL(icv::k_knn_colsum, dim3((unsigned)G.n_slabs), dim3(256), 0, st, x, n, d, ld, G.rows_per, partial);
+    hipLaunchKernelGGL(icv::k_knn_mean, dim3(1), dim3(256), 0, st, partial, G.n_slabs, d, n, mu, maxbits);
+    const double cfac = (double)(G.dp + 16) * 5.9604644775390625e-08;  // (DP + 16) 2^-24
+    hipLaunchKernelGGL(icv::k_knn_center, dim3((unsigned)(G.n_pad / 256 + 1)), dim3(256), 0, st, x, n, G.n_pad, d, ld, G.dp,
+                       mu, cfac, z, snorm, maxbits);
+    HIP_TRY(hipMemsetAsync(n_redo, 0, sizeof(unsigned), st));
+    HIP_TRY(mark(1));
+    const size_t lds = (size_t)4 * 2 * G.L * 64 * 4;
+    const dim3 grid((unsigned)(G.n_pad / icv::kKnnRows), (unsigned)G.parts);
+#define ICV_KNN_SWEEP(NK)                                                                                              \
+    {                                                                                                                  \
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(icv::k_knn_candidates<NK>),                          \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
+        hipLaunchKernelGGL(icv::k_knn_candidates<NK>, grid, dim3(256), lds, st, z, snorm, n, G.n_pad, G.chunk, G.L,    \
+                           cand, bound);                                                                               \
+    }
+    if (G.nk == 8) ICV_KNN_SWEEP(8)
+    else if (G.nk == 16) ICV_KNN_SWEEP(16)
+    else ICV_KNN_SWEEP(32)
+#undef ICV_KNN_SWEEP
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(mark(2));
+    const size_t lds_r = (size_t)G.parts * 2 * G.L * 12;
+    hipLaunchKernelGGL(icv::k_knn_rerank, dim3((unsigned)n), dim3(64), lds_r, st, x, n, d, ld, cand, bound, G.parts, G.L,
+                       km1, maxbits, knn_idx, knn_dist, redo, n_redo);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(mark(3));
+    unsigned h_redo = 0;
+    HIP_TRY(hipMemcpyAsync(&h_redo, n_redo, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_redo > 0) {
+        hipLaunchKernelGGL(icv::k_knn_exact, dim3(h_redo), dim3(256), 0, st, x, n, d, ld, km1, redo, knn_idx, knn_dist);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(mark(4));
+    if (n_exact) *n_exact = (int32_t)h_redo;
+    if (stage_ms) {
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(stage_ms + i, ev[i], ev[i + 1]));
+    }
+    return ICV_OK;
+}
+
+int icv_knn_fuzzy(const float* knn_dist, int64_t n, int32_t k, double* rho, double* sigma, double* weights, void* stream) {
+    if (!knn_dist || !rho || !sigma || !weights || n < 1 || k < 2 || k > 64)
+        return fail(ICV_ERR_INVALID, "bad knn_fuzzy arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AsyncBuf tmp;
+    HIP_TRY(tmp.alloc((size_t)(n + 1) * sizeof(double), st));
+    double* rowsum = tmp.as<double>();
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(icv::k_knn_rowsum, grid, dim3(256), 0, st, knn_dist, n, k - 1, rowsum);
+    hipLaunchKernelGGL(icv::k_knn_total, dim3(1), dim3(1024), 0, st, rowsum, n, rowsum + n);
+    hipLaunchKernelGGL(icv::k_knn_smooth, grid, dim3(256), 0, st, knn_dist, n, k - 1, rowsum, rowsum + n, rho, sigma, weights);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_knn_symmetrize_count(const int32_t* knn_idx, const double* weights, int64_t n, int32_t k, int64_t* row_nnz,
+                             void* stream) {
+    if (!knn_idx || !weights || !row_nnz || n < 1 || k < 2 || k > 64)
+        return fail(ICV_ERR_INVALID, "bad knn_symmetrize_count arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(row_nnz, 0, (size_t)n * sizeof(int64_t), st));
+    hipLaunchKernelGGL(icv::k_knn_sym_count, dim3((unsigned)((n * (k - 1) + 255) / 256)), dim3(256), 0, st, knn_idx, weights,
+                       n, k - 1, reinterpret_cast<unsigned long long*>(row_nnz));
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_knn_symmetrize_fill(const int32_t* knn_idx, const double* weights, int64_t n, int32_t k, const int64_t* indptr,
+                            int64_t nnz, int32_t* indices, float* data, void* stream) {
+    if (!knn_idx || !weights || !indptr || !indices || !data || n < 1 || k < 2 || k > 64 || nnz < 0 ||
+        nnz > 2 * n * (int64_t)(k - 1))
+        return fail(ICV_ERR_INVALID, "bad knn_symmetrize_fill arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AsyncBuf cur, tc, tv;
+    HIP_TRY(cur.alloc((size_t)n * sizeof(unsigned), st));
+    HIP_TRY(tc.alloc((size_t)nnz * sizeof(int32_t), st));
+    HIP_TRY(tv.alloc((size_t)nnz * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(cur.p, 0, (size_t)n * sizeof(unsigned), st));
+    hipLaunchKernelGGL(icv::k_knn_sym_fill, dim3((unsigned)((n * (k - 1) + 255) / 256)), dim3(256), 0, st, knn_idx, weights,
+                       n, k - 1, indptr, cur.as<unsigned>(), tc.as<int32_t>(), tv.as<float>());
+    hipLaunchKernelGGL(icv::k_knn_sort_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, indptr, n, tc.as<int32_t>(),
+                       tv.as<float>(), indices, data);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_knn_sort_rows(const int64_t* indptr, int64_t n, const int32_t* cols_in, const float* vals_in, int32_t* cols,
+                      float* vals, void* stream) {
+    if (!indptr || !cols_in || !vals_in || !cols || !vals || n < 1 || cols_in == cols || vals_in == vals)
+        return fail(ICV_ERR_INVALID, "bad knn_sort_rows arguments");
+    hipLaunchKernelGGL(icv::k_knn_sort_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       indptr, n, cols_in, vals_in, cols, vals);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
