@@ -526,6 +526,36 @@ int icv_knn_symmetrize_fill(const int32_t *knn_idx, const double *weights, int64
 int icv_knn_sort_rows(const int64_t *indptr, int64_t n, const int32_t *cols_in, const float *vals_in, int32_t *cols,
                       float *vals, void *stream);
 
+/* ---- tl.leiden: deterministic Leiden of a symmetric weighted graph, every phase on the device ------
+ * icv_leiden_quantise validates the CSR graph (rule 1: rows strictly ascending, finite, non-negative, no diagonal,
+ * symmetric pattern and values; each violation ICV_ERR_INVALID) and writes the integer graph of rule 2 (float32
+ * rounding, w = rint(v 2^32), entries with w = 0 dropped): q_indptr (n + 1), q_indices / q_weights (capacity nnz).
+ * result (host): [0] stored entries kept, [1] 2m = sum of the weights.  dtype: ICV_F32 / ICV_F64 of data.
+ * icv_leiden_iteration runs ONE iteration (local moving, refinement, aggregation, level by level) from the partition
+ * in labels (device, int32 n, ids in [0, n)) and writes the new one there (ids in [0, n), not renumbered).  gom =
+ * resolution / double(2m); seed = random_state; trace (host, 3 * 64 int32) receives per level (vertices, rounds of
+ * local moving, rounds of refinement), *n_levels the count, *n_moves the local-moving moves of all levels (0: the
+ * iteration changed nothing), *bound_reached whether a bound of rule 5 ended a phase.  stage_ms (host, optional):
+ * float[4] = local moving, refinement, aggregation, the rest.  The host reads two scalars per round.  Rows of any
+ * length: up to 512 entries a wavefront combines the row in LDS, longer rows take a workgroup and a table in the
+ * workspace.
+ * workspace: icv_leiden_workspace(n, nnz) bytes = 128 n + 80 nnz + O(1) (two aggregate graphs, the per-vertex
+ * arrays, the sort buffers, 24 nnz of tables for the long rows).  Outside it, from the stream's memory pool: the
+ * temporaries of the sort / segmented-sum / scan primitives, 8 (n + nnz) in icv_leiden_quantise, 36 n in
+ * icv_leiden_renumber.
+ * icv_leiden_sums: e[c] = weight inside label c (both directions), K[c] = its strength (device int64, n each).
+ * icv_leiden_renumber: rule 6 (decreasing size, ties by the smallest member); *n_communities on the host. */
+int icv_leiden_workspace(int64_t n, int64_t nnz, int64_t *bytes);
+int icv_leiden_quantise(const int64_t *indptr, const int32_t *indices, const void *data, int32_t dtype, int64_t n,
+                        int64_t nnz, int32_t use_weights, int64_t *q_indptr, int32_t *q_indices, int64_t *q_weights,
+                        int64_t *result, void *stream);
+int icv_leiden_iteration(const int64_t *indptr, const int32_t *indices, const int64_t *weights, int64_t n, int64_t nnz,
+                         double gom, uint64_t seed, int32_t iteration, int32_t *labels, void *workspace, int32_t *trace,
+                         int32_t *n_levels, int64_t *n_moves, int32_t *bound_reached, float *stage_ms, void *stream);
+int icv_leiden_sums(const int64_t *indptr, const int32_t *indices, const int64_t *weights, int64_t n,
+                    const int32_t *labels, int64_t *e, int64_t *K, void *stream);
+int icv_leiden_renumber(const int32_t *labels, int64_t n, int32_t *out, int32_t *n_communities, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

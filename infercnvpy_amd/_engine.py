@@ -1598,3 +1598,91 @@ def knn_sorted_rows(knn_idx, knn_dist):
         _lib.check(lib.icv_knn_sort_rows(_ptr(indptr), n, _ptr(knn_idx), _ptr(knn_dist), _ptr(cols), _ptr(vals),
                                          _stream_ptr(torch)))
     return indptr, cols.reshape(-1), vals.reshape(-1)
+
+
+# ---- tl.leiden: Leiden on the device (icv_leiden*) --------------------------------------------------------
+LEIDEN_MAX_ITERATIONS = 64
+
+
+def leiden_quality(e, K, resolution):
+    """Q of rule 3 from the communities' integer sums (math.fsum: exactly rounded, independent of the order)."""
+    M = sum(K)
+    if M == 0:
+        return 0.0
+    Mf = float(M)
+    return math.fsum((float(ec) - resolution * float(kc) * float(kc) / Mf) / Mf for ec, kc in zip(e, K))
+
+
+def leiden(indptr, indices, data, resolution=1.0, random_state=0, n_iterations=-1, use_weights=True, stages=None):
+    """(labels, info) of DESIGN.md 4.10 for the device CSR graph (indptr int64 n + 1, indices int32, data float32 /
+    float64; rows sorted): labels is a device int32 tensor numbered by rule 6.  ``stages``: a list that receives one
+    dict of milliseconds per iteration."""
+    torch = _torch()
+    lib = _lib.load()
+    n = indptr.numel() - 1
+    nnz = indices.numel()
+    assert indptr.is_cuda and indptr.dtype == torch.int64 and indices.dtype == torch.int32 and data.numel() == nnz
+    assert data.dtype in (torch.float32, torch.float64) and n >= 1
+    # the kernels trust the row pointers: check them here (two scalars and one comparison on the device)
+    if int(indptr[0].item()) != 0 or int(indptr[-1].item()) != nnz or bool((indptr[1:] < indptr[:-1]).any().item()):
+        raise ValueError("tl.leiden: indptr must start at 0, be non-decreasing and end at the number of stored entries")
+    if nnz >= 1 << 31:
+        raise ValueError("tl.leiden: at most 2^31 - 1 stored entries are supported")
+    seed = int(random_state) & ((1 << 64) - 1)
+    info = {"quality": [], "n_iterations": 0, "levels": [], "rounds": [], "bound_reached": False}
+    with torch.cuda.device(indptr.device):
+        st = _stream_ptr(torch)
+        indptr, indices, data = indptr.contiguous(), indices.contiguous(), data.contiguous()
+        q_indptr = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+        q_indices = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
+        q_w = torch.empty(max(nnz, 1), dtype=torch.int64, device="cuda")
+        res = (C.c_int64 * 2)()
+        t0 = _time.perf_counter()
+        _lib.check(lib.icv_leiden_quantise(_ptr(indptr), _ptr(indices), _ptr(data),
+                                           _lib.ICV_F32 if data.dtype == torch.float32 else _lib.ICV_F64, n, nnz,
+                                           int(bool(use_weights)), _ptr(q_indptr), _ptr(q_indices), _ptr(q_w), res, st))
+        quantise_ms = (_time.perf_counter() - t0) * 1e3
+        kept, M = int(res[0]), int(res[1])
+        labels = torch.arange(n, dtype=torch.int32, device="cuda")
+        out = labels  # without weight: n singletons, numbered by rule 6 already
+        n_comm = C.c_int32(n)
+        if M > 0:
+            gom = float(resolution) / float(M)
+            need = C.c_int64(0)
+            _lib.check(lib.icv_leiden_workspace(n, kept, C.byref(need)))
+            ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+            out = torch.empty_like(labels)
+            info["workspace_bytes"] = int(need.value)
+            e = torch.empty(n, dtype=torch.int64, device="cuda")
+            K = torch.empty(n, dtype=torch.int64, device="cuda")
+            trace = (C.c_int32 * (3 * 64))()
+            n_levels, n_moves, bound = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+            ms = (C.c_float * 4)() if stages is not None else None
+            it = 0
+            while True:
+                if n_iterations > 0 and it == n_iterations:
+                    break
+                if it == LEIDEN_MAX_ITERATIONS:
+                    info["bound_reached"] = info["bound_reached"] or n_iterations < 0
+                    break
+                _lib.check(lib.icv_leiden_iteration(_ptr(q_indptr), _ptr(q_indices), _ptr(q_w), n, kept, gom, seed, it,
+                                                    _ptr(labels), _ptr(ws), trace, C.byref(n_levels), C.byref(n_moves),
+                                                    C.byref(bound), ms, st))
+                it += 1
+                nl = n_levels.value
+                info["levels"].append([int(trace[3 * i]) for i in range(nl)])
+                info["rounds"].append([(int(trace[3 * i + 1]), int(trace[3 * i + 2])) for i in range(nl)])
+                info["bound_reached"] = info["bound_reached"] or bool(bound.value)
+                _lib.check(lib.icv_leiden_renumber(_ptr(labels), n, _ptr(out), C.byref(n_comm), st))
+                _lib.check(lib.icv_leiden_sums(_ptr(q_indptr), _ptr(q_indices), _ptr(q_w), n, _ptr(out), _ptr(e), _ptr(K),
+                                               st))
+                c = n_comm.value
+                info["quality"].append(leiden_quality(e[:c].tolist(), K[:c].tolist(), float(resolution)))
+                if stages is not None:
+                    stages.append({"local_moving_ms": float(ms[0]), "refinement_ms": float(ms[1]),
+                                   "aggregation_ms": float(ms[2]), "rest_ms": float(ms[3]), "quantise_ms": quantise_ms})
+                if n_iterations < 0 and n_moves.value == 0:
+                    break
+            info["n_iterations"] = it
+        info["n_communities"] = int(n_comm.value)
+    return out, info

@@ -39,6 +39,7 @@ EXPORTS = (
     "icv_device_count", "icv_developer_knobs_reload",
     "icv_knn_workspace", "icv_knn", "icv_knn_fuzzy", "icv_knn_symmetrize_count", "icv_knn_symmetrize_fill",
     "icv_knn_sort_rows",
+    "icv_leiden_workspace", "icv_leiden_quantise", "icv_leiden_iteration", "icv_leiden_sums", "icv_leiden_renumber",
 )
 
 
@@ -162,6 +163,12 @@ def load():
     lib.icv_knn_symmetrize_count.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.icv_knn_symmetrize_fill.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp, vp]
     lib.icv_knn_sort_rows.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    lib.icv_leiden_workspace.argtypes = [i64, i64, P(i64)]
+    lib.icv_leiden_quantise.argtypes = [vp, vp, vp, i32, i64, i64, i32, vp, vp, vp, P(i64), vp]
+    lib.icv_leiden_iteration.argtypes = [vp, vp, vp, i64, i64, dbl, C.c_uint64, i32, vp, vp, P(i32), P(i32), P(i64),
+                                         P(i32), P(C.c_float), vp]
+    lib.icv_leiden_sums.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.icv_leiden_renumber.argtypes = [vp, i64, vp, P(i32), vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -21,6 +21,10 @@
 #include <memory>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_reduce_by_key.hpp>
+#include <rocprim/device/device_scan.hpp>
+
 #include "icv_kernels.hpp"
 #include "icv_kernel_ws.hpp"
 #include "icv_kernel_x16.hpp"
@@ -34,6 +38,7 @@
 #include "icv_corr.hpp"
 #include "icv_pca.hpp"
 #include "icv_knn.hpp"
+#include "icv_leiden.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -3359,6 +3364,372 @@ int icv_knn_sort_rows(const int64_t* indptr, int64_t n, const int32_t* cols_in, 
     hipLaunchKernelGGL(icv::k_knn_sort_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        indptr, n, cols_in, vals_in, cols, vals);
     HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+}  // extern "C"
+
+// ---- tl.leiden (csrc/icv_leiden.hpp) ---------------------------------------------------------------------------------
+namespace {
+struct LdGeom {
+    // two level graphs (A, B: ping-pong above level 0), the per-vertex arrays, the sort buffers of the aggregation
+    size_t rp[2], col[2], w[2], loop[2], k, comm[2], K, cnt, sub, Ks, cs, ext, want, wantw, sel, o2c, fa, fb, ra, rb, fl, ll,
+        hk, hv, keys[2], vals[2], counters, bytes;
+    LdGeom(int64_t n, int64_t nnz) {
+        size_t o = 0;
+        auto seg = [&](size_t b) {
+            const size_t at = o;
+            o += (b + 255) / 256 * 256;
+            return at;
+        };
+        const size_t N = (size_t)n + 1, Z = (size_t)nnz + 1;
+        for (int i = 0; i < 2; ++i) {
+            rp[i] = seg(N * 8), col[i] = seg(Z * 4), w[i] = seg(Z * 8), loop[i] = seg(N * 8), comm[i] = seg(N * 4);
+            keys[i] = seg(Z * 8), vals[i] = seg(Z * 8);
+        }
+        k = seg(N * 8), K = seg(N * 8), cnt = seg(N * 4), sub = seg(N * 4), Ks = seg(N * 8), cs = seg(N * 4);
+        ext = seg(N * 8), want = seg(N * 4), wantw = seg(N * 8), sel = seg(N * 4), o2c = seg(N * 4);
+        fa = seg(N * 4), fb = seg(N * 4), ra = seg(N * 4), rb = seg(N * 4), fl = seg(N * 4), ll = seg(N * 4);
+        hk = seg(2 * Z * 4), hv = seg(2 * Z * 8);  // k_ld_decide_long's tables: 2 slots per stored entry
+        counters = seg(64);
+        bytes = o;
+    }
+};
+inline dim3 ld_grid(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
+
+// exclusive prefix sums of m int32 flags (rocprim; its temporary comes from the stream's pool)
+int ld_scan(const int32_t* in, int32_t* out, size_t m, hipStream_t st) {
+    size_t tb = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tb, in, out, (int32_t)0, m, rocprim::plus<int32_t>(), st));
+    AsyncBuf tmp;
+    HIP_TRY(tmp.alloc(tb, st));
+    HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, in, out, (int32_t)0, m, rocprim::plus<int32_t>(), st));
+    return ICV_OK;
+}
+#define ICV_TRY(expr)              \
+    do {                           \
+        const int rc_ = (expr);    \
+        if (rc_ != ICV_OK) return rc_; \
+    } while (0)
+
+struct LdLevel {
+    int n;
+    int64_t nnz;
+    const int64_t* rp;
+    const int32_t* col;
+    const long long* w;
+    const long long* loop;  // nullptr at level 0
+    int32_t* comm;
+};
+}  // namespace
+
+extern "C" {
+
+int icv_leiden_workspace(int64_t n, int64_t nnz, int64_t* bytes) {
+    if (!bytes || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31)
+        return fail(ICV_ERR_INVALID, "bad leiden_workspace arguments");
+    *bytes = (int64_t)LdGeom(n, nnz).bytes;
+    return ICV_OK;
+}
+
+int icv_leiden_quantise(const int64_t* indptr, const int32_t* indices, const void* data, int32_t dtype, int64_t n,
+                        int64_t nnz, int32_t use_weights, int64_t* q_indptr, int32_t* q_indices, int64_t* q_weights,
+                        int64_t* result, void* stream) {
+    if (!indptr || !q_indptr || !result || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 ||
+        (nnz > 0 && (!indices || !data || !q_indices || !q_weights)) || (dtype != ICV_F32 && dtype != ICV_F64))
+        return fail(ICV_ERR_INVALID, "bad leiden_quantise arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AsyncBuf wq, keep, flg;
+    HIP_TRY(wq.alloc((size_t)(nnz + 1) * 8, st));
+    HIP_TRY(keep.alloc((size_t)n * 8, st));
+    HIP_TRY(flg.alloc(32, st));
+    HIP_TRY(hipMemsetAsync(flg.p, 0, 32, st));
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(static_cast<char*>(flg.p) + 8);
+    if (dtype == ICV_F32)
+        hipLaunchKernelGGL(icv::k_ld_quantise<float>, ld_grid(n, 4), dim3(256), 0, st, indptr, indices,
+                           static_cast<const float*>(data), n, use_weights, wq.as<long long>(), keep.as<long long>(),
+                           flg.as<unsigned>(), sums);
+    else
+        hipLaunchKernelGGL(icv::k_ld_quantise<double>, ld_grid(n, 4), dim3(256), 0, st, indptr, indices,
+                           static_cast<const double*>(data), n, use_weights, wq.as<long long>(), keep.as<long long>(),
+                           flg.as<unsigned>(), sums);
+    HIP_TRY(hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, flg.p, 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const unsigned f = (unsigned)(h[0] & 0xFFFFFFFFu);
+    if (f & 8) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix has a column index out of range");
+    if (f & 16) return fail(ICV_ERR_INVALID, "tl.leiden: the rows of the adjacency matrix must be sorted, without duplicates");
+    if (f & 1) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix has non-finite values");
+    if (f & 2) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix has negative values");
+    if (f & 4) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix has stored diagonal entries");
+    if (f & 32) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix is not symmetric");
+    const unsigned __int128 total = ((unsigned __int128)h[2] << 32) + h[1];
+    if ((f & 64) || total >= ((unsigned __int128)1 << 62))
+        return fail(ICV_ERR_INVALID,
+                    "tl.leiden: the weights are too large (sum of the integer weights must stay below 2^62)");
+    ICV_TRY(icv_row_offsets(keep.as<int64_t>(), n, q_indptr, stream));
+    if (nnz > 0)
+        hipLaunchKernelGGL(icv::k_ld_compact, ld_grid(n, 4), dim3(256), 0, st, indptr, indices, wq.as<long long>(), n,
+                           q_indptr, q_indices, reinterpret_cast<long long*>(q_weights));
+    HIP_TRY(hipGetLastError());
+    int64_t kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, q_indptr + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    result[0] = kept;
+    result[1] = (int64_t)total;
+    return ICV_OK;
+}
+
+int icv_leiden_iteration(const int64_t* indptr, const int32_t* indices, const int64_t* weights, int64_t n, int64_t nnz,
+                         double gom, uint64_t seed, int32_t iteration, int32_t* labels, void* workspace, int32_t* trace,
+                         int32_t* n_levels, int64_t* n_moves, int32_t* bound_reached, float* stage_ms, void* stream) {
+    if (!indptr || !labels || !workspace || !trace || !n_levels || !n_moves || !bound_reached || n < 1 ||
+        n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 || (nnz > 0 && (!indices || !weights)) ||
+        !(gom >= 0.0) || !(gom <= 1.7976931348623157e308) || iteration < 0)
+        return fail(ICV_ERR_INVALID, "bad leiden_iteration arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const LdGeom G(n, nnz);
+    char* ws = static_cast<char*>(workspace);
+#define LD(T, f) reinterpret_cast<T*>(ws + G.f)
+    long long *k = LD(long long, k), *K = LD(long long, K), *Ks = LD(long long, Ks), *ext = LD(long long, ext),
+              *wantw = LD(long long, wantw);
+    int32_t *cnt = LD(int32_t, cnt), *sub = LD(int32_t, sub), *cs = LD(int32_t, cs), *want = LD(int32_t, want),
+            *sel = LD(int32_t, sel), *o2c = LD(int32_t, o2c), *fa = LD(int32_t, fa), *fb = LD(int32_t, fb),
+            *ra = LD(int32_t, ra), *rb = LD(int32_t, rb), *fl = LD(int32_t, fl), *ll = LD(int32_t, ll), *hk = LD(int32_t, hk);
+    long long* hv = LD(long long, hv);
+    unsigned* counters = LD(unsigned, counters);  // [0] wanting [1] selected [2] selected to empty [3] long rows
+    unsigned long long* moves = reinterpret_cast<unsigned long long*>(counters + 4);
+    float ms[4] = {0, 0, 0, 0};  // local moving, refinement, aggregation, rest
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct EvGuard {
+        hipEvent_t *a, *b;
+        ~EvGuard() {
+            if (*a) (void)hipEventDestroy(*a);
+            if (*b) (void)hipEventDestroy(*b);
+        }
+    } guard{&ev0, &ev1};
+    if (stage_ms) {
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+    }
+    auto tic = [&]() -> hipError_t { return stage_ms ? hipEventRecord(ev0, st) : hipSuccess; };
+    auto toc = [&](int slot) -> hipError_t {
+        if (!stage_ms) return hipSuccess;
+        hipError_t e = hipEventRecord(ev1, st);
+        if (e != hipSuccess) return e;
+        e = hipEventSynchronize(ev1);
+        if (e != hipSuccess) return e;
+        float t = 0;
+        e = hipEventElapsedTime(&t, ev0, ev1);
+        ms[slot] += t;
+        return e;
+    };
+
+    LdLevel L{(int)n, nnz, indptr, indices, reinterpret_cast<const long long*>(weights), nullptr, LD(int32_t, comm[0])};
+    HIP_TRY(hipMemcpyAsync(L.comm, labels, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(icv::k_ld_iota, ld_grid(n), dim3(256), 0, st, n, o2c);
+    HIP_TRY(hipMemsetAsync(counters, 0, 64, st));
+    *n_moves = 0;
+    *bound_reached = 0;
+    *n_levels = 0;
+    bool done = false;
+    for (int level = 0; level < icv::kLdMaxLevels; ++level) {
+        const int ln = L.n;
+        const int max_rounds = 64 + (ln < 4096 ? ln : 4096);
+        // strengths and the starting partition's sums
+        HIP_TRY(tic());
+        HIP_TRY(hipMemsetAsync(K, 0, (size_t)ln * 8, st));
+        HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)ln * 4, st));
+        HIP_TRY(hipMemsetAsync(counters + 3, 0, 4, st));
+        hipLaunchKernelGGL(icv::k_ld_strength, ld_grid(ln, 4), dim3(256), 0, st, L.rp, L.w, L.loop, ln, k, ll, counters + 3);
+        hipLaunchKernelGGL(icv::k_ld_init_comm, ld_grid(ln), dim3(256), 0, st, L.comm, k, ln, K, cnt);
+        HIP_TRY(hipGetLastError());
+        unsigned h[4], n_long = 0;
+        HIP_TRY(hipMemcpyAsync(&n_long, counters + 3, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        int r_move = 0, r_ref = 0;
+        for (;;) {  // ---- local moving
+            if (r_move == max_rounds) {
+                *bound_reached = 1;
+                break;
+            }
+            HIP_TRY(hipMemsetAsync(counters, 0, 12, st));
+            hipLaunchKernelGGL(icv::k_ld_decide<false>, ld_grid(ln, 4), dim3(256), 0, st, ln, L.rp, L.col, L.w, k, L.comm, K,
+                               cnt, nullptr, nullptr, nullptr, gom, want, wantw, counters);
+            if (n_long)
+                hipLaunchKernelGGL(icv::k_ld_decide_long<false>, dim3(n_long), dim3(256), 0, st, ll, L.rp, L.col, L.w, k, L.comm,
+                                   K, cnt, nullptr, nullptr, nullptr, gom, hk, hv, want, wantw, counters);
+            hipLaunchKernelGGL(icv::k_ld_select, ld_grid(ln, 4), dim3(256), 0, st, ln, L.rp, L.col, L.comm, want,
+                               icv::ld_round_base(seed, iteration, level, 0, r_move), 1, sel, counters);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h, counters, 16, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (h[0] == 0) break;
+            ++r_move;
+            if (h[1] == 0) continue;
+            if (h[2]) {
+                hipLaunchKernelGGL(icv::k_ld_empty_flags, ld_grid(ln + 1), dim3(256), 0, st, ln, cnt, sel, fa, fb);
+                ICV_TRY(ld_scan(fa, ra, (size_t)ln + 1, st));
+                ICV_TRY(ld_scan(fb, rb, (size_t)ln + 1, st));
+                hipLaunchKernelGGL(icv::k_ld_free_list, ld_grid(ln), dim3(256), 0, st, ln, cnt, ra, fl);
+                hipLaunchKernelGGL(icv::k_ld_assign_empty, ld_grid(ln), dim3(256), 0, st, ln, ra, rb, fl, sel);
+            }
+            hipLaunchKernelGGL(icv::k_ld_apply_move, ld_grid(ln), dim3(256), 0, st, ln, sel, k, L.comm, K, cnt, moves);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(toc(0));
+        HIP_TRY(tic());
+        // ---- refinement (K is now the communities' K_C)
+        hipLaunchKernelGGL(icv::k_ld_refine_init, ld_grid(ln, 4), dim3(256), 0, st, ln, L.rp, L.col, L.w, k, L.comm, sub, Ks,
+                           cs, ext);
+        for (;;) {
+            if (r_ref == max_rounds) {
+                *bound_reached = 1;
+                break;
+            }
+            HIP_TRY(hipMemsetAsync(counters, 0, 12, st));
+            hipLaunchKernelGGL(icv::k_ld_decide<true>, ld_grid(ln, 4), dim3(256), 0, st, ln, L.rp, L.col, L.w, k, sub, Ks, cs,
+                               L.comm, K, ext, gom, want, wantw, counters);
+            if (n_long)
+                hipLaunchKernelGGL(icv::k_ld_decide_long<true>, dim3(n_long), dim3(256), 0, st, ll, L.rp, L.col, L.w, k, sub, Ks,
+                                   cs, L.comm, K, ext, gom, hk, hv, want, wantw, counters);
+            hipLaunchKernelGGL(icv::k_ld_select, ld_grid(ln, 4), dim3(256), 0, st, ln, L.rp, L.col, sub, want,
+                               icv::ld_round_base(seed, iteration, level, 1, r_ref), 0, sel, counters);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h, counters, 16, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (h[0] == 0) break;
+            ++r_ref;
+            hipLaunchKernelGGL(icv::k_ld_apply_refine, ld_grid(ln, 4), dim3(256), 0, st, ln, L.rp, L.col, L.w, sel, wantw, k,
+                               sub, Ks, cs, ext);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(toc(1));
+        HIP_TRY(tic());
+        trace[3 * level] = ln;
+        trace[3 * level + 1] = r_move;
+        trace[3 * level + 2] = r_ref;
+        *n_levels = level + 1;
+        // ---- aggregation on the refined partition
+        hipLaunchKernelGGL(icv::k_ld_used_flags, ld_grid(ln + 1), dim3(256), 0, st, ln, cs, cnt, fa, fb);
+        ICV_TRY(ld_scan(fa, ra, (size_t)ln + 1, st));
+        ICV_TRY(ld_scan(fb, rb, (size_t)ln + 1, st));
+        int32_t n2 = 0;
+        HIP_TRY(hipMemcpyAsync(&n2, ra + ln, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n2 == ln) {
+            done = true;
+            HIP_TRY(toc(2));
+            break;
+        }
+        const int nx = (level & 1) ? 0 : 1;  // level 0 reads the caller's graph; buffers alternate above it
+        int64_t* rp2 = LD(int64_t, rp[nx]);
+        int32_t* col2 = LD(int32_t, col[nx]);
+        long long* loop2 = LD(long long, loop[nx]);
+        int32_t* comm2 = LD(int32_t, comm[nx]);
+        unsigned long long *keys_in = LD(unsigned long long, keys[0]), *keys_out = LD(unsigned long long, keys[1]);
+        long long *vals_in = LD(long long, vals[0]), *vals_out = LD(long long, vals[1]);
+        long long* w2 = LD(long long, w[nx]);
+        HIP_TRY(hipMemsetAsync(loop2, 0, (size_t)n2 * 8, st));
+        hipLaunchKernelGGL(icv::k_ld_agg_vertices, ld_grid(ln), dim3(256), 0, st, ln, sub, L.comm, ra, rb, L.loop, comm2,
+                           loop2);
+        hipLaunchKernelGGL(icv::k_ld_o2c, ld_grid(n), dim3(256), 0, st, n, sub, ra, o2c);
+        int64_t nnz2 = 0;
+        if (L.nnz > 0) {
+            hipLaunchKernelGGL(icv::k_ld_agg_keys, ld_grid(ln, 4), dim3(256), 0, st, ln, L.rp, L.col, L.w, sub, ra, keys_in,
+                               vals_in, loop2);
+            HIP_TRY(hipGetLastError());
+            size_t tb = 0;
+            HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, (size_t)L.nnz, 0, 64, st));
+            {
+                AsyncBuf tmp;
+                HIP_TRY(tmp.alloc(tb, st));
+                HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, keys_in, keys_out, vals_in, vals_out, (size_t)L.nnz, 0, 64, st));
+            }
+            // unique keys -> keys_in, their sums -> w2, count -> counters + 8
+            unsigned* n_unique = counters + 8;
+            HIP_TRY(rocprim::reduce_by_key(nullptr, tb, keys_out, vals_out, (size_t)L.nnz, keys_in, w2, n_unique,
+                                           rocprim::plus<long long>(), rocprim::equal_to<unsigned long long>(), st));
+            {
+                AsyncBuf tmp;
+                HIP_TRY(tmp.alloc(tb, st));
+                HIP_TRY(rocprim::reduce_by_key(tmp.p, tb, keys_out, vals_out, (size_t)L.nnz, keys_in, w2, n_unique,
+                                               rocprim::plus<long long>(), rocprim::equal_to<unsigned long long>(), st));
+            }
+            unsigned hu = 0;
+            unsigned long long last = 0;
+            HIP_TRY(hipMemcpyAsync(&hu, n_unique, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&last, keys_out + (L.nnz - 1), 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            nnz2 = (int64_t)hu - (last == ~0ull ? 1 : 0);  // the entries inside a vertex share the last key
+            if (nnz2 > 0) hipLaunchKernelGGL(icv::k_ld_agg_cols, ld_grid(nnz2), dim3(256), 0, st, nnz2, keys_in, col2);
+        }
+        hipLaunchKernelGGL(icv::k_ld_agg_rowptr, ld_grid(n2 + 1), dim3(256), 0, st, n2, nnz2, keys_in, rp2);
+        HIP_TRY(hipGetLastError());
+        L = LdLevel{n2, nnz2, rp2, col2, w2, loop2, comm2};
+        HIP_TRY(toc(2));
+    }
+    if (!done) *bound_reached = 1;
+    HIP_TRY(tic());
+    hipLaunchKernelGGL(icv::k_ld_gather, ld_grid(n), dim3(256), 0, st, n, L.comm, o2c, labels);
+    HIP_TRY(hipGetLastError());
+    unsigned long long hm = 0;
+    HIP_TRY(hipMemcpyAsync(&hm, moves, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(toc(3));
+    *n_moves = (int64_t)hm;
+    if (stage_ms)
+        for (int i = 0; i < 4; ++i) stage_ms[i] = ms[i];
+#undef LD
+    return ICV_OK;
+}
+
+int icv_leiden_sums(const int64_t* indptr, const int32_t* indices, const int64_t* weights, int64_t n,
+                    const int32_t* labels, int64_t* e, int64_t* K, void* stream) {
+    if (!indptr || !labels || !e || !K || n < 1) return fail(ICV_ERR_INVALID, "bad leiden_sums arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(e, 0, (size_t)n * 8, st));
+    HIP_TRY(hipMemsetAsync(K, 0, (size_t)n * 8, st));
+    hipLaunchKernelGGL(icv::k_ld_sums, ld_grid(n, 4), dim3(256), 0, st, n, indptr, indices,
+                       reinterpret_cast<const long long*>(weights), labels, reinterpret_cast<long long*>(e),
+                       reinterpret_cast<long long*>(K));
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_leiden_renumber(const int32_t* labels, int64_t n, int32_t* out, int32_t* n_communities, void* stream) {
+    if (!labels || !out || !n_communities || n < 1 || n > (int64_t)1 << 30)
+        return fail(ICV_ERR_INVALID, "bad leiden_renumber arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AsyncBuf buf;
+    const size_t N = ((size_t)n + 63) / 64 * 64;
+    HIP_TRY(buf.alloc(N * (4 + 4 + 8 + 8 + 4 + 4 + 4) + 64, st));
+    char* p = static_cast<char*>(buf.p);
+    unsigned long long *keys = reinterpret_cast<unsigned long long*>(p), *keys2 = keys + N;
+    int32_t *size = reinterpret_cast<int32_t*>(keys2 + N), *first = size + N, *ids = first + N, *ids2 = ids + N,
+            *rank = ids2 + N;
+    unsigned* nc = reinterpret_cast<unsigned*>(rank + N);
+    HIP_TRY(hipMemsetAsync(size, 0, N * 4, st));
+    HIP_TRY(hipMemsetAsync(first, 0x7f, N * 4, st));
+    HIP_TRY(hipMemsetAsync(nc, 0, 4, st));
+    hipLaunchKernelGGL(icv::k_ld_sizes, ld_grid(n), dim3(256), 0, st, n, labels, size, first);
+    hipLaunchKernelGGL(icv::k_ld_size_keys, ld_grid(n), dim3(256), 0, st, n, size, first, keys, ids, nc);
+    HIP_TRY(hipGetLastError());
+    size_t tb = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, keys2, ids, ids2, (size_t)n, 0, 64, st));
+    {
+        AsyncBuf tmp;
+        HIP_TRY(tmp.alloc(tb, st));
+        HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, keys, keys2, ids, ids2, (size_t)n, 0, 64, st));
+    }
+    hipLaunchKernelGGL(icv::k_ld_scatter_rank, ld_grid(n), dim3(256), 0, st, n, ids2, rank);
+    hipLaunchKernelGGL(icv::k_ld_gather, ld_grid(n), dim3(256), 0, st, n, rank, labels, out);
+    HIP_TRY(hipGetLastError());
+    unsigned h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, nc, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_communities = (int32_t)h;
     return ICV_OK;
 }
 
