@@ -419,7 +419,8 @@ int icv_pairwise_sqeuclidean_tiles(const float *x, int64_t n, int32_t d, int64_t
  *                      list order, zero where another rank owns the row: all-reduce(SUM) them in between
  *   icv_ward_pairs     reciprocal pairs of the round (replicated); compacts the local rows first when the column
  *                      layout asks for it; h_counts = {n_live, n_merges, n_pairs, n_act} (synchronises the
- *                      stream); all_active != 0: list every live row for the next scan
+ *                      stream); all_active != 0: list every live row for the next scan (the pass after a round
+ *                      without a pair; it is not counted in icv_ward_finish's h_rounds)
  *   icv_ward_round_pairs  slots (i kept, j absorbed) of the pairs just found, HOST arrays of n_pairs
  * until n_live == 1; icv_ward_finish writes the linkage matrix as icv_ward_linkage does.  One in-flight call per
  * state. */

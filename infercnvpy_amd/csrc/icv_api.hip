@@ -2354,14 +2354,16 @@ int ward_compact(icv_ward_s* w, float* D, int64_t ld, hipStream_t st) {
 }
 
 // reciprocal pairs of the round; strip layout: compacts first when fewer than half of the positions are alive,
-// and again (then it must fit) when the round's new columns would not fit the spare region
+// and again (then it must fit) when the round's new columns would not fit the spare region.  all_active (the pass
+// that lists every row after a round without a pair) is bookkeeping only and is not counted as a round, for the
+// one-call and the step-wise entry points alike.
 int ward_pairs(icv_ward_s* w, float* D, int64_t ld, bool all_active, hipStream_t st) {
     if (!w->strip) {
         hipLaunchKernelGGL(icv::k_ward_pairs, dim3(1), dim3(1024), 0, st, (int)w->n, w->live, w->cstate, w->qmask, w->mdesc,
                            w->pair_d, w->size_old, w->size_new, w->alive, w->nn, w->dmin, w->log_i, w->log_j, w->log_d,
                            w->log_size, w->act, all_active ? 1 : 0, reinterpret_cast<icv::WardCounts*>(w->counts));
         HIP_TRY(hipGetLastError());
-        ++w->rounds;
+        if (!all_active) ++w->rounds;
         return ward_read_counts(w, st);
     }
     {
@@ -2384,7 +2386,7 @@ int ward_pairs(icv_ward_s* w, float* D, int64_t ld, bool all_active, hipStream_t
         const int width_before = w->h.width;
         if (int rc = ward_read_counts(w, st)) return rc;
         if (!w->h.need_compact) {
-            ++w->rounds;
+            if (!all_active) ++w->rounds;
             return ICV_OK;
         }
         if (attempt == 1) break;
@@ -2455,7 +2457,6 @@ int icv_ward_linkage(float* dist_sq, int64_t n, int64_t ld, int32_t spare_column
             if (retry) return fail(ICV_ERR_INVALID, "ward_linkage: distances are not finite");
             retry = true;
             if (int rc = ward_pairs(w.get(), dist_sq, ld, true, st)) return rc;
-            --w->rounds;  // bookkeeping only, not a round
             if (w->h.n_pairs > 0) retry = false;
         } else {
             retry = false;

@@ -387,7 +387,8 @@ __global__ void __launch_bounds__(1024) k_ward_pairs(int n, int* live, int* csta
         int r = -1, a = 0;
         if (idx < n_live) {
             r = live[idx];
-            a = cstate[r] == -1 && (all_active || cstate[nn[r]] != -1);
+            const int c = nn[r];  // -1: the row found no finite distance (searched again every round)
+            a = cstate[r] == -1 && (all_active || c < 0 || cstate[c] != -1);
         }
         const int p = block_scan(a);
         if (a) act[p] = r;

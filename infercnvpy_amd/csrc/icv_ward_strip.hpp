@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) k_ward_merge_s(float* D, int64_t ld, int 
             best_c = c < 0 ? P.pos_slot[q] : c;
         } else if (v == best) {
             const int cc = c < 0 ? P.pos_slot[q] : c;
-            if (best_c < 0 || cc < best_c) best_c = cc;
+            if (cc < best_c) best_c = cc;  // best_c < 0: v is +inf, which is no neighbour (as in the in-place kernels)
         }
     };
     // columns whose cluster did not merge: in place (returns true if `out` changed)
@@ -191,7 +191,7 @@ __global__ void __launch_bounds__(256) k_ward_scan_s(const float* D, int64_t ld,
             best_c = P.pos_slot[q];
         } else if (v == best) {
             const int c = P.pos_slot[q];
-            if (best_c < 0 || c < best_c) best_c = c;
+            if (c < best_c) best_c = c;  // best_c < 0: v is +inf, which is no neighbour (as in the in-place kernels)
         }
     };
     if (DENSE) {
@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(256) k_ward_scan_s(const float* D, int64_t ld,
             const int c = live[idx];
             if (c == r) continue;
             const float v = Dr[P.slot_pos[c]];
-            if (v < best || (v == best && (best_c < 0 || c < best_c))) {
+            if (v < best || (v == best && c < best_c)) {
                 best = v;
                 best_c = c;
             }
@@ -377,7 +377,8 @@ __global__ void __launch_bounds__(1024) k_ward_pairs_s(int n, int cap, int* live
             r = live[idx];
             const int cs = cstate[r];
             fu = cs == -1;
-            fa = fu && (all_active || cstate[nn[r]] != -1);
+            const int c = nn[r];  // -1: the row found no finite distance (searched again every round)
+            fa = fu && (all_active || c < 0 || cstate[c] != -1);
             fk = alive[r];
         }
         scan3(fa, fu, fk, e0, e1, e2);

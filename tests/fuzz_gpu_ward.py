@@ -4,7 +4,8 @@ Per seed: n in 2..1500 cells, d in 4..99 features, 1..10 blobs (now and then wit
 structure), both column layouts of the Ward rounds (spare columns / in place).  Checked against scipy's float64
 `linkage(method="ward")`: a valid linkage, the multiset of cluster sizes, sorted heights to 2e-4 relative (float32
 distances; duplicated cells: 1e-3 of the tallest merge), >= 97 % of the merged leaf sets (merges whose heights agree to
-rounding may permute).  Then `cnv_score`
+rounding may permute).  And against the numpy oracle of the rounds (tests/_ward_oracle.py) on the GPU's own distance
+matrix: the linkage matrix and the round count must be equal, bit for bit.  Then `cnv_score`
 and `ithcna` on the same matrix against their numpy restatements."""
 import os
 import sys
@@ -21,8 +22,12 @@ def one_case(seed):
     import scipy.sparse as sp
     from scipy.cluster.hierarchy import is_valid_linkage
 
+    import torch
+
     import infercnvpy_amd as cnv
     import test_gpu_parity as T
+    from _ward_oracle import ward_rounds
+    from infercnvpy_amd import _engine
     from infercnvpy_amd._compat import SimpleAnnData
     from oracle import infercnv_oracle as O
 
@@ -44,10 +49,14 @@ def one_case(seed):
         os.environ["ICV_WARD_IN_PLACE"] = "1"
     T._knobs()  # (the library reads its developer knobs once)
     try:
-        Z = cnv.tl.ward_linkage(X)
+        Z, rounds = cnv.tl.ward_linkage(X, return_rounds=True)
+        d2 = _engine.pairwise_sqeuclidean(torch.from_numpy(X).cuda()).cpu().numpy()
     finally:
         os.environ.pop("ICV_WARD_IN_PLACE", None)
         T._knobs()
+    Ze, rounds_e = ward_rounds(d2)  # the rounds alone: an equality, whatever the Gram rounded
+    assert rounds == rounds_e, desc + f" rounds {rounds} vs oracle {rounds_e}"
+    np.testing.assert_array_equal(Z, Ze, err_msg=desc)
     Zs = O.ward_linkage(X)
     assert Z.shape == Zs.shape == (n - 1, 4), desc
     assert is_valid_linkage(Z), desc

@@ -118,7 +118,7 @@ def test_two_ranks_match_single_gpu():
         np.testing.assert_array_equal(results[r][3], Z1)
 
 
-def _ward_one_gpu_worker(rank, world, port, n, d, in_place, q):
+def _ward_one_gpu_worker(rank, world, port, n, d, in_place, ties, q):
     if in_place:
         os.environ["ICV_WARD_IN_PLACE"] = "1"  # the column layout without spare columns, on every rank
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -131,7 +131,7 @@ def _ward_one_gpu_worker(rank, world, port, n, d, in_place, q):
     try:
         from infercnvpy_amd import dist as icd
 
-        X = _ward_points(n, d)
+        X = _ward_points(n, d, ties)
         cut = np.linspace(0, n, world + 1).astype(int)
         Z, rounds = icd.ward_linkage_sharded(torch.from_numpy(X[cut[rank]:cut[rank + 1]]).cuda(), return_rounds=True)
         q.put((rank, "ok", Z, rounds))
@@ -143,17 +143,27 @@ def _ward_one_gpu_worker(rank, world, port, n, d, in_place, q):
         dist.destroy_process_group()
 
 
-def _ward_points(n, d):
+def _ward_points(n, d, ties=False):
+    if ties:  # points on a small integer lattice: exact distances, duplicates, ties in every search
+        import _ward_cases
+
+        return _ward_cases.int_points(n, d=d)[0]
     rng = np.random.RandomState(n)
     return (rng.standard_normal((n, d)) * 0.4 + rng.standard_normal((7, d))[rng.randint(0, 7, n)]).astype(np.float32)
 
 
-@pytest.mark.parametrize("world,n,d,in_place", [(2, 2500, 64, False), (3, 5300, 40, False), (2, 700, 16, False),
-                                                  (2, 2500, 64, True)])
-def test_sharded_ward_two_processes_one_gpu(world, n, d, in_place):
+_SHARDED_WARD = [(2, 2500, 64, False), (3, 5300, 40, False), (2, 700, 16, False), (2, 2500, 64, True)]
+_SHARDED_WARD_TIES = [(2, 2500, 3, False), (2, 2500, 3, True)]
+
+
+@pytest.mark.parametrize("world,n,d,in_place,ties",
+                         [pytest.param(*c, False, id="-".join(map(str, c))) for c in _SHARDED_WARD]
+                         + [pytest.param(*c, True, id="-".join(map(str, c)) + "-ties") for c in _SHARDED_WARD_TIES])
+def test_sharded_ward_two_processes_one_gpu(world, n, d, in_place, ties):
     """Sharded tiles + sharded rounds equal the one-GPU linkage bit for bit (n = 700: one super-row, the second
     rank holds nothing; n = 5300: six super-rows over three ranks, the last one partial; in_place: the step kernels
-    of the layout without spare columns)."""
+    of the layout without spare columns; ties: integer lattice points, where the one-GPU result is itself held to the
+    numpy oracle by test_gpu_ward_exact.py)."""
     import torch.multiprocessing as mp
 
     from infercnvpy_amd.tl import ward_linkage
@@ -161,7 +171,7 @@ def test_sharded_ward_two_processes_one_gpu(world, n, d, in_place):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_ward_one_gpu_worker, args=(r, world, port, n, d, in_place, q)) for r in range(world)]
+    procs = [ctx.Process(target=_ward_one_gpu_worker, args=(r, world, port, n, d, in_place, ties, q)) for r in range(world)]
     for p in procs:
         p.start()
     results = sorted((q.get(timeout=600) for _ in procs), key=lambda r: r[0])
@@ -169,7 +179,7 @@ def test_sharded_ward_two_processes_one_gpu(world, n, d, in_place):
         p.join(timeout=60)
     for rank, status, _, _ in results:
         assert status == "ok", f"rank {rank}: {status}"
-    Z1, rounds1 = ward_linkage(_ward_points(n, d), return_rounds=True)
+    Z1, rounds1 = ward_linkage(_ward_points(n, d, ties), return_rounds=True)
     for r in range(world):
         assert results[r][3] == rounds1
         np.testing.assert_array_equal(results[r][2], Z1)
