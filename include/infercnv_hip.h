@@ -557,6 +557,25 @@ int icv_leiden_sums(const int64_t *indptr, const int32_t *indices, const int64_t
                     const int32_t *labels, int64_t *e, int64_t *K, void *stream);
 int icv_leiden_renumber(const int32_t *labels, int64_t n, int32_t *out, int32_t *n_communities, void *stream);
 
+/* ---- tl.umap: deterministic UMAP layout of a symmetric fuzzy graph ---------------------------------
+ * icv_umap_epochs runs the epochs [epoch_begin, epoch_end) of an n_epochs schedule on the positions y (device float32,
+ * n x n_components row-major, in / out), one kernel launch per epoch.  The schedule is stateless (rule 2), so any
+ * range may be run alone and [0, E) in one call equals E calls of one epoch bit for bit.  The graph is a canonical CSR
+ * (indptr int64 n + 1 trusted, indices int32, data float32; rule 1: rows strictly ascending, finite, non-negative, no
+ * diagonal, symmetric pattern and values; each violation ICV_ERR_INVALID, checked in every call before y is touched).
+ * n_components: 2 or 3.  a, b > 0; gamma >= 0; 0 <= negative_sample_rate <= 64; initial_alpha >= 0; seed =
+ * random_state.  Every row sum is an int64 sum of contributions rounded to 2^-32: the result is a pure function of
+ * the arguments.  Rows up to 512 entries take a wavefront, longer rows a workgroup (the same launch).
+ * stage_ms (host, optional): float[2] = validation, epochs.  The host reads three scalars after the validation; the
+ * epochs are enqueued without synchronisation (with stage_ms the call waits for them).
+ * workspace: icv_umap_workspace(n, nnz, n_components) bytes = 4 n n_components + 4 (n + 1) + 64, each part rounded up
+ * to 256 (the second position buffer, the list of the long rows, three scalars); nnz only bounds the arguments. */
+int icv_umap_workspace(int64_t n, int64_t nnz, int32_t n_components, int64_t *bytes);
+int icv_umap_epochs(const int64_t *indptr, const int32_t *indices, const float *data, int64_t n, int64_t nnz,
+                    int32_t n_components, double a, double b, double gamma, int32_t negative_sample_rate,
+                    double initial_alpha, int32_t n_epochs, int32_t epoch_begin, int32_t epoch_end, uint64_t seed,
+                    float *y, void *workspace, float *stage_ms, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

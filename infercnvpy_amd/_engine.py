@@ -1686,3 +1686,41 @@ def leiden(indptr, indices, data, resolution=1.0, random_state=0, n_iterations=-
             info["n_iterations"] = it
         info["n_communities"] = int(n_comm.value)
     return out, info
+
+
+# ---- tl.umap: the layout epochs on the device (icv_umap*) --------------------------------------------------
+def umap_epochs(indptr, indices, data, y, *, a, b, gamma=1.0, negative_sample_rate=5, initial_alpha=1.0, n_epochs,
+                epoch_begin=0, epoch_end=None, random_state=0, stage_ms=None):
+    """Run the epochs [epoch_begin, epoch_end) of an n_epochs schedule of DESIGN.md 4.11 on the positions ``y`` (device
+    float32 n x c, c in (2, 3), contiguous; updated in place and returned) for the device CSR graph (indptr int64
+    n + 1, indices int32, data float32; rows sorted, symmetric).  ``stage_ms``: a dict that receives the milliseconds
+    of the validation and of the epochs (added to what it holds)."""
+    torch = _torch()
+    lib = _lib.load()
+    n = indptr.numel() - 1
+    nnz = indices.numel()
+    assert indptr.is_cuda and indptr.dtype == torch.int64 and indices.dtype == torch.int32 and data.numel() == nnz
+    assert data.dtype == torch.float32 and n >= 1
+    assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.dim() == 2 and y.shape[0] == n
+    # the kernels trust the row pointers: check them here (two scalars and one comparison on the device)
+    if int(indptr[0].item()) != 0 or int(indptr[-1].item()) != nnz or bool((indptr[1:] < indptr[:-1]).any().item()):
+        raise ValueError("tl.umap: indptr must start at 0, be non-decreasing and end at the number of stored entries")
+    if nnz >= 1 << 31:
+        raise ValueError("tl.umap: at most 2^31 - 1 stored entries are supported")
+    c = int(y.shape[1])
+    epoch_end = n_epochs if epoch_end is None else epoch_end
+    seed = int(random_state) & ((1 << 64) - 1)
+    with torch.cuda.device(indptr.device):
+        st = _stream_ptr(torch)
+        indptr, indices, data = indptr.contiguous(), indices.contiguous(), data.contiguous()
+        need = C.c_int64(0)
+        _lib.check(lib.icv_umap_workspace(n, nnz, c, C.byref(need)))
+        ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+        ms = (C.c_float * 2)() if stage_ms is not None else None
+        _lib.check(lib.icv_umap_epochs(_ptr(indptr), _ptr(indices), _ptr(data), n, nnz, c, float(a), float(b),
+                                       float(gamma), int(negative_sample_rate), float(initial_alpha), int(n_epochs),
+                                       int(epoch_begin), int(epoch_end), seed, _ptr(y), _ptr(ws), ms, st))
+        if stage_ms is not None:
+            stage_ms["validation_ms"] = stage_ms.get("validation_ms", 0.0) + float(ms[0])
+            stage_ms["epochs_ms"] = stage_ms.get("epochs_ms", 0.0) + float(ms[1])
+    return y

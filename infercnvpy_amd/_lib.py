@@ -40,6 +40,7 @@ EXPORTS = (
     "icv_knn_workspace", "icv_knn", "icv_knn_fuzzy", "icv_knn_symmetrize_count", "icv_knn_symmetrize_fill",
     "icv_knn_sort_rows",
     "icv_leiden_workspace", "icv_leiden_quantise", "icv_leiden_iteration", "icv_leiden_sums", "icv_leiden_renumber",
+    "icv_umap_workspace", "icv_umap_epochs",
 )
 
 
@@ -169,6 +170,9 @@ def load():
                                          P(i32), P(C.c_float), vp]
     lib.icv_leiden_sums.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
     lib.icv_leiden_renumber.argtypes = [vp, i64, vp, P(i32), vp]
+    lib.icv_umap_workspace.argtypes = [i64, i64, i32, P(i64)]
+    lib.icv_umap_epochs.argtypes = [vp, vp, vp, i64, i64, i32, dbl, dbl, dbl, i32, dbl, i32, i32, i32, C.c_uint64, vp, vp,
+                                    P(C.c_float), vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

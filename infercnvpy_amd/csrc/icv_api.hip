@@ -39,6 +39,7 @@
 #include "icv_pca.hpp"
 #include "icv_knn.hpp"
 #include "icv_leiden.hpp"
+#include "icv_umap.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -3731,6 +3732,120 @@ int icv_leiden_renumber(const int32_t* labels, int64_t n, int32_t* out, int32_t*
     HIP_TRY(hipMemcpyAsync(&h, nc, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     *n_communities = (int32_t)h;
+    return ICV_OK;
+}
+
+}  // extern "C"
+
+// ---- tl.umap (csrc/icv_umap.hpp) ---------------------------------------------------------------------------------------
+namespace {
+struct UmGeom {
+    size_t y2, long_list, head, bytes;  // the second position buffer, the long rows, flags / count / largest weight
+    UmGeom(int64_t n, int32_t c) {
+        size_t o = 0;
+        auto seg = [&](size_t b) {
+            const size_t at = o;
+            o += (b + 255) / 256 * 256;
+            return at;
+        };
+        y2 = seg((size_t)n * c * 4), long_list = seg(((size_t)n + 1) * 4), head = seg(64);
+        bytes = o;
+    }
+};
+inline bool um_finite(double x) { return x >= -1.7976931348623157e308 && x <= 1.7976931348623157e308; }
+}  // namespace
+
+extern "C" {
+
+int icv_umap_workspace(int64_t n, int64_t nnz, int32_t n_components, int64_t* bytes) {
+    if (!bytes || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 ||
+        (n_components != 2 && n_components != 3))
+        return fail(ICV_ERR_INVALID, "bad umap_workspace arguments");
+    *bytes = (int64_t)UmGeom(n, n_components).bytes;
+    return ICV_OK;
+}
+
+int icv_umap_epochs(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t nnz,
+                    int32_t n_components, double a, double b, double gamma, int32_t negative_sample_rate,
+                    double initial_alpha, int32_t n_epochs, int32_t epoch_begin, int32_t epoch_end, uint64_t seed, float* y,
+                    void* workspace, float* stage_ms, void* stream) {
+    if (!indptr || !y || !workspace || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 ||
+        (nnz > 0 && (!indices || !data)) || (n_components != 2 && n_components != 3) || !um_finite(a) || !(a > 0.0) ||
+        !um_finite(b) || !(b > 0.0) || !um_finite(gamma) || !(gamma >= 0.0) || negative_sample_rate < 0 ||
+        negative_sample_rate > icv::kUmMaxNegatives || !um_finite(initial_alpha) || !(initial_alpha >= 0.0) ||
+        n_epochs < 1 || epoch_begin < 0 || epoch_end < epoch_begin || epoch_end > n_epochs)
+        return fail(ICV_ERR_INVALID, "bad umap_epochs arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const UmGeom G(n, n_components);
+    char* ws = static_cast<char*>(workspace);
+    float* y2 = reinterpret_cast<float*>(ws + G.y2);
+    int32_t* long_list = reinterpret_cast<int32_t*>(ws + G.long_list);
+    unsigned* head = reinterpret_cast<unsigned*>(ws + G.head);
+    float ms[2] = {0, 0};  // validation, epochs
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct EvGuard {
+        hipEvent_t *a, *b;
+        ~EvGuard() {
+            if (*a) (void)hipEventDestroy(*a);
+            if (*b) (void)hipEventDestroy(*b);
+        }
+    } guard{&ev0, &ev1};
+    if (stage_ms) {
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+    }
+    auto tic = [&]() -> hipError_t { return stage_ms ? hipEventRecord(ev0, st) : hipSuccess; };
+    auto toc = [&](int slot) -> hipError_t {
+        if (!stage_ms) return hipSuccess;
+        hipError_t e = hipEventRecord(ev1, st);
+        if (e != hipSuccess) return e;
+        e = hipEventSynchronize(ev1);
+        if (e != hipSuccess) return e;
+        return hipEventElapsedTime(&ms[slot], ev0, ev1);
+    };
+
+    HIP_TRY(tic());
+    HIP_TRY(hipMemsetAsync(head, 0, 64, st));
+    hipLaunchKernelGGL(icv::k_um_check, ld_grid(n, 4), dim3(256), 0, st, indptr, indices, data, n, head, long_list);
+    HIP_TRY(hipGetLastError());
+    unsigned h[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, head, 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(toc(0));
+    const unsigned f = h[0], n_long = h[1];
+    if (f & 8) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix has a column index out of range");
+    if (f & 16) return fail(ICV_ERR_INVALID, "tl.umap: the rows of the adjacency matrix must be sorted, without duplicates");
+    if (f & 1) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix has non-finite values");
+    if (f & 2) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix has negative values");
+    if (f & 4) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix has stored diagonal entries");
+    if (f & 32) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix is not symmetric");
+    float w_max = 0.f;
+    std::memcpy(&w_max, &h[2], 4);
+
+    icv::UmEpoch P;
+    P.a = a, P.b = b, P.c_att = (-2.0 * a) * b, P.c_rep = (2.0 * gamma) * b;
+    P.w_max = (double)w_max, P.w_min = (double)w_max / (double)n_epochs;
+    P.n = n, P.r = negative_sample_rate;
+    const unsigned short_blocks = (unsigned)((n + 3) / 4);
+    const dim3 grid(short_blocks + n_long);
+    float *src = y, *dst = y2;
+    HIP_TRY(tic());
+    for (int32_t t = epoch_begin < 1 ? 1 : epoch_begin; t < epoch_end; ++t) {  // nothing is active in epoch 0
+        P.alpha = initial_alpha * (1.0 - (double)t / (double)n_epochs);
+        P.t = (double)t, P.tm1 = (double)(t - 1);
+        P.base = icv::ld_mix(seed ^ icv::ld_mix((uint64_t)t));
+        if (n_components == 2)
+            hipLaunchKernelGGL(icv::k_um_epoch<2>, grid, dim3(256), 0, st, indptr, indices, data, src, dst, long_list,
+                               short_blocks, P);
+        else
+            hipLaunchKernelGGL(icv::k_um_epoch<3>, grid, dim3(256), 0, st, indptr, indices, data, src, dst, long_list,
+                               short_blocks, P);
+        std::swap(src, dst);
+    }
+    HIP_TRY(hipGetLastError());
+    if (src != y) HIP_TRY(hipMemcpyAsync(y, src, (size_t)n * n_components * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(toc(1));
+    if (stage_ms) stage_ms[0] = ms[0], stage_ms[1] = ms[1];
     return ICV_OK;
 }
 

@@ -34,12 +34,12 @@ def _graph(adata, neighbors_key, adjacency, obsp):
     return adata.obsp[key]
 
 
-def _host_csr(g):
+def _host_csr(g, who="tl.leiden"):
     """Canonical CSR arrays (int64, int32, float32 / float64) of a scipy matrix; shape errors before the GPU."""
     if g.ndim != 2 or g.shape[0] != g.shape[1]:
-        raise ValueError("tl.leiden: the adjacency matrix must be square")
+        raise ValueError(f"{who}: the adjacency matrix must be square")
     if g.shape[0] < 1:
-        raise ValueError("tl.leiden: the adjacency matrix is empty")
+        raise ValueError(f"{who}: the adjacency matrix is empty")
     a = sp.csr_matrix(g)
     if a is g:
         a = a.copy()
