@@ -143,3 +143,66 @@ def mixture(n, d, seed=0, offset=0.0, n_clusters=6):
     lab = rng.integers(0, n_clusters, size=n)
     x = centres[lab] + rng.normal(size=(n, d)) * scale
     return (x + offset * x[:, 0].std()).astype(np.float32)
+
+
+def hub(n=3000, d=50, seed=0):
+    """Normal points normalised to radius 5 and cell 0 at the origin: in 50 dimensions the others are ~ 7 apart, so
+    cell 0 is every cell's nearest neighbour and its connectivity row has n - 1 entries."""
+    rng = np.random.default_rng(seed)
+    x = rng.normal(size=(n, d))
+    x *= 5.0 / np.sqrt((x * x).sum(axis=1, keepdims=True))
+    x[0] = 0.0
+    return x.astype(np.float32)
+
+
+def small_clusters(n_clusters=60, size=10, d=5, spread=1e6, seed=0):
+    """Unit-normal clusters of `size` cells (fewer than k) with centres `spread` apart: a row's k - 1 neighbours are
+    its size - 1 cluster mates and then very far cells, whose membership strengths are 0 in float32."""
+    rng = np.random.default_rng(seed)
+    centres = rng.normal(size=(n_clusters, d)) * spread
+    return (np.repeat(centres, size, axis=0) + rng.normal(size=(n_clusters * size, d))).astype(np.float32)
+
+
+def simplex(n=64):
+    """The n unit vectors: every d2 is 2, so every neighbour is a tie that goes to the lower index."""
+    return np.eye(n, dtype=np.float32)
+
+
+def near_duplicates():
+    """The 3000 x 50 mixture with the duplicate blocks of test_duplicate_blocks, rows 2001 .. 2069 set to row 2000 moved
+    by a few float32 ulps in ONE column each, up (odd row) or down (even row).  Columns are taken by ascending magnitude
+    of row 2000.  Row 2000 holds one value below 2^-5 and two more below 2^-3, so one-ulp steps alone give only three
+    distinct distances up to 1.49e-8; rows 2001 .. 2010 therefore step 1, 1, 2, 2, ... 5, 5 ulps in the smallest column
+    (2^-29 each), and rows 2011 .. 2069 step one ulp in the following columns, two rows per column.  The 14 nearest
+    neighbours of row 2000 are then at 1, 2, 3, 4, 5 x 2^-29 with 4 x 2^-29 = 2^-27 a tie between a four-ulp step and
+    the one-ulp steps of the next two columns: d2 ~ 1e-17 against float32 keys of order 1."""
+    x = mixture(3000, 50, seed=11)
+    x[100:111] = x[100]
+    x[[5, 900, 2999]] = x[5]
+    x[2000:2070] = x[2000]
+    order = np.argsort(np.abs(x[2000]), kind="stable")
+    for m in range(1, 70):
+        c, steps = (order[0], (m + 1) // 2) if m <= 10 else (order[(m - 9) // 2], 1)
+        for _ in range(steps):
+            x[2000 + m, c] = np.nextafter(x[2000 + m, c], np.float32(np.inf if m % 2 else -np.inf))
+    return x
+
+
+LADDER_K = 30
+
+
+def ladder(m=12, n_far=30, d=3, lo=75.0, hi=145.0, seed=0):
+    """A unit-normal cluster of m cells and n_far cells on the first axis at lo .. hi in equal steps, for
+    k = LADDER_K = 30.  A cluster row (sigma ~ 1) lists its m - 1 mates and the k - m nearest rungs with strengths
+    exp(-75 / sigma) .. exp(-116 / sigma): through the float32 subnormals down to 0.  The rungs are nearer to one another than
+    to the cluster and list only rungs, so those strengths reach the connectivities unsymmetrised."""
+    rng = np.random.default_rng(seed)
+    far = np.zeros((n_far, d))
+    far[:, 0] = np.linspace(lo, hi, n_far)
+    return np.concatenate([rng.normal(size=(m, d)), far]).astype(np.float32)
+
+
+def scaled(x, p):
+    """x times 2^p in float32: exact while nothing overflows or becomes subnormal."""
+    with np.errstate(over="ignore", under="ignore"):
+        return np.asarray(x, dtype=np.float32) * np.float32(2.0**p)

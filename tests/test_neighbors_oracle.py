@@ -97,6 +97,88 @@ def test_oracle_five_points_by_hand():
     assert r["distances"].nnz == 10
 
 
+# ---- the edge inputs of tests/test_gpu_neighbors_edges.py: the property that makes each one an edge ---------------------
+TINY = float(np.finfo(np.float32).tiny)  # 2^-126
+
+
+def test_hub_row_has_every_other_cell():
+    c = O.neighbors(O.hub(), 15)["connectivities"]
+    assert np.diff(c.indptr)[0] == 3000 - 1
+
+
+def test_small_clusters_have_far_neighbours_of_weight_zero():
+    x = O.small_clusters()
+    r = O.neighbors(x, 15)
+    same = r["knn_indices"] // 10 == np.arange(600)[:, None] // 10
+    assert np.all(same[:, :9]) and not same[:, 9:].any()  # 9 near, 5 very far
+    assert np.all(r["knn_distances"][:, :9] < 10) and np.all(r["knn_distances"][:, 9:] > 1e4)
+    w32 = r["weights"].astype(np.float32)
+    assert np.all(w32[:, 9:] == 0) and (w32 == 0).sum() == 3000 and w32.size == 8400
+    assert np.all(np.diff(r["connectivities"].indptr) == 9)  # fewer than k - 1
+    assert r["floored"].sum() == 600
+
+
+def test_simplex_is_all_ties_and_floored():
+    x = O.simplex()
+    assert x.dtype == np.float32 and x.shape == (64, 64)
+    r = O.neighbors(x, 15)
+    full = O.sq_dists(x, np.arange(64))
+    assert np.all(full[~np.eye(64, dtype=bool)] == 2.0)
+    assert r["knn_indices"][5].tolist() == [0, 1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14]
+    for i in range(64):  # every neighbour is a tie: the lowest indices win
+        assert r["knn_indices"][i].tolist() == [j for j in range(16) if j != i][:14]
+    assert np.all(r["rho"] > 0) and r["floored"].all()
+    assert np.all(r["sigma"] == 1e-3 * r["rho"])  # the bisection halved 64 times to 2^-64, far below the floor
+
+
+def test_near_duplicates_are_distinct_below_the_float32_keys():
+    x = O.near_duplicates()
+    assert x.dtype == np.float32 and x.shape == (3000, 50)
+    diff = x[2001:2070] != x[2000]
+    assert np.all(diff.sum(axis=1) == 1)  # one column each
+    idx, dist, d2 = O.knn(x, 15)
+    assert np.all((idx[2000] > 2000) & (idx[2000] < 2070))
+    assert np.all(dist[2000] > 0) and np.all(dist[2000] < 1e-8) and np.all(d2[2000] < 1e-16)
+    assert len(np.unique(dist[2000])) >= 4
+    assert len(np.unique(d2[2000])) < 14  # exact ties
+    assert float((x[2000].astype(np.float64) ** 2).sum()) > 1  # float32 keys of order 1: ulp 1e-7 >> d2
+
+
+@pytest.mark.parametrize("p", [60, 100, -70, -100, -120])
+def test_scaling_by_a_power_of_two_keeps_the_neighbours(p):
+    x = O.mixture(1000, 50, seed=1)
+    idx0, dist0, _ = O.knn(x, 15)
+    xs = O.scaled(x, p)
+    assert xs.dtype == np.float32 and np.isfinite(xs).all()
+    idx, dist, _ = O.knn(xs, 15)
+    assert np.array_equal(idx, idx0)
+    n_sub = int(((xs != 0) & (np.abs(xs) < TINY)).sum())
+    if p == -120:
+        assert n_sub > 0  # (455 here)
+        assert np.all(dist >= TINY) and dist.max() < 1e-35  # the distances stay normal numbers
+    else:
+        assert n_sub == 0 and np.array_equal(xs.astype(np.float64), x.astype(np.float64) * 2.0**p)
+        assert np.array_equal(dist.astype(np.float64), dist0.astype(np.float64) * 2.0**p)
+    z2 = ((xs.astype(np.float64) - xs.astype(np.float64).mean(axis=0)) ** 2).sum(axis=1)
+    assert (z2.max() >= 1e37) == (p > 0)  # on which side of the sweep's magnitude gate (1e36) the input lies, with room
+    assert (z2.min() > float(np.finfo(np.float32).max)) == (p == 100)  # |z|^2 overflows float32 on every row
+
+
+def test_ladder_weights_pass_through_the_subnormals_to_zero():
+    x = O.ladder()
+    r = O.neighbors(x, O.LADDER_K)
+    w = r["weights"]
+    w32 = w.astype(np.float32)
+    assert ((w32 > 0) & (w32 < TINY)).sum() >= 5  # (62 here)
+    assert ((w32 == 0) & (w > 0)).sum() >= 5  # (96 here)
+    # no weight within a factor e^(+-1e-6) of the round-to-zero boundary 2^-150 (nor any w == 0 in float64)
+    assert np.all(w > 0) and np.abs(np.log(w) - 150 * np.log(0.5)).min() > 1e-6
+    assert not (r["knn_indices"][12:] < 12).any()  # the rungs do not list the cluster: C = w there
+    c = r["connectivities"]
+    assert (c.data < TINY).sum() >= 5  # subnormal stored entries
+    assert c[:12, 12:].nnz == ((w32[:12] != 0) & (r["knn_indices"][:12] >= 12)).sum() <= 12 * 18 - 5  # dropped ones
+
+
 # ---- the public function without a GPU --------------------------------------------------------------------------------
 def _adata(x, key="X_cnv_pca"):
     from infercnvpy_amd._compat import SimpleAnnData
