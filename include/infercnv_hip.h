@@ -576,6 +576,41 @@ int icv_umap_epochs(const int64_t *indptr, const int32_t *indices, const float *
                     double initial_alpha, int32_t n_epochs, int32_t epoch_begin, int32_t epoch_end, uint64_t seed,
                     float *y, void *workspace, float *stage_ms, void *stream);
 
+/* ---- tl.tsne: deterministic t-SNE with the exact repulsion ---------------------------------------------
+ * icv_tsne_affinities: rule 2 on the stored float32 distances of icv_knn (n x k, nearest first; 1 <= k <= 63;
+ * 0 < perplexity < k), float64, one lane per row: beta[i] by the fixed bisection (at most 64 bracket steps, then 64
+ * halvings, no early exit) on the entropy of exp(-beta (d_r^2 - d_0^2)) with the library's WRITTEN exponential, and the
+ * conditional affinities cond[i * k + r] (a row of equal distances: beta 1, cond 1 / k).  No synchronisation.
+ * icv_tsne_symmetrize_count / _fill: W = A + A^T (A = cond at the columns knn_idx) as canonical CSR, float32, entries
+ * that round to 0 not stored; shapes, temporary memory and the two-call protocol of icv_knn_symmetrize_* (whose k
+ * counts the cell itself: here k is the number of columns of knn_idx, 1 <= k <= 63). */
+int icv_tsne_affinities(const float *knn_dist, int64_t n, int32_t k, double perplexity, double *beta, double *cond,
+                        void *stream);
+int icv_tsne_symmetrize_count(const int32_t *knn_idx, const double *cond, int64_t n, int32_t k, int64_t *row_nnz,
+                              void *stream);
+int icv_tsne_symmetrize_fill(const int32_t *knn_idx, const double *cond, int64_t n, int32_t k, const int64_t *indptr,
+                             int64_t nnz, int32_t *indices, float *data, void *stream);
+/* icv_tsne_iterations runs the iterations [iter_begin, iter_end) of rules 4-6 on the caller's state (device float32,
+ * n x n_components row-major, in / out): positions y, last updates `update` (zeros before iteration 0) and gains (ones
+ * before iteration 0).  Two kernel launches per iteration: the repulsion over all ordered pairs, and the attraction
+ * over the stored entries with the gradient step.  The schedule is stateless (exaggeration early_exaggeration and
+ * momentum 0.5 for t < exaggeration_iters, then 1 and 0.8), so any range may be run alone and [0, T) in one call
+ * equals T calls of one iteration bit for bit; no early stopping.  The graph W is a canonical CSR (indptr int64 n + 1
+ * trusted, indices int32, data float32: rows strictly ascending, finite, 0 <= value <= 2, no diagonal, symmetric
+ * pattern and values; each violation ICV_ERR_INVALID, checked in every call before the state is touched); a row above
+ * 2^22 entries is ICV_ERR_UNSUPPORTED.  n_components: 2 or 3.  early_exaggeration, learning_rate finite and > 0.
+ * Every sum over pairs or entries is an exact int64 sum: the result is a pure function of the arguments.
+ * stage_ms (host, optional): float[2] = validation, iterations.  The host reads three scalars after the validation;
+ * the iterations are enqueued without synchronisation (with stage_ms the call waits for them).
+ * workspace: icv_tsne_workspace(n, nnz, n_components) bytes = 3 x 4 n n_components (the second state buffers)
+ * + 2 x (8 n + 8 n n_components + 256) (two sets of integer accumulators) + 4 ceil(n / 256) (tickets) + 4 (n + 1)
+ * (the long rows) + 256, each part rounded up to 256; nnz only bounds the arguments. */
+int icv_tsne_workspace(int64_t n, int64_t nnz, int32_t n_components, int64_t *bytes);
+int icv_tsne_iterations(const int64_t *indptr, const int32_t *indices, const float *data, int64_t n, int64_t nnz,
+                        int32_t n_components, double early_exaggeration, int32_t exaggeration_iters,
+                        double learning_rate, int32_t iter_begin, int32_t iter_end, float *y, float *update,
+                        float *gains, void *workspace, float *stage_ms, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

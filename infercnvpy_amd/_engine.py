@@ -1724,3 +1724,78 @@ def umap_epochs(indptr, indices, data, y, *, a, b, gamma=1.0, negative_sample_ra
             stage_ms["validation_ms"] = stage_ms.get("validation_ms", 0.0) + float(ms[0])
             stage_ms["epochs_ms"] = stage_ms.get("epochs_ms", 0.0) + float(ms[1])
     return y
+
+
+# ---- tl.tsne: affinities and gradient iterations on the device (icv_tsne*) ---------------------------------
+def tsne_affinities(knn_dist, perplexity):
+    """(beta, cond) of rule 2 for the device distances of :func:`knn` (n x kk float32, nearest first): float64 device
+    tensors n and n x kk."""
+    torch = _torch()
+    lib = _lib.load()
+    n, kk = knn_dist.shape
+    assert knn_dist.is_cuda and knn_dist.dtype == torch.float32 and knn_dist.is_contiguous()
+    with torch.cuda.device(knn_dist.device):
+        beta = torch.empty(n, dtype=torch.float64, device="cuda")
+        cond = torch.empty((n, kk), dtype=torch.float64, device="cuda")
+        _lib.check(lib.icv_tsne_affinities(_ptr(knn_dist), n, kk, float(perplexity), _ptr(beta), _ptr(cond),
+                                           _stream_ptr(torch)))
+    return beta, cond
+
+
+def tsne_symmetrize(knn_idx, cond):
+    """W = A + A^T of the conditional affinities as canonical CSR, float32, no stored zeros: device tensors (indptr int64,
+    indices int32, data float32)."""
+    torch = _torch()
+    lib = _lib.load()
+    n, kk = knn_idx.shape
+    assert knn_idx.is_cuda and knn_idx.dtype == torch.int32 and knn_idx.is_contiguous()
+    assert cond.dtype == torch.float64 and cond.is_contiguous() and tuple(cond.shape) == (n, kk)
+    with torch.cuda.device(knn_idx.device):
+        st = _stream_ptr(torch)
+        counts = torch.empty(n, dtype=torch.int64, device="cuda")
+        _lib.check(lib.icv_tsne_symmetrize_count(_ptr(knn_idx), _ptr(cond), n, kk, _ptr(counts), st))
+        indptr = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+        _lib.check(lib.icv_row_offsets(_ptr(counts), n, _ptr(indptr), st))
+        nnz = int(indptr[-1].item())
+        indices = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
+        data = torch.empty(max(nnz, 1), dtype=torch.float32, device="cuda")
+        _lib.check(lib.icv_tsne_symmetrize_fill(_ptr(knn_idx), _ptr(cond), n, kk, _ptr(indptr), nnz, _ptr(indices),
+                                                _ptr(data), st))
+    return indptr, indices[:nnz], data[:nnz]
+
+
+def tsne_iterations(indptr, indices, data, y, update, gains, *, early_exaggeration=12.0, exaggeration_iters=250,
+                    learning_rate=1000.0, iter_begin=0, iter_end, stage_ms=None):
+    """Run the iterations [iter_begin, iter_end) of DESIGN.md 4.12 on the state (``y``, ``update``, ``gains``: device
+    float32 n x c, c in (2, 3), contiguous; updated in place and returned) for the device CSR graph W (indptr int64
+    n + 1, indices int32, data float32; rows sorted, symmetric).  ``stage_ms``: a dict that receives the milliseconds
+    of the validation and of the iterations (added to what it holds)."""
+    torch = _torch()
+    lib = _lib.load()
+    n = indptr.numel() - 1
+    nnz = indices.numel()
+    assert indptr.is_cuda and indptr.dtype == torch.int64 and indices.dtype == torch.int32 and data.numel() == nnz
+    assert data.dtype == torch.float32 and n >= 1
+    for s in (y, update, gains):
+        assert s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and s.dim() == 2 and s.shape == y.shape
+    assert y.shape[0] == n
+    # the kernels trust the row pointers: check them here (two scalars and one comparison on the device)
+    if int(indptr[0].item()) != 0 or int(indptr[-1].item()) != nnz or bool((indptr[1:] < indptr[:-1]).any().item()):
+        raise ValueError("tl.tsne: indptr must start at 0, be non-decreasing and end at the number of stored entries")
+    if nnz >= 1 << 31:
+        raise ValueError("tl.tsne: at most 2^31 - 1 stored entries are supported")
+    c = int(y.shape[1])
+    with torch.cuda.device(indptr.device):
+        st = _stream_ptr(torch)
+        indptr, indices, data = indptr.contiguous(), indices.contiguous(), data.contiguous()
+        need = C.c_int64(0)
+        _lib.check(lib.icv_tsne_workspace(n, nnz, c, C.byref(need)))
+        ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+        ms = (C.c_float * 2)() if stage_ms is not None else None
+        _lib.check(lib.icv_tsne_iterations(_ptr(indptr), _ptr(indices), _ptr(data), n, nnz, c, float(early_exaggeration),
+                                           int(exaggeration_iters), float(learning_rate), int(iter_begin), int(iter_end),
+                                           _ptr(y), _ptr(update), _ptr(gains), _ptr(ws), ms, st))
+        if stage_ms is not None:
+            stage_ms["validation_ms"] = stage_ms.get("validation_ms", 0.0) + float(ms[0])
+            stage_ms["iterations_ms"] = stage_ms.get("iterations_ms", 0.0) + float(ms[1])
+    return y, update, gains

@@ -41,6 +41,8 @@ EXPORTS = (
     "icv_knn_sort_rows",
     "icv_leiden_workspace", "icv_leiden_quantise", "icv_leiden_iteration", "icv_leiden_sums", "icv_leiden_renumber",
     "icv_umap_workspace", "icv_umap_epochs",
+    "icv_tsne_affinities", "icv_tsne_symmetrize_count", "icv_tsne_symmetrize_fill", "icv_tsne_workspace",
+    "icv_tsne_iterations",
 )
 
 
@@ -173,6 +175,12 @@ def load():
     lib.icv_umap_workspace.argtypes = [i64, i64, i32, P(i64)]
     lib.icv_umap_epochs.argtypes = [vp, vp, vp, i64, i64, i32, dbl, dbl, dbl, i32, dbl, i32, i32, i32, C.c_uint64, vp, vp,
                                     P(C.c_float), vp]
+    lib.icv_tsne_affinities.argtypes = [vp, i64, i32, dbl, vp, vp, vp]
+    lib.icv_tsne_symmetrize_count.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.icv_tsne_symmetrize_fill.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp, vp]
+    lib.icv_tsne_workspace.argtypes = [i64, i64, i32, P(i64)]
+    lib.icv_tsne_iterations.argtypes = [vp, vp, vp, i64, i64, i32, dbl, i32, dbl, i32, i32, vp, vp, vp, vp, P(C.c_float),
+                                        vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -40,6 +40,7 @@
 #include "icv_knn.hpp"
 #include "icv_leiden.hpp"
 #include "icv_umap.hpp"
+#include "icv_tsne.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -3334,7 +3335,7 @@ int icv_knn_symmetrize_count(const int32_t* knn_idx, const double* weights, int6
         return fail(ICV_ERR_INVALID, "bad knn_symmetrize_count arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(row_nnz, 0, (size_t)n * sizeof(int64_t), st));
-    hipLaunchKernelGGL(icv::k_knn_sym_count, dim3((unsigned)((n * (k - 1) + 255) / 256)), dim3(256), 0, st, knn_idx, weights,
+    hipLaunchKernelGGL(icv::k_knn_sym_count<false>, dim3((unsigned)((n * (k - 1) + 255) / 256)), dim3(256), 0, st, knn_idx, weights,
                        n, k - 1, reinterpret_cast<unsigned long long*>(row_nnz));
     HIP_TRY(hipGetLastError());
     return ICV_OK;
@@ -3351,7 +3352,7 @@ int icv_knn_symmetrize_fill(const int32_t* knn_idx, const double* weights, int64
     HIP_TRY(tc.alloc((size_t)nnz * sizeof(int32_t), st));
     HIP_TRY(tv.alloc((size_t)nnz * sizeof(float), st));
     HIP_TRY(hipMemsetAsync(cur.p, 0, (size_t)n * sizeof(unsigned), st));
-    hipLaunchKernelGGL(icv::k_knn_sym_fill, dim3((unsigned)((n * (k - 1) + 255) / 256)), dim3(256), 0, st, knn_idx, weights,
+    hipLaunchKernelGGL(icv::k_knn_sym_fill<false>, dim3((unsigned)((n * (k - 1) + 255) / 256)), dim3(256), 0, st, knn_idx, weights,
                        n, k - 1, indptr, cur.as<unsigned>(), tc.as<int32_t>(), tv.as<float>());
     hipLaunchKernelGGL(icv::k_knn_sort_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, indptr, n, tc.as<int32_t>(),
                        tv.as<float>(), indices, data);
@@ -3844,6 +3845,187 @@ int icv_umap_epochs(const int64_t* indptr, const int32_t* indices, const float* 
     }
     HIP_TRY(hipGetLastError());
     if (src != y) HIP_TRY(hipMemcpyAsync(y, src, (size_t)n * n_components * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(toc(1));
+    if (stage_ms) stage_ms[0] = ms[0], stage_ms[1] = ms[1];
+    return ICV_OK;
+}
+
+}  // extern "C"
+
+// ---- tl.tsne (csrc/icv_tsne.hpp) ---------------------------------------------------------------------------------------
+namespace {
+struct TsGeom {
+    // the second state buffers, two sets of accumulators (row normalisers, repulsion sums, the two halves of Z), the
+    // tickets of k_ts_repulse, the long rows, flags / count / longest row
+    size_t y2, u2, g2, zr[2], rr[2], hl[2], ticket, long_list, head, bytes, zero_begin, zero_end;
+    TsGeom(int64_t n, int32_t c) {
+        size_t o = 0;
+        auto seg = [&](size_t b) {
+            const size_t at = o;
+            o += (b + 255) / 256 * 256;
+            return at;
+        };
+        y2 = seg((size_t)n * c * 4), u2 = seg((size_t)n * c * 4), g2 = seg((size_t)n * c * 4);
+        zero_begin = o;
+        for (int s = 0; s < 2; ++s) zr[s] = seg((size_t)n * 8), rr[s] = seg((size_t)n * c * 8), hl[s] = seg(256);
+        ticket = seg(((size_t)n + 255) / 256 * 4);
+        zero_end = o;
+        long_list = seg(((size_t)n + 1) * 4), head = seg(256);
+        bytes = o;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int icv_tsne_affinities(const float* knn_dist, int64_t n, int32_t k, double perplexity, double* beta, double* cond,
+                        void* stream) {
+    if (!knn_dist || !beta || !cond || n < 1 || k < 1 || k > 63 || !(perplexity > 0.0) || !(perplexity < (double)k))
+        return fail(ICV_ERR_INVALID, "bad tsne_affinities arguments");
+    hipLaunchKernelGGL(icv::k_ts_affinity, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       knn_dist, n, k, std::log(perplexity), beta, cond);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_tsne_symmetrize_count(const int32_t* knn_idx, const double* cond, int64_t n, int32_t k, int64_t* row_nnz,
+                              void* stream) {
+    if (!knn_idx || !cond || !row_nnz || n < 1 || k < 1 || k > 63)
+        return fail(ICV_ERR_INVALID, "bad tsne_symmetrize_count arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(row_nnz, 0, (size_t)n * sizeof(int64_t), st));
+    hipLaunchKernelGGL(icv::k_knn_sym_count<true>, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, knn_idx, cond, n,
+                       k, reinterpret_cast<unsigned long long*>(row_nnz));
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_tsne_symmetrize_fill(const int32_t* knn_idx, const double* cond, int64_t n, int32_t k, const int64_t* indptr,
+                             int64_t nnz, int32_t* indices, float* data, void* stream) {
+    if (!knn_idx || !cond || !indptr || !indices || !data || n < 1 || k < 1 || k > 63 || nnz < 0 || nnz > 2 * n * (int64_t)k)
+        return fail(ICV_ERR_INVALID, "bad tsne_symmetrize_fill arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AsyncBuf cur, tc, tv;
+    HIP_TRY(cur.alloc((size_t)n * sizeof(unsigned), st));
+    HIP_TRY(tc.alloc((size_t)nnz * sizeof(int32_t), st));
+    HIP_TRY(tv.alloc((size_t)nnz * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(cur.p, 0, (size_t)n * sizeof(unsigned), st));
+    hipLaunchKernelGGL(icv::k_knn_sym_fill<true>, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, knn_idx, cond, n,
+                       k, indptr, cur.as<unsigned>(), tc.as<int32_t>(), tv.as<float>());
+    hipLaunchKernelGGL(icv::k_knn_sort_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, indptr, n, tc.as<int32_t>(),
+                       tv.as<float>(), indices, data);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_tsne_workspace(int64_t n, int64_t nnz, int32_t n_components, int64_t* bytes) {
+    if (!bytes || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 ||
+        (n_components != 2 && n_components != 3))
+        return fail(ICV_ERR_INVALID, "bad tsne_workspace arguments");
+    *bytes = (int64_t)TsGeom(n, n_components).bytes;
+    return ICV_OK;
+}
+
+int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t nnz,
+                        int32_t n_components, double early_exaggeration, int32_t exaggeration_iters, double learning_rate,
+                        int32_t iter_begin, int32_t iter_end, float* y, float* update, float* gains, void* workspace,
+                        float* stage_ms, void* stream) {
+    if (!indptr || !y || !update || !gains || !workspace || n < 1 || n > (int64_t)1 << 30 || nnz < 0 ||
+        nnz >= (int64_t)1 << 31 || (nnz > 0 && (!indices || !data)) || (n_components != 2 && n_components != 3) ||
+        !um_finite(early_exaggeration) || !(early_exaggeration > 0.0) || !um_finite(learning_rate) ||
+        !(learning_rate > 0.0) || exaggeration_iters < 0 || iter_begin < 0 || iter_end < iter_begin)
+        return fail(ICV_ERR_INVALID, "bad tsne_iterations arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int32_t C = n_components;
+    const TsGeom G(n, C);
+    char* ws = static_cast<char*>(workspace);
+    int32_t* long_list = reinterpret_cast<int32_t*>(ws + G.long_list);
+    unsigned* head = reinterpret_cast<unsigned*>(ws + G.head);
+    unsigned* ticket = reinterpret_cast<unsigned*>(ws + G.ticket);
+    auto u64 = [&](size_t at) { return reinterpret_cast<unsigned long long*>(ws + at); };
+    float ms[2] = {0, 0};  // validation, iterations
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct EvGuard {
+        hipEvent_t *a, *b;
+        ~EvGuard() {
+            if (*a) (void)hipEventDestroy(*a);
+            if (*b) (void)hipEventDestroy(*b);
+        }
+    } guard{&ev0, &ev1};
+    if (stage_ms) {
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+    }
+    auto tic = [&]() -> hipError_t { return stage_ms ? hipEventRecord(ev0, st) : hipSuccess; };
+    auto toc = [&](int slot) -> hipError_t {
+        if (!stage_ms) return hipSuccess;
+        hipError_t e = hipEventRecord(ev1, st);
+        if (e != hipSuccess) return e;
+        e = hipEventSynchronize(ev1);
+        if (e != hipSuccess) return e;
+        return hipEventElapsedTime(&ms[slot], ev0, ev1);
+    };
+
+    HIP_TRY(tic());
+    HIP_TRY(hipMemsetAsync(head, 0, 64, st));
+    hipLaunchKernelGGL(icv::k_ts_check, ld_grid(n, 4), dim3(256), 0, st, indptr, indices, data, n, head, long_list);
+    HIP_TRY(hipGetLastError());
+    unsigned h[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, head, 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(toc(0));
+    const unsigned f = h[0], n_long = h[1];
+    if (f & 8) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has a column index out of range");
+    if (f & 16) return fail(ICV_ERR_INVALID, "tl.tsne: the rows of the adjacency matrix must be sorted, without duplicates");
+    if (f & 1) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has non-finite values");
+    if (f & 2) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has negative values");
+    if (f & 4) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has stored diagonal entries");
+    if (f & 32) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix is not symmetric");
+    if (f & 64) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has values above 2 (affinities are at most 2)");
+    if ((int64_t)h[2] > icv::kTsMaxRow) return fail(ICV_ERR_UNSUPPORTED, "tl.tsne: a row has more than 2^22 stored entries");
+
+    // the j range is split so that the grid has about 2048 workgroups (8 per CU), in whole tiles
+    const int64_t i_blocks = (n + 255) / 256;
+    int64_t split = (2048 + i_blocks - 1) / i_blocks;
+    const int64_t tiles = (n + icv::kTsTile - 1) / icv::kTsTile;
+    split = split < 1 ? 1 : (split > tiles ? tiles : split);
+    split = split > 65535 ? 65535 : split;
+    const int64_t chunk = (tiles + split - 1) / split * icv::kTsTile;
+    const dim3 rgrid((unsigned)i_blocks, (unsigned)((n + chunk - 1) / chunk));
+    const unsigned short_blocks = (unsigned)((n + 3) / 4);
+    const dim3 sgrid(short_blocks + n_long);
+    icv::TsStep P;
+    P.eta = learning_rate, P.n = n;
+    float *sy = y, *su = update, *sg = gains;
+    float *dy = reinterpret_cast<float*>(ws + G.y2), *du = reinterpret_cast<float*>(ws + G.u2),
+          *dg = reinterpret_cast<float*>(ws + G.g2);
+    HIP_TRY(tic());
+    HIP_TRY(hipMemsetAsync(ws + G.zero_begin, 0, G.zero_end - G.zero_begin, st));
+    int cur = 0;
+    for (int32_t t = iter_begin; t < iter_end; ++t, cur ^= 1) {
+        const bool early = t < exaggeration_iters;
+        P.coef = (early ? early_exaggeration : 1.0) / (2.0 * (double)n);
+        P.mom = early ? 0.5 : 0.8;
+        unsigned long long *zr = u64(G.zr[cur]), *rr = u64(G.rr[cur]), *hl = u64(G.hl[cur]);
+        unsigned long long *zr_n = u64(G.zr[cur ^ 1]), *rr_n = u64(G.rr[cur ^ 1]), *hl_n = u64(G.hl[cur ^ 1]);
+        if (C == 2) {
+            hipLaunchKernelGGL(icv::k_ts_repulse<2>, rgrid, dim3(256), 0, st, sy, n, chunk, zr, rr, hl, ticket);
+            hipLaunchKernelGGL(icv::k_ts_step<2>, sgrid, dim3(256), 0, st, indptr, indices, data, long_list, short_blocks, P,
+                               rr, hl, zr_n, rr_n, hl_n, sy, su, sg, dy, du, dg);
+        } else {
+            hipLaunchKernelGGL(icv::k_ts_repulse<3>, rgrid, dim3(256), 0, st, sy, n, chunk, zr, rr, hl, ticket);
+            hipLaunchKernelGGL(icv::k_ts_step<3>, sgrid, dim3(256), 0, st, indptr, indices, data, long_list, short_blocks, P,
+                               rr, hl, zr_n, rr_n, hl_n, sy, su, sg, dy, du, dg);
+        }
+        std::swap(sy, dy), std::swap(su, du), std::swap(sg, dg);
+    }
+    HIP_TRY(hipGetLastError());
+    if (sy != y) {
+        const size_t bytes = (size_t)n * C * 4;
+        HIP_TRY(hipMemcpyAsync(y, sy, bytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(update, su, bytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(gains, sg, bytes, hipMemcpyDeviceToDevice, st));
+    }
     HIP_TRY(toc(1));
     if (stage_ms) stage_ms[0] = ms[0], stage_ms[1] = ms[1];
     return ICV_OK;

@@ -376,7 +376,9 @@ __global__ void __launch_bounds__(256) k_knn_smooth(const float* __restrict__ di
     }
 }
 
-// value of C at (i, idx[i][s]) and whether row j = idx[i][s] lists i
+// value of C at (i, idx[i][s]) and whether row j = idx[i][s] lists i.  SUM = false: the fuzzy union A + A^T - A o A^T
+// (pp.neighbors); SUM = true: A + A^T (tl.tsne, DESIGN.md 4.12 rule 3)
+template <bool SUM>
 __device__ __forceinline__ float knn_sym_value(const int32_t* __restrict__ idx, const double* __restrict__ w, int km1,
                                                int64_t i, int s, int& j, bool& mutual) {
     j = idx[i * km1 + s];
@@ -390,11 +392,12 @@ __device__ __forceinline__ float knn_sym_value(const int32_t* __restrict__ idx, 
             mutual = true;
             break;
         }
-    return (float)((wij + wji) - wij * wji);
+    return SUM ? (float)(wij + wji) : (float)((wij + wji) - wij * wji);
 }
 
 // count[r] += stored entries of row r of C: its own neighbours, and the rows that list r without being listed by it
 // (integer atomics: the counts do not depend on the order).  Entries that round to 0 in float32 are not stored.
+template <bool SUM>
 __global__ void __launch_bounds__(256) k_knn_sym_count(const int32_t* __restrict__ idx, const double* __restrict__ w,
                                                        int64_t n, int km1, unsigned long long* __restrict__ count) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -402,13 +405,14 @@ __global__ void __launch_bounds__(256) k_knn_sym_count(const int32_t* __restrict
     const int64_t i = e / km1;
     int j;
     bool mutual;
-    const float c = knn_sym_value(idx, w, km1, i, (int)(e - i * km1), j, mutual);
+    const float c = knn_sym_value<SUM>(idx, w, km1, i, (int)(e - i * km1), j, mutual);
     if (c == 0.0f) return;
     atomicAdd(count + i, 1ull);
     if (!mutual) atomicAdd(count + j, 1ull);
 }
 
 // the same walk, writing (column, value) at indptr[row] + cursor[row]++ (any order: k_knn_sort_rows makes it canonical)
+template <bool SUM>
 __global__ void __launch_bounds__(256) k_knn_sym_fill(const int32_t* __restrict__ idx, const double* __restrict__ w,
                                                       int64_t n, int km1, const int64_t* __restrict__ indptr,
                                                       unsigned* __restrict__ cursor, int32_t* __restrict__ cols,
@@ -418,7 +422,7 @@ __global__ void __launch_bounds__(256) k_knn_sym_fill(const int32_t* __restrict_
     const int64_t i = e / km1;
     int j;
     bool mutual;
-    const float c = knn_sym_value(idx, w, km1, i, (int)(e - i * km1), j, mutual);
+    const float c = knn_sym_value<SUM>(idx, w, km1, i, (int)(e - i * km1), j, mutual);
     if (c == 0.0f) return;
     int64_t p = indptr[i] + atomicAdd(cursor + i, 1u);
     cols[p] = j;

@@ -1,8 +1,9 @@
 from ._infercnv import infercnv, infercnv_device
 from ._leiden import leiden
 from ._pca import pca
+from ._tsne import tsne
 from ._umap import umap
 from ._linkage import cell_linkage, leaves_list, ward_linkage
 from ._scores import cnv_score, ithcna, ithgex
 
-__all__ = ["infercnv", "infercnv_device", "pca", "leiden", "umap", "cnv_score", "ithcna", "ithgex", "cell_linkage", "ward_linkage", "leaves_list"]
+__all__ = ["infercnv", "infercnv_device", "pca", "leiden", "umap", "tsne", "cnv_score", "ithcna", "ithgex", "cell_linkage", "ward_linkage", "leaves_list"]
