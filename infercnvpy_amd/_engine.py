@@ -1613,10 +1613,10 @@ def leiden_quality(e, K, resolution):
     return math.fsum((float(ec) - resolution * float(kc) * float(kc) / Mf) / Mf for ec, kc in zip(e, K))
 
 
-def leiden(indptr, indices, data, resolution=1.0, random_state=0, n_iterations=-1, use_weights=True, stages=None):
-    """(labels, info) of DESIGN.md 4.10 for the device CSR graph (indptr int64 n + 1, indices int32, data float32 /
-    float64; rows sorted): labels is a device int32 tensor numbered by rule 6.  ``stages``: a list that receives one
-    dict of milliseconds per iteration."""
+def leiden_quantise(indptr, indices, data, use_weights=True):
+    """Rules 1-2 of DESIGN.md 4.10 (icv_leiden_quantise) for the device CSR graph (indptr int64 n + 1, indices int32,
+    data float32 / float64): (q_indptr int64 n + 1, q_indices int32, q_weights int64, total) with the kept entries only
+    and total = the sum of the integer weights; ValueError for every violation of rule 1 or 2."""
     torch = _torch()
     lib = _lib.load()
     n = indptr.numel() - 1
@@ -1628,35 +1628,75 @@ def leiden(indptr, indices, data, resolution=1.0, random_state=0, n_iterations=-
         raise ValueError("tl.leiden: indptr must start at 0, be non-decreasing and end at the number of stored entries")
     if nnz >= 1 << 31:
         raise ValueError("tl.leiden: at most 2^31 - 1 stored entries are supported")
-    seed = int(random_state) & ((1 << 64) - 1)
-    info = {"quality": [], "n_iterations": 0, "levels": [], "rounds": [], "bound_reached": False}
     with torch.cuda.device(indptr.device):
-        st = _stream_ptr(torch)
         indptr, indices, data = indptr.contiguous(), indices.contiguous(), data.contiguous()
         q_indptr = torch.empty(n + 1, dtype=torch.int64, device="cuda")
         q_indices = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
         q_w = torch.empty(max(nnz, 1), dtype=torch.int64, device="cuda")
         res = (C.c_int64 * 2)()
-        t0 = _time.perf_counter()
         _lib.check(lib.icv_leiden_quantise(_ptr(indptr), _ptr(indices), _ptr(data),
                                            _lib.ICV_F32 if data.dtype == torch.float32 else _lib.ICV_F64, n, nnz,
-                                           int(bool(use_weights)), _ptr(q_indptr), _ptr(q_indices), _ptr(q_w), res, st))
-        quantise_ms = (_time.perf_counter() - t0) * 1e3
-        kept, M = int(res[0]), int(res[1])
+                                           int(bool(use_weights)), _ptr(q_indptr), _ptr(q_indices), _ptr(q_w), res,
+                                           _stream_ptr(torch)))
+    kept = int(res[0])
+    return q_indptr, q_indices[:kept], q_w[:kept], int(res[1])
+
+
+def leiden_workspace(n, nnz):
+    """The uint8 device tensor leiden_iteration needs for a graph of n vertices and nnz integer entries."""
+    need = C.c_int64(0)
+    _lib.check(_lib.load().icv_leiden_workspace(n, nnz, C.byref(need)))
+    return _torch().empty(need.value, dtype=_torch().uint8, device="cuda")
+
+
+def leiden_iteration(q_indptr, q_indices, q_w, gom, seed, it, labels, workspace, stage_ms=None):
+    """ONE iteration of rule 4 (icv_leiden_iteration) of the integer graph of leiden_quantise from the partition in
+    ``labels`` (device int32 n, ids in [0, n); overwritten by the new partition, not renumbered): (vertices per level,
+    (local moving, refinement) rounds per level, local moves of all levels, whether a rule-5 bound was reached).
+    ``gom`` = resolution / float(total), ``seed`` in [0, 2^64), ``it`` the iteration's index, ``workspace`` of
+    leiden_workspace(n, entries); ``stage_ms``: a ctypes float[4] that receives the stage times."""
+    torch = _torch()
+    lib = _lib.load()
+    n = q_indptr.numel() - 1
+    nnz = q_indices.numel()
+    assert q_indptr.is_cuda and q_indptr.dtype == torch.int64 and q_indices.dtype == torch.int32
+    assert q_w.dtype == torch.int64 and q_w.numel() == nnz and q_indices.is_contiguous() and q_w.is_contiguous()
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.numel() == n and labels.is_contiguous()
+    trace = (C.c_int32 * (3 * 64))()
+    n_levels, n_moves, bound = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+    with torch.cuda.device(q_indptr.device):
+        _lib.check(lib.icv_leiden_iteration(_ptr(q_indptr), _ptr(q_indices), _ptr(q_w), n, nnz, float(gom), int(seed),
+                                            int(it), _ptr(labels), _ptr(workspace), trace, C.byref(n_levels),
+                                            C.byref(n_moves), C.byref(bound), stage_ms, _stream_ptr(torch)))
+    nl = n_levels.value
+    return ([int(trace[3 * i]) for i in range(nl)], [(int(trace[3 * i + 1]), int(trace[3 * i + 2])) for i in range(nl)],
+            int(n_moves.value), bool(bound.value))
+
+
+def leiden(indptr, indices, data, resolution=1.0, random_state=0, n_iterations=-1, use_weights=True, stages=None):
+    """(labels, info) of DESIGN.md 4.10 for the device CSR graph (indptr int64 n + 1, indices int32, data float32 /
+    float64; rows sorted): labels is a device int32 tensor numbered by rule 6.  ``stages``: a list that receives one
+    dict of milliseconds per iteration."""
+    torch = _torch()
+    lib = _lib.load()
+    n = indptr.numel() - 1
+    seed = int(random_state) & ((1 << 64) - 1)
+    info = {"quality": [], "n_iterations": 0, "levels": [], "rounds": [], "bound_reached": False}
+    t0 = _time.perf_counter()
+    q_indptr, q_indices, q_w, M = leiden_quantise(indptr, indices, data, use_weights)
+    quantise_ms = (_time.perf_counter() - t0) * 1e3
+    with torch.cuda.device(indptr.device):
+        st = _stream_ptr(torch)
         labels = torch.arange(n, dtype=torch.int32, device="cuda")
         out = labels  # without weight: n singletons, numbered by rule 6 already
         n_comm = C.c_int32(n)
         if M > 0:
             gom = float(resolution) / float(M)
-            need = C.c_int64(0)
-            _lib.check(lib.icv_leiden_workspace(n, kept, C.byref(need)))
-            ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+            ws = leiden_workspace(n, q_indices.numel())
             out = torch.empty_like(labels)
-            info["workspace_bytes"] = int(need.value)
+            info["workspace_bytes"] = int(ws.numel())
             e = torch.empty(n, dtype=torch.int64, device="cuda")
             K = torch.empty(n, dtype=torch.int64, device="cuda")
-            trace = (C.c_int32 * (3 * 64))()
-            n_levels, n_moves, bound = C.c_int32(0), C.c_int64(0), C.c_int32(0)
             ms = (C.c_float * 4)() if stages is not None else None
             it = 0
             while True:
@@ -1665,14 +1705,11 @@ def leiden(indptr, indices, data, resolution=1.0, random_state=0, n_iterations=-
                 if it == LEIDEN_MAX_ITERATIONS:
                     info["bound_reached"] = info["bound_reached"] or n_iterations < 0
                     break
-                _lib.check(lib.icv_leiden_iteration(_ptr(q_indptr), _ptr(q_indices), _ptr(q_w), n, kept, gom, seed, it,
-                                                    _ptr(labels), _ptr(ws), trace, C.byref(n_levels), C.byref(n_moves),
-                                                    C.byref(bound), ms, st))
+                levels, rounds, moves, bound = leiden_iteration(q_indptr, q_indices, q_w, gom, seed, it, labels, ws, ms)
                 it += 1
-                nl = n_levels.value
-                info["levels"].append([int(trace[3 * i]) for i in range(nl)])
-                info["rounds"].append([(int(trace[3 * i + 1]), int(trace[3 * i + 2])) for i in range(nl)])
-                info["bound_reached"] = info["bound_reached"] or bool(bound.value)
+                info["levels"].append(levels)
+                info["rounds"].append(rounds)
+                info["bound_reached"] = info["bound_reached"] or bound
                 _lib.check(lib.icv_leiden_renumber(_ptr(labels), n, _ptr(out), C.byref(n_comm), st))
                 _lib.check(lib.icv_leiden_sums(_ptr(q_indptr), _ptr(q_indices), _ptr(q_w), n, _ptr(out), _ptr(e), _ptr(K),
                                                st))
@@ -1681,7 +1718,7 @@ def leiden(indptr, indices, data, resolution=1.0, random_state=0, n_iterations=-
                 if stages is not None:
                     stages.append({"local_moving_ms": float(ms[0]), "refinement_ms": float(ms[1]),
                                    "aggregation_ms": float(ms[2]), "rest_ms": float(ms[3]), "quantise_ms": quantise_ms})
-                if n_iterations < 0 and n_moves.value == 0:
+                if n_iterations < 0 and moves == 0:
                     break
             info["n_iterations"] = it
         info["n_communities"] = int(n_comm.value)

@@ -119,18 +119,46 @@ def _segment_sums(key, w):
     return ks[start], np.add.reduceat(ws, start)
 
 
-def _gain(gom, dk, kv, dK):
+def _inexact(*ints):
+    """How many of the int64 values are not float64 numbers (their conversion rounds)."""
+    return sum(int((np.asarray(x).astype(np.float64).astype(np.int64) != x).sum()) for x in ints)
+
+
+def _gain(gom, dk, kv, dK, stats=None):
+    if stats is not None:
+        stats["inexact_gain"] += _inexact(dk, kv, dK)
     return dk.astype(np.float64) - (gom * kv.astype(np.float64)) * dK.astype(np.float64)
 
 
-def _wellconn(gom, E, K, T):
+def _wellconn(gom, E, K, T, stats=None):
+    if stats is not None:
+        stats["inexact_wellconn"] += _inexact(E, K, T - K)
     return E.astype(np.float64) >= (gom * K.astype(np.float64)) * (T - K).astype(np.float64)
+
+
+def new_stats():
+    """The branch counters `iteration` fills (they only observe):
+    empty_rounds          local-moving rounds in which a selected vertex chose EMPTY
+    empty_short_rounds    ... in which the selected EMPTY vertices outnumbered the free ids
+    empty_got_none        selected EMPTY vertices that got no id (rule 4d, "none if they ran out")
+    tie_lower_id          decisions taken whose best gain was shared by another candidate (the lower id won)
+    zero_gain_refine      refinement decisions taken at gain == 0 exactly
+    refine_candidates_rejected / refine_movers_rejected    by wellconn
+    blocked               wanting vertices that took part in a round and lost to a neighbour (rule 4c)
+    thinned               wanting vertices left out of a local-moving round by the top priority bit
+    row_lengths           per level entered: (level, sorted distinct row lengths)
+    inexact_gain / inexact_wellconn   int64 values converted to float64 that were not float64 numbers"""
+    s = dict.fromkeys(("empty_rounds", "empty_short_rounds", "empty_got_none", "tie_lower_id", "zero_gain_refine",
+                       "refine_candidates_rejected", "refine_movers_rejected", "blocked", "thinned", "inexact_gain",
+                       "inexact_wellconn"), 0)
+    s["row_lengths"] = []
+    return s
 
 
 EMPTY = -2
 
 
-def _decide(L, gom, label, KL, cntL, refine, comm=None, Kc=None, ext=None):
+def _decide(L, gom, label, KL, cntL, refine, comm=None, Kc=None, ext=None, stats=None):
     """want[v] (target label, EMPTY, or -1) and wantw[v] = k_{v -> target} from the snapshot."""
     n = L.n
     want = np.full(n, -1, dtype=np.int64)
@@ -144,48 +172,66 @@ def _decide(L, gom, label, KL, cntL, refine, comm=None, Kc=None, ext=None):
     own = pc == a[pv]
     kva[pv[own]] = s[own]
     if refine:
-        mover = (cntL[a] == 1) & _wellconn(gom, ext, L.k, Kc[comm])
-        ok = ~own & mover[pv] & _wellconn(gom, ext[pc], KL[pc], Kc[comm[pv]])
+        single = cntL[a] == 1
+        mover = single & _wellconn(gom, ext, L.k, Kc[comm], stats)
+        cand = _wellconn(gom, ext[pc], KL[pc], Kc[comm[pv]], stats)
+        ok = ~own & mover[pv] & cand
+        if stats is not None:
+            stats["refine_movers_rejected"] += int((single & ~mover).sum())
+            stats["refine_candidates_rejected"] += int((~own & mover[pv] & ~cand).sum())
     else:
         ok = ~own
     pv, pc, s = pv[ok], pc[ok], s[ok]
-    g = _gain(gom, s - kva[pv], L.k[pv], KL[pc] - KL[a[pv]] + L.k[pv])
+    g = _gain(gom, s - kva[pv], L.k[pv], KL[pc] - KL[a[pv]] + L.k[pv], stats)
     o = np.lexsort((pc, -g, pv))
     pv, pc, s, g = pv[o], pc[o], s[o], g[o]
     first = np.flatnonzero(np.concatenate([[True], pv[1:] != pv[:-1]])) if len(pv) else np.zeros(0, dtype=np.int64)
     bv, bc, bs, bg = pv[first], pc[first], s[first], g[first]
+    if stats is not None and len(pv):
+        nxt = np.minimum(first + 1, len(pv) - 1)
+        tied = (nxt > first) & (pv[nxt] == bv) & (g[nxt] == bg)  # the runner-up has the same gain: the lower id won
     best_g = np.full(n, -np.inf)
     best_g[bv] = bg
     if refine:
         sel = bg >= 0
         want[bv[sel]] = bc[sel]
         wantw[bv[sel]] = bs[sel]
+        if stats is not None and len(pv):
+            stats["tie_lower_id"] += int((tied & sel).sum())
+            stats["zero_gain_refine"] += int((bg == 0).sum())
         return want, wantw
     sel = bg > 0
     want[bv[sel]] = bc[sel]
     has_entries = np.diff(L.indptr) > 0
-    ge = _gain(gom, -kva, L.k, L.k - KL[a])
+    ge = _gain(gom, -kva, L.k, L.k - KL[a], stats)
     to_empty = has_entries & (cntL[a] > 1) & (ge > 0) & (ge > best_g)
     want[to_empty] = EMPTY
+    if stats is not None and len(pv):
+        stats["tie_lower_id"] += int((tied & sel & ~to_empty[bv]).sum())
     return want, wantw
 
 
-def _select(L, want, label, s, thin):
+def _select(L, want, label, s, thin, stats=None):
     """Rule 4c: the wanting vertices that move this round."""
     p = prio(s, L.n)
     wants = want != -1
     if thin:
-        wants &= (p >> np.uint64(63)) == 1
+        top = (p >> np.uint64(63)) == 1
+        if stats is not None:
+            stats["thinned"] += int((wants & ~top).sum())
+        wants &= top
     r, c = L.row, L.col
     both = wants[r] & wants[c] & ((want[c] == label[r]) | (label[c] == want[r]))
     r, c = r[both], c[both]
     beats = (p[r] > p[c]) | ((p[r] == p[c]) & (r < c))
     lose = np.zeros(L.n, dtype=bool)
     lose[r[~beats]] = True
+    if stats is not None:
+        stats["blocked"] += int((wants & lose).sum())
     return np.where(wants & ~lose, want, -1)
 
 
-def _local_moving(L, gom, comm, seed, it, level):
+def _local_moving(L, gom, comm, seed, it, level, stats=None):
     n = L.n
     K = np.zeros(n, dtype=np.int64)
     np.add.at(K, comm, L.k)
@@ -195,15 +241,19 @@ def _local_moving(L, gom, comm, seed, it, level):
         if rounds == max_rounds(n):
             bound = True
             break
-        want, _ = _decide(L, gom, comm, K, cnt, False)
+        want, _ = _decide(L, gom, comm, K, cnt, False, stats=stats)
         if not (want != -1).any():
             break
-        sel = _select(L, want, comm, round_base(seed, it, level, 0, rounds), True)
+        sel = _select(L, want, comm, round_base(seed, it, level, 0, rounds), True, stats)
         rounds += 1
         we = np.flatnonzero(sel == EMPTY)
         if len(we):
             free = np.flatnonzero(cnt == 0)
             m = min(len(we), len(free))
+            if stats is not None:
+                stats["empty_rounds"] += 1
+                stats["empty_short_rounds"] += len(we) > len(free)
+                stats["empty_got_none"] += len(we) - m
             sel[we[:m]] = free[:m]
             sel[we[m:]] = -1
         mv = np.flatnonzero(sel >= 0)
@@ -217,7 +267,7 @@ def _local_moving(L, gom, comm, seed, it, level):
     return moves, rounds, bound
 
 
-def _refine(L, gom, comm, seed, it, level):
+def _refine(L, gom, comm, seed, it, level, stats=None):
     n = L.n
     Kc = np.zeros(n, dtype=np.int64)
     np.add.at(Kc, comm, L.k)
@@ -232,10 +282,10 @@ def _refine(L, gom, comm, seed, it, level):
         if rounds == max_rounds(n):
             bound = True
             break
-        want, wantw = _decide(L, gom, sub, Ks, cs, True, comm, Kc, ext)
+        want, wantw = _decide(L, gom, sub, Ks, cs, True, comm, Kc, ext, stats)
         if not (want != -1).any():
             break
-        sel = _select(L, want, sub, round_base(seed, it, level, 1, rounds), False)
+        sel = _select(L, want, sub, round_base(seed, it, level, 1, rounds), False, stats)
         rounds += 1
         mv = np.flatnonzero(sel >= 0)
         t = sel[mv]
@@ -304,14 +354,40 @@ def renumber(labels):
     return new[labels].astype(np.int32)
 
 
-def leiden(graph, resolution=1.0, random_state=0, n_iterations=-1, use_weights=True, return_info=False):
+def iteration(indptr, indices, w, gom, seed, it, labels, stats=None):
+    """ONE iteration (rule 4) of the integer graph from ANY partition `labels` (ids in [0, n)), as icv_leiden_iteration
+    runs it: (labels_out int64, not renumbered; vertices per level; (local moving, refinement) rounds per level; the
+    local moves of all levels; whether a rule-5 bound was reached).  `stats` (new_stats()) receives the branch counters."""
+    n = len(indptr) - 1
+    seed = int(seed) & MASK
+    L = _Level(np.asarray(indptr, dtype=np.int64), np.asarray(indices), np.asarray(w, dtype=np.int64),
+               np.zeros(n, dtype=np.int64))
+    comm, o2c = np.array(labels, dtype=np.int64), np.arange(n, dtype=np.int64)
+    total, sizes, rnds, bound, done = 0, [], [], False, False
+    for level in range(MAX_LEVELS):
+        if stats is not None:
+            stats["row_lengths"].append((level, np.unique(np.diff(L.indptr))))
+        moves, r_move, b1 = _local_moving(L, gom, comm, seed, it, level, stats)
+        sub, r_ref, b2 = _refine(L, gom, comm, seed, it, level, stats)
+        total += moves
+        sizes.append(L.n)
+        rnds.append((r_move, r_ref))
+        bound |= b1 or b2
+        if len(np.unique(sub)) == L.n:
+            done = True
+            break
+        L, comm, r = _aggregate(L, comm, sub)
+        o2c = r[o2c]
+    return comm[o2c], sizes, rnds, total, bound or not done
+
+
+def leiden(graph, resolution=1.0, random_state=0, n_iterations=-1, use_weights=True, return_info=False, stats=None):
     """Labels (int32, rule 6) of DESIGN 4.10; with return_info also the dict tl.leiden reports."""
     indptr, indices, w = quantise(graph, use_weights)
     n = len(indptr) - 1
     resolution = float(resolution)
     seed = int(random_state) & MASK
-    L0 = _Level(indptr, indices, w, np.zeros(n, dtype=np.int64))
-    M = int(sum(int(x) for x in L0.k))
+    M = sum(int(x) for x in w)
     info = {"quality": [], "n_iterations": 0, "levels": [], "rounds": [], "bound_reached": False}
     labels = np.arange(n, dtype=np.int64)
     if M > 0:
@@ -321,25 +397,11 @@ def leiden(graph, resolution=1.0, random_state=0, n_iterations=-1, use_weights=T
             if n_iterations > 0 and it == n_iterations:
                 break
             if it == MAX_ITERATIONS:
-                info["bound_reached"] = n_iterations < 0
+                info["bound_reached"] = info["bound_reached"] or n_iterations < 0
                 break
-            L, comm, o2c = L0, labels.copy(), np.arange(n, dtype=np.int64)
-            total, sizes, rnds, done = 0, [], [], False
-            for level in range(MAX_LEVELS):
-                moves, r_move, b1 = _local_moving(L, gom, comm, seed, it, level)
-                sub, r_ref, b2 = _refine(L, gom, comm, seed, it, level)
-                total += moves
-                sizes.append(L.n)
-                rnds.append((r_move, r_ref))
-                info["bound_reached"] |= b1 or b2
-                if len(np.unique(sub)) == L.n:
-                    done = True
-                    break
-                L, comm, r = _aggregate(L, comm, sub)
-                o2c = r[o2c]
-            info["bound_reached"] |= not done
-            labels = comm[o2c]
+            labels, sizes, rnds, total, bound = iteration(indptr, indices, w, gom, seed, it, labels, stats)
             it += 1
+            info["bound_reached"] = info["bound_reached"] or bound
             info["levels"].append(sizes)
             info["rounds"].append(rnds)
             info["quality"].append(quality(*community_sums(indptr, indices, w, renumber(labels)), resolution))
@@ -505,3 +567,180 @@ def small_graphs():
         "n2": path(2),
         "wide_weights": wide_weights(),
     }
+
+
+# ---- edge builders (tests/test_gpu_leiden_edges.py; test_leiden_oracle.py asserts that the oracle reaches each branch) -
+def rows_at_split():
+    """Rows of 511, 512, 513 and 514 entries: around the 512 at which a row leaves the LDS kernel for the long-row one."""
+    return cliques([513, 514, 512], ring=True)
+
+
+SPLIT_HUBS = (511, 512, 513, 514, 515)
+
+
+def pairs_with_hubs(pairs=515, hubs=SPLIT_HUBS, weight=2.0 ** -20):
+    """`pairs` disjoint edges plus one hub per entry t of `hubs`, joined to the first vertex of the first t edges by a
+    light edge.  Every edge becomes one vertex of the aggregate, so the hubs have rows on both sides of 512 entries at
+    level 0 AND at level 1."""
+    n = 2 * pairs + len(hubs)
+    r = [np.arange(0, 2 * pairs, 2)]
+    c = [np.arange(1, 2 * pairs, 2)]
+    v = [np.ones(pairs)]
+    for h, t in enumerate(hubs):
+        r.append(np.arange(0, 2 * t, 2))
+        c.append(np.full(t, 2 * pairs + h))
+        v.append(np.full(t, weight))
+    return _sym(np.concatenate(r), np.concatenate(c), np.concatenate(v), n)
+
+
+def heavy_mixed(n=300, seed=0):
+    """Random graph, half of its weights 2^18 (1 + j 2^-23) and half j 2^-32, j in [1, 4096): float32 numbers whose
+    integer weights 2^50 + j 2^27 and j add up to sums of more than 53 bits, so the int64 -> float64 conversions of the
+    gain and of wellconn round."""
+    rng = np.random.default_rng(seed)
+    m = 4 * n
+    r, c = rng.integers(0, n, m), rng.integers(0, n, m)
+    keep = r < c
+    r, c = r[keep], c[keep]
+    _, first = np.unique(r * n + c, return_index=True)
+    r, c = r[first], c[first]
+    j = rng.integers(1, 4096, len(r)).astype(np.float64)
+    heavy = rng.permutation(len(r)) < len(r) // 2
+    return _sym(r, c, np.where(heavy, 2.0 ** 18 * (1 + j * 2.0 ** -23), j * 2.0 ** -32), n)
+
+
+def near_limit():
+    """name -> graph at the limit sum w < 2^62 of rule 2; the names that start with "over" must raise."""
+    r = np.array([0, 1, 2, 3, 4, 0, 1, 2, 0])
+    c = np.array([1, 2, 3, 4, 5, 2, 3, 5, 5])
+    v = np.array([2.0 ** 27, 2.0 ** 26, 2.0 ** 26 * (1 + 2.0 ** -23), 2.0 ** 27 - 8, 2.0 ** 25, 5 * 2.0 ** -32, 2.0 ** -7,
+                  3 * 2.0 ** -32, 2.0 ** 25 * (1 + 2.0 ** -22)])
+    return {
+        "pair_below": path(2) * (2.0 ** 29 - 32),       # sum w = 2^62 - 2^38
+        "mixed_below": _sym(r, c, v, 6),                # sum w = 0.875 2^62, with weights of 3 and 5 in it
+        "over_pair": path(2) * 2.0 ** 29,               # sum w = 2^62 exactly, every value below 2^30
+        "over_k3": complete(3) * 2.0 ** 29,
+    }
+
+
+def rint_ties():
+    """Path whose edge i has the value (i + 1) 2^-33, i < 9: w = rint((i + 1) / 2) with the ties 0.5, 1.5, 2.5, 3.5 and
+    4.5 (to even: 0, 2, 2, 4, 4); then a float32 subnormal (w = 0: dropped) and a weight of 1 that closes the ring."""
+    vals = np.concatenate([np.arange(1, 10) * 2.0 ** -33, [2.0 ** -140, 1.0]])
+    n = len(vals)
+    return _sym(np.arange(n), (np.arange(n) + 1) % n, vals, n)
+
+
+def cycle(n):
+    return _sym(np.arange(n), (np.arange(n) + 1) % n, np.ones(n), n)
+
+
+EMPTIES_GAMMA = 8.0
+# (n, members, random_state): found by empties_search(); every `it` of EMPTIES_ITS runs out of free ids with that seed
+EMPTIES_ITS = (0, 1, 63)
+EMPTIES_CASES = {"two": (12, 2, 13), "five": (14, 5, 8)}
+
+
+def empties_run_out(n, members):
+    """(graph, labels): a cycle of n vertices; `members` non-adjacent vertices (0, 2, 4, ...) share the label 0, every
+    other vertex is alone, so members - 1 ids are free.  At gamma = EMPTIES_GAMMA > n / 2 no vertex gains by joining a
+    neighbour and every member prefers an empty community: when all of them are selected in one round, one gets none."""
+    labels = np.arange(n, dtype=np.int32)
+    labels[0:2 * members:2] = 0
+    return cycle(n), labels
+
+
+def empties_search(n, members, seeds=range(4096)):
+    """The first random_state of `seeds` at which the case runs out of free ids for every `it` of EMPTIES_ITS."""
+    g, labels = empties_run_out(n, members)
+    indptr, indices, w = quantise(g)
+    gom = EMPTIES_GAMMA / float(sum(int(x) for x in w))
+    for seed in seeds:
+        for it in EMPTIES_ITS:
+            st = new_stats()
+            iteration(indptr, indices, w, gom, seed, it, labels, st)
+            if st["empty_got_none"] == 0:
+                break
+        else:
+            return seed
+    return None
+
+
+def zero_gain_cases():
+    """name -> (graph, gamma): complete graphs in ONE community at gamma = n / (n - 1), where joining a neighbour in the
+    refinement has the gain 0 exactly (w - (gamma / (n (n - 1) w)) ((n - 1) w)^2, every product a float64 number): the
+    refinement merges at gain >= 0, so the iteration has a second level."""
+    return {"k2": (complete(2), 2.0), "k3": (complete(3), 1.5), "k5": (complete(5), 1.25)}
+
+
+def kv_not_float32():
+    """(graph, gamma): the path 0 - 1 - 2 with w_01 = 2^32 and w_12 = 1, so k_1 = 2^32 + 1 is a float64 but no float32
+    number, at gamma = 2 (1 + 2^-34): the gain of 1 joining 0 is 2^32 - gom (2^32 + 1) 2^32 = -0.25, no move, and +0.75
+    with k_1 rounded to float32.  Nothing moves: the labels are the singletons."""
+    return _sym([0, 1], [1, 2], [1.0, 2.0 ** -32], 3), 2.0 * (1 + 2.0 ** -34)
+
+
+def start_partitions(graph, seed=0):
+    """name -> int32 labels (ids in [0, n)) to start `iteration` from; "converged" is added by the tests."""
+    n = graph.shape[0]
+    rng = np.random.default_rng(seed)
+    ids = rng.choice(n, max(n // 9, 2), replace=False)  # ids used sparsely over [0, n)
+    return {
+        "one": np.zeros(n, dtype=np.int32),
+        "gaps": ids[rng.integers(0, len(ids), n)].astype(np.int32),
+        "disconnected": (np.arange(n) % 6 * (n // 6)).astype(np.int32),  # every 6th vertex: spread over the graph
+    }
+
+
+def converged(graph, resolution, seed):
+    """Labels (not renumbered) after the iterations of leiden(graph, resolution, seed, -1), and how many ran."""
+    indptr, indices, w = quantise(graph)
+    gom = float(resolution) / float(sum(int(x) for x in w))
+    labels = np.arange(len(indptr) - 1, dtype=np.int64)
+    for it in range(MAX_ITERATIONS):
+        labels, _, _, moves, _ = iteration(indptr, indices, w, gom, seed, it, labels)
+        if moves == 0:
+            return labels.astype(np.int32), it + 1
+    raise AssertionError("not converged")
+
+
+# ---- rule 5: a seeded search for an input that reaches the round bound -------------------------------------------------
+def rule5_shapes():
+    """Graphs of up to 12 vertices, among them the symmetric shapes of rule 4c (non-adjacent vertices coupled through
+    K_c): complete bipartite graphs, stars, cycles, two hubs that share their leaves."""
+    def bipartite(a, b):
+        r, c = np.meshgrid(np.arange(a), a + np.arange(b), indexing="ij")
+        return _sym(r.ravel(), c.ravel(), np.ones(a * b), a + b)
+
+    out = {f"k{a}_{b}": bipartite(a, b) for a, b in ((2, 2), (2, 5), (2, 10), (3, 3), (3, 9), (4, 4), (4, 8), (6, 6))}
+    out.update({f"star{n}": star(n) for n in (3, 7, 11)})
+    out.update({f"cycle{n}": cycle(n) for n in (4, 6, 8, 12)})
+    out.update({"complete6": complete(6), "complete12": complete(12), "path12": path(12),
+                "cliques3x4": cliques([3] * 4, ring=True), "cliques4x3": cliques([4] * 3, ring=True)})
+    return out
+
+
+def rule5_search(budget, seed=0):
+    """`budget` cases (shape, optional random weights, starting partition, gamma in [0, 8], random_state, it) drawn from
+    default_rng(seed): (the cases that reached a bound, the most rounds of a phase minus that level's bound)."""
+    rng = np.random.default_rng(seed)
+    shapes = list(rule5_shapes().items())
+    gammas = (0.0, 0.25, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, 8.0)
+    found, closest = [], -10 ** 9
+    for case in range(budget):
+        name, g = shapes[rng.integers(len(shapes))]
+        n = g.shape[0]
+        if rng.integers(3) == 0:  # symmetric random weights 2^-k
+            u = sp.triu(g).tocoo()
+            g = _sym(u.row, u.col, 2.0 ** -rng.integers(0, 12, u.nnz).astype(np.float64), n)
+        kind = rng.integers(5)
+        labels = (np.arange(n), np.zeros(n, dtype=np.int64), np.arange(n) % 2, np.arange(n) // 2 * 2,
+                  rng.integers(0, n, n))[kind]
+        gamma, rs, it = gammas[rng.integers(len(gammas))], int(rng.integers(1 << 62)), int(rng.integers(64))
+        indptr, indices, w = quantise(g)
+        gom = gamma / float(sum(int(x) for x in w))
+        _, sizes, rnds, _, bound = iteration(indptr, indices, w, gom, rs, it, labels)
+        closest = max(closest, max(max(r) - max_rounds(s) for s, r in zip(sizes, rnds)))
+        if bound:
+            found.append((case, name, kind, gamma, rs, it))
+    return found, closest
