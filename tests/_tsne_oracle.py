@@ -38,6 +38,7 @@ import _umap_oracle as uo
 TAG_TSNE = uo.MASK - 2
 MAX_NEIGHBORS = 63
 LONG_ROW = 512  # rows above this many entries take a workgroup on the device (nothing changes in the numbers)
+TILE = 256  # positions per LDS tile of the device's repulsion (nothing changes in the numbers)
 
 _LOG2E = 1.4426950408889634
 _LN2_HI = float.fromhex("0x1.62e42fee00000p-1")
@@ -205,9 +206,31 @@ def schedule(t, early_exaggeration=12.0, exaggeration_iters=250):
     return (float(early_exaggeration), 0.5) if t < exaggeration_iters else (1.0, 0.8)
 
 
-def gradient(g, y, ex):
-    """g of rule 6 (float64 n x c)."""
-    Zr, R = repulsion(y)
+def repulsion_grouped(y):
+    """:func:`repulsion` for positions that take few distinct values: the m x m quantised terms of the distinct points
+    once, times the number of cells at each point (int64), minus rint(2^32) for the pair (i, i) (its R term is 0), and
+    scattered back to the cells.  The sums are integer sums, so the result equals ``repulsion(y)`` exactly."""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    pts, inv, cnt = np.unique(y, axis=0, return_inverse=True, return_counts=True)
+    inv, cnt = np.asarray(inv).reshape(-1), cnt.astype(np.int64)
+    c = y.shape[1]
+    one = np.float32(1.0)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        dx = [pts[:, k, None] - pts[None, :, k] for k in range(c)]
+        d2 = dx[0] * dx[0] + dx[1] * dx[1]
+        if c == 3:
+            d2 = d2 + dx[2] * dx[2]
+        q = one / (one + d2)
+        qq = q * q
+        assert qq.dtype == np.float32
+        Zr = _q32(q) @ cnt - (1 << 32)
+        R = np.stack([_q32(qq * dx[k]) @ cnt for k in range(c)], axis=1)
+    return Zr[inv], R[inv]
+
+
+def gradient(g, y, ex, repulse=repulsion):
+    """g of rule 6 (float64 n x c); `repulse`: :func:`repulsion` or :func:`repulsion_grouped`."""
+    Zr, R = repulse(y)
     Z = normaliser(Zr)
     A = attraction(g, y)
     rep = (R.astype(np.float64) * 2.0 ** -32) / Z if Z > 0 else np.zeros(R.shape)
@@ -268,3 +291,186 @@ def tsne(x, *, perplexity=30.0, n_components=2, max_iter=1000, init_pos="pca", r
     y0 = pca_init(x, n_components) if init_pos == "pca" else random_init(n, n_components, random_state)
     state = run(Graph(w), start(y0), 0, max_iter, early_exaggeration=early_exaggeration, learning_rate=learning_rate)
     return state[0], {"knn_indices": idx, "knn_distances": dist, "beta": beta, "cond": p, "W": w}
+
+
+# ---- the device's geometry and the inputs of the edge tests (tests/test_gpu_tsne_edges.py; test_tsne_oracle.py asserts
+# ---- on the CPU that each of them enters the branch it is for) -----------------------------------------------------------
+def repulse_geometry(n):
+    """(i_blocks, tiles, split, chunk, grid_y) of the device's repulsion grid: icv_tsne_iterations' integer arithmetic.
+    A workgroup (bx, by) owns the cells [256 bx, +256) and streams the positions [chunk by, +chunk) in tiles of TILE."""
+    i_blocks = (n + 255) // 256
+    split = (2048 + i_blocks - 1) // i_blocks
+    tiles = (n + TILE - 1) // TILE
+    split = min(max(1, min(split, tiles)), 65535)
+    chunk = (tiles + split - 1) // split * TILE
+    return i_blocks, tiles, split, chunk, (n + chunk - 1) // chunk
+
+
+def affinities_steps(knn_dist, perplexity):
+    """The evaluation of the doubling / halving phase of rule 2 at which each row has seen both sides: 0 .. 63, -1 for a
+    row that never does (beta stays 2^63 or 2^-63), -2 for a row of equal distances."""
+    d = np.asarray(knn_dist, dtype=np.float32).astype(np.float64)
+    rel = d * d - (d * d)[:, :1]
+    target = math.log(float(perplexity))
+    n = len(d)
+    steps = np.where(rel[:, -1] == 0.0, -2, -1)
+    seen_up, seen_down, beta = np.zeros(n, bool), np.zeros(n, bool), np.ones(n)
+    for step in range(64):
+        up = _above(rel, beta, target)
+        seen_up |= up
+        seen_down |= ~up
+        steps = np.where((steps == -1) & seen_up & seen_down, step, steps)
+        beta = np.where(up, beta * 2.0, beta / 2.0)
+    return steps
+
+
+TILE_SIZES = (11520, 11521, 16385)  # chunk 256 (the largest such n) / 512 / 768, the last two with a 257-cell last chunk
+TILE_VARIANTS = ("drawn", "lonely_last", "second_tile")
+
+
+def tile_positions(n, c, variant, seed=0):
+    """n cells drawn from 100 distinct float32 points, so that every tile holds other counts and the grouped oracle
+    applies.  "lonely_last": cell n - 1 alone at a point of its own (dropping the last tile changes Z); "second_tile":
+    the cells 256 .. 511 sit on cell 0."""
+    rng = np.random.default_rng([seed, n, c])
+    pts = rng.normal(size=(101, c)).astype(np.float32)
+    y = pts[rng.integers(0, 100, n)]
+    if variant == "lonely_last":
+        y[n - 1] = pts[100]
+    elif variant == "second_tile":
+        y[TILE:2 * TILE] = y[0]
+    else:
+        assert variant == "drawn"
+    return np.ascontiguousarray(y)
+
+
+def ring_graph(n, offsets=(1, 7, 300, 5000), seed=0):
+    """Symmetric, 2 len(offsets) entries per row: i -- (i + o) mod n with seeded float32 weights in (0, 2]."""
+    rng = np.random.default_rng([seed, n])
+    i = np.arange(n, dtype=np.int64)
+    rows = np.concatenate([i for _ in offsets])
+    cols = np.concatenate([(i + o) % n for o in offsets])
+    w = (np.float32(2.0) * (np.float32(1.0) - rng.random(len(rows), dtype=np.float32))).astype(np.float64)
+    g = sp.coo_matrix((np.r_[w, w], (np.r_[rows, cols], np.r_[cols, rows])), shape=(n, n)).tocsr()
+    g.sort_indices()
+    assert g.nnz == 2 * len(rows) and g.data.max() <= 2.0 and g.data.min() > 0.0
+    return g
+
+
+GAINS = (0.01, 0.012, 0.0125, 1.0, 1e3)  # 0.8 times the first two is below the floor, 0.8 times the third is at it
+UPDATES = (0.0, -0.0, 1e-30, -1e-30, 1.0, -1.0, 1e6, -1e6)
+
+
+def crafted_state(y, scale=None):
+    """(y, u, gain) with every pair of GAINS x UPDATES (coordinate k takes GAINS[k mod 5] and UPDATES[k mod 8]);
+    `scale` multiplies the updates (the tile tests use small ones so that the positions stay where they are)."""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    k = np.arange(y.size)
+    u = np.asarray(UPDATES, dtype=np.float32)[k % 8].reshape(y.shape)
+    if scale is not None:
+        u = u * np.float32(scale)
+    return y, u, np.asarray(GAINS, dtype=np.float32)[k % 5].reshape(y.shape)
+
+
+ROW_GRAPHS = {"star511": 0, "star512": 0, "star513": 1, "star768": 1, "two_centres": 2, "last_vertex": 1}  # long rows
+
+
+def row_graph(name, seed=0):
+    """Graphs whose longest rows sit at LONG_ROW: stars with a centre row of 511 / 512 / 513 / 768 entries, two centres
+    of 513 and 600 entries, and a 600-entry row that is the last vertex.  One stored weight is exactly 2, one a
+    float32 subnormal and one a stored 0 (all three in a centre row and in a leaf's)."""
+    if name.startswith("star"):
+        m = int(name[4:])
+        rows, cols, n = np.zeros(m, dtype=np.int64), np.arange(1, m + 1), m + 1
+    elif name == "two_centres":  # row 0: 1 .. 513; row 1: 0 and 2 .. 600
+        rows = np.r_[np.zeros(513, dtype=np.int64), np.ones(599, dtype=np.int64)]
+        cols, n = np.r_[np.arange(1, 514), np.arange(2, 601)], 601
+    else:
+        assert name == "last_vertex"
+        rows, cols, n = np.full(600, 600, dtype=np.int64), np.arange(600), 601
+    rng = np.random.default_rng([seed, len(rows)])
+    w = rng.random(len(rows)) + 0.01
+    w = (w * (2.0 / w.max())).astype(np.float32)
+    pick = rng.choice(np.flatnonzero(w < 2.0), 2, replace=False)
+    w[pick[0]], w[pick[1]] = np.float32(1e-40), 0.0
+    w = w.astype(np.float64)
+    g = sp.coo_matrix((np.r_[w, w], (np.r_[rows, cols], np.r_[cols, rows])), shape=(n, n)).tocsr()
+    g.sort_indices()
+    return g
+
+
+AFFINITY_KK = (1, 2, 15, 63)
+AFFINITY_N = (1, 255, 256, 257, 1000)
+AFFINITY_EXPONENTS = tuple(range(-62, 63, 4))
+AFFINITY_KINDS = ("scaled", "flat", "d0_positive", "scaled", "nine_zeros", "underflow")
+
+
+def affinity_base(kk):
+    """Sorted, d_0 = 0: rel_r = r / 4.  At kk = 15 beta is 2.1965 (perplexity 5) and 0.010691 (perplexity 14.999)."""
+    return (np.sqrt(np.arange(kk)) * 0.5).astype(np.float32)
+
+
+def affinity_scaled(kk):
+    """(rows, e): the base row times 2^e for every e of AFFINITY_EXPONENTS (exact in float32 and in every product of
+    rule 2, so beta shifts by exactly 2^-2e while the doubling / halving brackets it)."""
+    e = np.asarray(AFFINITY_EXPONENTS)
+    return np.ldexp(affinity_base(kk)[None, :], e[:, None]).astype(np.float32), e
+
+
+def affinity_perplexities(kk):
+    return tuple(p for p in (5.0, kk - 1e-3) if p < kk)
+
+
+def affinity_rows(kk, n):
+    """(distances n x kk float32, kind of each row): the kinds of AFFINITY_KINDS interleaved so that every wavefront
+    holds all of them; the scaled rows alternate between the two ends of AFFINITY_EXPONENTS and walk inwards."""
+    scaled, _ = affinity_scaled(kk)
+    m = len(scaled)
+    order = [j // 2 if j % 2 == 0 else m - 1 - j // 2 for j in range(m)]
+    base = affinity_base(kk)
+    d = np.zeros((n, kk), dtype=np.float32)
+    kinds = []
+    s = 0
+    for r in range(n):
+        kind = AFFINITY_KINDS[r % len(AFFINITY_KINDS)]
+        kinds.append(kind)
+        if kind == "scaled":
+            d[r] = scaled[order[s % m]]
+            s += 1
+        elif kind == "flat":  # 0, 3, 1e-30 (the square underflows in float32, not in float64), 1e30
+            d[r] = (0.0, 3.0, 1e-30, 1e30)[(r // 6) % 4]
+        elif kind == "d0_positive":
+            d[r] = np.float32(0.75) + base * np.float32(1 + (r // 6) % 5)
+        elif kind == "nine_zeros":
+            d[r, 9:] = base[:max(kk - 9, 0)] + np.float32(0.25)
+        else:  # up to 7 neighbours near 1, the others from 40 on: beta (rel_r) > 708 for them at perplexity 5
+            d[r] = np.float32(1.0) + base * np.float32(0.125)
+            d[r, 7:] = np.float32(40.0) + base[:max(kk - 7, 0)]
+            d[r, 0] = 0.0
+    assert (np.diff(d, axis=1) >= 0).all()
+    return d, np.asarray(kinds)
+
+
+UPDATE_CASES = ("crossed", "zero_gradient", "far_line", "huge")
+
+
+def update_case(name, c, n=300, seed=0):
+    """(graph, state, what the CPU test asserts about it) for rule 6:
+    "crossed": GAINS x UPDATES x both signs of the gradient on a ring graph, positions N(0, 1);
+    "zero_gradient": no stored entry and coincident positions: g = 0 exactly while u != 0;
+    "far_line": cells 1e6 apart on a line: every q < 2^-33, so Z = 0 with n > 1;
+    "huge": positions 2^19 N(0, 1): d2 reaches 1e11 and most terms quantise to 0 or +-1."""
+    rng = np.random.default_rng([seed, c, n])
+    g = ring_graph(n, offsets=(1, 7, 30), seed=seed)
+    if name == "crossed":
+        y = rng.normal(size=(n, c)).astype(np.float32)
+    elif name == "zero_gradient":
+        g = sp.csr_matrix((n, n), dtype=np.float64)
+        y = np.zeros((n, c), dtype=np.float32) + rng.normal(size=c).astype(np.float32)
+    elif name == "far_line":
+        y = np.zeros((n, c), dtype=np.float32)
+        y[:, 0] = np.arange(n) * 1e6
+    else:
+        assert name == "huge"
+        y = (rng.normal(size=(n, c)) * 2.0 ** 19).astype(np.float32)
+    return g, crafted_state(y)

@@ -288,3 +288,186 @@ def test_argument_checks_need_no_gpu():
         rc = lib.icv_tsne_iterations(one, one, one, a["n"], 4, a["c"], a["ex"], a["exi"], a["eta"], a["t0"], a["t1"], one,
                                      one, one, one, None, None)
         assert rc == _lib.ICV_ERR_INVALID and b"tsne_iterations" in lib.icv_last_error()
+
+
+# ---- the geometry of the device's grid and the inputs of tests/test_gpu_tsne_edges.py ------------------------------------
+@pytest.mark.parametrize("c", (2, 3))
+def test_grouped_repulsion_equals_the_full_one(c):
+    rng = np.random.default_rng(c)
+    pts = rng.normal(size=(97, c)).astype(np.float32)
+    pts[0] = 0.0
+    pts[1, 0] = -0.0  # a negative zero is its own bit pattern and the same position
+    y = pts[rng.integers(0, 97, 2000)]
+    Zr, R = to.repulsion(y)
+    Zg, Rg = to.repulsion_grouped(y)
+    assert Zg.dtype == np.int64 and Rg.dtype == np.int64 and np.array_equal(Zg, Zr) and np.array_equal(Rg, R)
+    assert len(np.unique(y, axis=0)) == 97 and R.any()
+    og = to.Graph(to.ring_graph(2000, offsets=(1, 7, 300)))
+    assert to.gradient(og, y, 12.0, repulse=to.repulsion_grouped).tobytes() == to.gradient(og, y, 12.0).tobytes()
+    lone = np.float32([[0.5, -1.0, 2.0][:c]])  # n = 1: no pair at all
+    assert to.repulsion_grouped(lone)[0].tolist() == [0] and not to.repulsion_grouped(lone)[1].any()
+
+
+def test_repulse_geometry():
+    geom = to.repulse_geometry
+    assert geom(11520) == (45, 45, 45, 256, 45)  # the largest n of one tile per workgroup
+    assert geom(11521) == (46, 46, 45, 512, 23) and 11521 - 22 * 512 == 257
+    assert geom(16385) == (65, 65, 32, 768, 22) and 16385 - 21 * 768 == 257
+    assert geom(257) == (2, 2, 2, 256, 2)
+    for n in (1, 2, 255, 256):
+        assert geom(n) == (1, 1, 1, 256, 1)
+    assert all(geom(n)[3] == 256 for n in (257, 2000, 5000, 11520)) and geom(20000)[3] == 1024
+    for n in (1, 300, 11521, 16385, 20000, 10 ** 6, 1 << 30):  # the grid covers every position once, in whole tiles
+        i_blocks, tiles, split, chunk, grid_y = geom(n)
+        assert chunk % to.TILE == 0 and (grid_y - 1) * chunk < n <= grid_y * chunk and grid_y <= split <= 65535
+    assert to.TILE_SIZES == (11520, 11521, 16385)
+
+
+@pytest.mark.parametrize("c", (2, 3))
+def test_tile_inputs_enter_their_branches(c):
+    for n in to.TILE_SIZES:
+        chunk = to.repulse_geometry(n)[3]
+        tile_of = np.arange(n) // to.TILE
+        y = {v: to.tile_positions(n, c, v) for v in to.TILE_VARIANTS}
+        pts, inv = np.unique(y["drawn"], axis=0, return_inverse=True)
+        assert len(pts) == 100
+        counts = np.zeros((tile_of.max() + 1, 100), dtype=np.int64)
+        np.add.at(counts, (tile_of, np.asarray(inv).reshape(-1)), 1)
+        assert len(np.unique(counts, axis=0)) == len(counts)  # no two tiles hold the same counts
+        last = y["lonely_last"]
+        assert not (last[:-1] == last[-1]).all(axis=1).any() and np.array_equal(last[:-1], y["drawn"][:-1])
+        if n % to.TILE == 1:
+            assert tile_of[-1] != tile_of[-2] and (n - 1) % chunk == to.TILE  # the one cell of the last, partial tile
+        # dropping that cell changes every other Zr
+        assert (to.repulsion_grouped(last)[0][:-1] != to.repulsion_grouped(last[:-1])[0]).all()
+        second = y["second_tile"]
+        assert (second[256:512] == second[0]).all() and (chunk == 256 or 512 <= chunk)
+        assert to.repulsion_grouped(second)[0][0] >= 256 << 32
+        g = to.ring_graph(n)
+        assert (np.diff(g.indptr) == 8).all() and (g != g.T).nnz == 0
+        state = to.crafted_state(y["drawn"], scale=2.0 ** -10)
+        assert len(np.unique(state[1].view(np.uint32))) == 8 and len(np.unique(state[2])) == 5
+
+
+def test_row_graphs_sit_at_the_long_row_threshold():
+    longest = {"star511": 511, "star512": 512, "star513": 513, "star768": 768, "two_centres": 600, "last_vertex": 600}
+    for name, n_long in to.ROW_GRAPHS.items():
+        g = to.row_graph(name)
+        og = to.Graph(g)
+        lengths = np.diff(og.indptr)
+        assert lengths.max() == longest[name] and int((lengths > to.LONG_ROW).sum()) == n_long, name
+        assert (g != g.T).nnz == 0 and g.has_sorted_indices
+        w32 = g.data.astype(np.float32)
+        tiny = np.finfo(np.float32).tiny
+        assert w32.max() == 2.0 and (w32 == 2.0).sum() == 2 and (w32 == 0.0).sum() == 2  # each value and its mirror
+        assert ((w32 > 0) & (w32 < tiny)).sum() == 2 and len(og.w) == g.nnz  # the stored 0 stays stored
+        if name == "two_centres":
+            assert sorted(lengths[lengths > to.LONG_ROW].tolist()) == [513, 600]
+        if name == "last_vertex":
+            assert lengths[-1] == 600 and lengths[:-1].max() == 1
+    assert 768 % 256 == 0 and 768 % 512 != 0 and 600 % 256 != 0  # a long row's last round of 256 lanes is partial at 513, 600
+
+
+def test_affinity_rows_enter_their_branches():
+    """What the hand-built distances do in the oracle (kk = 15 carries the properties; the other kk the kinds)."""
+    rows, e = to.affinity_scaled(15)
+    assert e[0] == -62 and e[-1] == 62 and (np.diff(e) == 4).all() and (rows[:, 0] == 0).all()
+    base = to.affinity_base(15)[None, :]
+    assert np.array_equal(rows[e == 2], base * np.float32(4)) and 0 not in e
+    for perplexity, last_up, first_down in ((5.0, -34, 34), (14.999, -38, 30)):
+        beta, p = to.affinities(rows, perplexity)
+        steps = to.affinities_steps(rows, perplexity)
+        assert np.isfinite(p).all() and np.isfinite(beta).all()
+        up, down = e <= last_up, e >= first_down
+        assert (beta[up] == 2.0 ** 63).all() and (beta[down] == 2.0 ** -63).all()
+        assert (steps[up | down] == -1).all() and (steps[~(up | down)] >= 0).all()
+        mid = np.flatnonzero(~(up | down))
+        b0, p0 = (a[0] for a in to.affinities(base, perplexity))
+        assert np.array_equal(beta[mid], np.ldexp(b0, -2 * e[mid]))  # the shift is exact
+        assert all(p[i].tobytes() == p0.tobytes() for i in mid)
+        # the small end: every beta rel_r <= x = 2^63 2^2e 14 / 4, so e_r lies in [1 - x, 1] and p_r 15 within x of 1:
+        # to rounding at e = -62 (x = 2^-59)
+        x = np.ldexp(3.5, 63 + 2 * e[up])
+        assert (np.abs(p[up] * 15 - 1).max(axis=1) <= x + 2.0 ** -50).all() and x[0] < 2.0 ** -59
+        # the large end: beta rel_r >= x = 2^(2e - 63) / 4 for r >= 1, so p_0 >= 1 / (1 + 14 exp(-x)): x = 8 at e = 34
+        x = np.ldexp(0.25, 2 * e[down] - 63)
+        assert (p[down][:, 0] >= 1 / (1 + 14 * np.exp(-x)) - 1e-15).all() and (p[e >= 34][:, 0] > 0.995).all()
+        big = e >= 40
+        assert np.array_equal(p[big], np.eye(1, 15).repeat(big.sum(), axis=0))  # beta rel_1 >= 2^15: (1, 0, ...)
+        if perplexity == 5.0:
+            assert 2.0 < b0 < 4.0 and steps[e == -30][0] == 62  # bracketed only at beta = 2^62
+    assert round(float(to.affinities(base, 14.999)[0][0]), 6) == 0.010691
+
+    for kk in to.AFFINITY_KK:
+        d, kinds = to.affinity_rows(kk, to.AFFINITY_N[-1])
+        assert d.dtype == np.float32 and all(set(kinds[w:w + 64]) == set(to.AFFINITY_KINDS) for w in range(0, 960, 64))
+        assert to.affinity_rows(kk, 257)[0].tobytes() == d[:257].tobytes()
+        assert to.affinity_perplexities(kk) == {1: (0.999,), 2: (1.999,), 15: (5.0, 14.999), 63: (5.0, 62.999)}[kk]
+        rel = d.astype(np.float64) ** 2
+        rel -= rel[:, :1]
+        for perplexity in to.affinity_perplexities(kk):
+            beta, p = to.affinities(d, perplexity)
+            steps = to.affinities_steps(d, perplexity)
+            assert np.isfinite(p).all() and np.isfinite(beta).all() and (p >= 0).all()
+            assert (steps[kinds == "flat"] == -2).all()
+            if kk == 1:
+                assert (steps == -2).all() and (beta == 1).all() and (p == 1).all()
+                continue
+            for w in range(0, 960, 64):  # a wavefront: flat rows, rows never bracketed at either end, late ones
+                s, b = steps[w:w + 64], beta[w:w + 64]
+                assert (s == -2).any() and (b == 2.0 ** 63).any() and (b == 2.0 ** -63).any() and (s >= 30).any()
+            assert (steps >= 60).any() and (d[kinds == "d0_positive"][:, 0] > 0).all()
+            assert (steps[kinds == "d0_positive"] >= 0).all()
+            if kk >= 15:
+                nine = kinds == "nine_zeros"
+                assert (d[nine][:, :9] == 0).all() and (d[nine][:, 9] > 0).all()
+                if perplexity == 5.0:  # nine neighbours tie at 0: the entropy never falls below log 9
+                    assert (beta[nine] == 2.0 ** 63).all() and (p[nine][:, :9] == 1 / 9).all()
+                    under = kinds == "underflow"
+                    assert ((beta[:, None] * rel)[under][:, 7:] > 708).all() and (p[under][:, 7:] == 0).all()
+                    assert (steps[under] >= 0).all()
+
+
+@pytest.mark.parametrize("c", (2, 3))
+def test_update_cases_enter_their_branches(c):
+    floor = np.float32(0.01)
+    g, state = to.update_case("crossed", c)
+    og = to.Graph(g)
+    y, u, gain = state
+    assert y.shape == (300, c)
+    for t in (249, 250, 251):
+        gr = to.gradient(og, y, to.schedule(t)[0])
+        combos = {(float(a), float(b).hex(), bool(s)) for a, b, s in zip(gain.ravel(), u.ravel(), (gr < 0).ravel())}
+        assert len(combos) == 5 * 8 * 2 and (gr != 0).all()  # every gain x update x sign of the gradient
+        new = to.iteration(og, *state, t)
+        raw = np.where(u.astype(np.float64) * gr < 0, gain.astype(np.float64) + 0.2, gain.astype(np.float64) * 0.8)
+        assert (raw < 0.01).any() and (new[2][raw < 0.01] == floor).all() and (new[2] >= floor).all()
+        assert float(np.float32(0.0125)) * 0.8 >= 0.01 > float(np.float32(0.012)) * 0.8  # on either side of the floor
+        zero = (u.astype(np.float64) * gr == 0)
+        k = np.arange(y.size) % 8
+        assert np.array_equal(zero, u == 0) and zero.sum() == (k < 2).sum() and np.signbit(u[zero]).sum() == (k == 1).sum()
+        assert all(np.isfinite(a).all() for a in new)
+
+    g, state = to.update_case("zero_gradient", c)
+    og = to.Graph(g)
+    assert g.nnz == 0 and not to.gradient(og, state[0], 12.0).any() and (state[1] != 0).any()
+    new = to.iteration(og, *state, 0)
+    assert new[1].tobytes() == (state[1] * np.float32(0.5)).tobytes() and np.signbit(new[1]).sum() == state[1].size // 2
+    assert np.array_equal(new[2], np.maximum((state[2].astype(np.float64) * 0.8).astype(np.float32), floor))
+
+    one = (sp.csr_matrix((1, 1)), to.crafted_state(np.ones((1, c), dtype=np.float32)))
+    for g, state in (one, to.update_case("far_line", c)):
+        Zr, R = to.repulsion(state[0])
+        assert to.normaliser(Zr) == 0.0 and not Zr.any() and not R.any()
+        gr = to.gradient(to.Graph(g), state[0], 12.0)
+        assert np.isfinite(gr).all() and (gr.any() or g.nnz == 0)
+    d = np.diff(to.update_case("far_line", c)[1][0][:, 0].astype(np.float64))
+    assert (1.0 / (1.0 + d.min() ** 2) < 2.0 ** -33) and len(d) == 299
+
+    g, state = to.update_case("huge", c)
+    Zr, R, _ = to.repulsion(state[0], return_abs=True)
+    y64 = state[0].astype(np.float64)
+    d2 = ((y64[:, None, :] - y64[None, :, :]) ** 2).sum(axis=2)
+    assert d2.max() >= 1e11 * c and to.normaliser(Zr) > 0
+    terms = np.rint(4294967296.0 / (1.0 + d2[~np.eye(300, dtype=bool)]))
+    assert (terms <= 1).mean() > 0.5 and (terms == 0).any() and (terms == 1).any()
