@@ -109,10 +109,13 @@ def _quantise(v):
     return np.rint(v * 4294967296.0).astype(np.int64)
 
 
-def contributions(g, y, t, *, n_epochs, a, b, gamma=1.0, negative_sample_rate=5, seed=0):
-    """(rows, q): the int64 contributions (m x c) of epoch t and the row each one goes to; 1 + r per active entry."""
+def contributions(g, y, t, *, n_epochs, a, b, gamma=1.0, negative_sample_rate=5, seed=0, drop=None):
+    """(rows, q): the int64 contributions (m x c) of epoch t and the row each one goes to; 1 + r per active entry.
+    `drop`: entries treated as inactive (what a kernel that loses them would compute; the others keep their samples)."""
     r = int(negative_sample_rate)
     e = g.active(t, n_epochs)
+    if drop is not None:
+        e = e[~np.isin(e, drop)]
     i = g.rows[e]
     y64 = y.astype(np.float64)
     c = y.shape[1]
@@ -132,11 +135,12 @@ def contributions(g, y, t, *, n_epochs, a, b, gamma=1.0, negative_sample_rate=5,
     return np.concatenate(rows), np.concatenate(qs).reshape(-1, c)
 
 
-def epoch(g, y, t, *, n_epochs, a, b, gamma=1.0, negative_sample_rate=5, initial_alpha=1.0, seed=0, order=None):
+def epoch(g, y, t, *, n_epochs, a, b, gamma=1.0, negative_sample_rate=5, initial_alpha=1.0, seed=0, order=None,
+          drop=None):
     """(y_new, m): one epoch from the snapshot y (float32 n x c); m[i] = contributions of row i.  `order`: a
-    permutation of the contributions (the sum does not depend on it)."""
+    permutation of the contributions (the sum does not depend on it); `drop`: see :func:`contributions`."""
     rows, q = contributions(g, y, t, n_epochs=n_epochs, a=a, b=b, gamma=gamma,
-                            negative_sample_rate=negative_sample_rate, seed=seed)
+                            negative_sample_rate=negative_sample_rate, seed=seed, drop=drop)
     if order is not None:
         rows, q = rows[order], q[order]
     S = np.zeros(y.shape, dtype=np.int64)
@@ -157,6 +161,103 @@ def run(g, y, epoch_begin, epoch_end, keep=(), **kw):
             snaps[t] = y
         y, _ = epoch(g, y, t, **kw)
     return (y, snaps) if keep else y
+
+
+def tolerance(ref, m):
+    """The bound of a one-epoch comparison with :func:`epoch`'s (ref, m).  Derived, not measured: pow may differ in its
+    last bit, which moves a contribution to the neighbouring multiple of 2^-32 (m_i contributions, alpha <= 1), and
+    then the final float32 rounding may fall to the other side."""
+    return np.spacing(np.abs(ref)).astype(np.float64) + m[:, None] * 2.0 ** -32
+
+
+def negatives(g, y, t, *, n_epochs, negative_sample_rate=5, seed=0):
+    """(i, k, d2) of every negative sample of epoch t (rule 4): the row, the sampled vertex and their squared distance."""
+    r = int(negative_sample_rate)
+    e = g.active(t, n_epochs)
+    c = (e.astype(np.uint64)[:, None] * np.uint64(r) + np.arange(r, dtype=np.uint64)[None, :]).ravel()
+    h = counter_hash(seed, t, c)
+    k = (((h >> np.uint64(32)) * np.uint64(g.n)) >> np.uint64(32)).astype(np.int64)
+    i = np.repeat(g.rows[e], r)
+    return i, k, _pair(y.astype(np.float64), i, k, 1.0)[1]
+
+
+# ---- edge builders (tests/test_gpu_umap_edges.py; test_umap_oracle.py asserts that the oracle reaches each branch) -----
+CHUNK = 64      # entries a wavefront tests per ballot
+LDS_ROW = 512   # longest row a wavefront compacts; longer rows take a workgroup
+HUBS = (63, 64, 65, 127, 128, 129, 191, 192, 193, 511, 512, 513, 514, 1025)
+
+
+def _sym(rows, cols, vals, n):
+    """Symmetric CSR of the edges (rows, cols) with float32 values; stored zeros (of either sign) are kept."""
+    rows, cols, vals = np.asarray(rows), np.asarray(cols), np.asarray(vals, dtype=np.float32)
+    r, c, v = np.concatenate([rows, cols]), np.concatenate([cols, rows]), np.concatenate([vals, vals])
+    order = np.lexsort((c, r))
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=n))])
+    return sp.csr_matrix((v[order], c[order].astype(np.int32), indptr.astype(np.int64)), shape=(n, n))
+
+
+def hubs_mixed(hubs=HUBS, leaves=1030, seed=0):
+    """A path of weight 1 over `leaves` vertices plus one hub per entry d of `hubs`, joined to the leaves 0 .. d - 1 by
+    weights j / 64, j uniform in [0, 64] (float32-exact; the zeros are stored).  Hub h is vertex leaves + h, so its row
+    has d entries in ascending leaf order: rows on both sides of every multiple of 64 and of the 512-entry split, whose
+    64-entry chunks mix active and inactive entries in most epochs."""
+    rng = np.random.default_rng(seed)
+    r, c, v = [np.arange(leaves - 1)], [np.arange(1, leaves)], [np.ones(leaves - 1)]
+    for h, d in enumerate(hubs):
+        r.append(np.arange(d))
+        c.append(np.full(d, leaves + h))
+        v.append(rng.integers(0, 65, d) / 64.0)
+    return _sym(np.concatenate(r), np.concatenate(c), np.concatenate(v), leaves + len(hubs))
+
+
+def hub_rows(g, leaves=1030):
+    """The hub vertices of :func:`hubs_mixed` (every vertex from `leaves` on)."""
+    return np.arange(leaves, g.shape[0])
+
+
+def split_mixed(seed=1):
+    """The pattern of ``_leiden_oracle.rows_at_split()``: cliques of 513, 514 and 512 vertices joined in a ring, rows of
+    511 .. 514 entries (hundreds of long rows next to hundreds of short ones), with symmetric weights j / 8, j uniform
+    in [0, 8]."""
+    import _leiden_oracle as lo
+
+    g = sp.coo_matrix(lo.rows_at_split())
+    up = g.row < g.col
+    rng = np.random.default_rng(seed)
+    return _sym(g.row[up], g.col[up], rng.integers(0, 9, int(up.sum())) / 8.0, g.shape[0])
+
+
+def threshold_values(n_epochs):
+    """name -> float32 weight around the limits of rule 2 when w_max = 1."""
+    thr = np.float32(1.0 / n_epochs)
+    return {"one": np.float32(1.0), "at": thr, "above": np.nextafter(thr, np.float32(2.0)),
+            "below": np.nextafter(thr, np.float32(0.0)), "zero": np.float32(0.0), "minus_zero": np.float32(-0.0),
+            "third": np.float32(1.0 / 3.0), "subnormal": np.nextafter(np.float32(0.0), np.float32(1.0))}
+
+
+def threshold_weights(n_epochs):
+    """A star whose leaf 1 + q carries the q-th weight of :func:`threshold_values`, followed by a path of weight 1 / 3
+    over four more vertices hanging off the last leaf (rows that mix a firing and a non-firing entry)."""
+    w = np.array(list(threshold_values(n_epochs).values()), dtype=np.float32)
+    k = len(w)
+    r = np.concatenate([np.zeros(k, dtype=np.int64), np.arange(k, k + 4)])
+    c = np.concatenate([np.arange(1, k + 1), np.arange(k + 1, k + 5)])
+    return _sym(r, c, np.concatenate([w, np.full(4, np.float32(1.0 / 3.0))]), k + 5)
+
+
+def zero_weights(n=21):
+    """A path whose stored weights are all zero, of both signs: w_max = 0."""
+    return _sym(np.arange(n - 1), np.arange(1, n), np.where(np.arange(n - 1) % 2, -0.0, 0.0), n)
+
+
+def chunk_counts(g, v, t, n_epochs):
+    """Active entries per 64-entry chunk of row v in epoch t, and the entries per chunk."""
+    b, e = int(g.indptr[v]), int(g.indptr[v + 1])
+    act = np.zeros(e - b, dtype=np.int64)
+    a = g.active(t, n_epochs)
+    act[a[(a >= b) & (a < e)] - b] = 1
+    edges = np.arange(0, e - b, CHUNK)
+    return np.add.reduceat(act, edges), np.diff(np.r_[edges, e - b])
 
 
 # ---- the quality measure ----------------------------------------------------------------------------------------------

@@ -13,6 +13,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "gol
 import _leiden_oracle as lo  # noqa: E402
 import _neighbors_oracle as no  # noqa: E402
 import _umap_oracle as uo  # noqa: E402
+from _umap_checks import check_epoch as _check_epoch  # noqa: E402
+from _umap_checks import coincident as _coincident  # noqa: E402
+from _umap_checks import device as _device  # noqa: E402
+from _umap_checks import gpu_epochs as _gpu_epochs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 A, B = uo.A_DEFAULT, uo.B_DEFAULT
@@ -53,24 +57,6 @@ def _graph(name):
     return _cache[name]
 
 
-def _device(g):
-    import torch
-
-    g = sp.csr_matrix(g)
-    return (torch.from_numpy(g.indptr.astype(np.int64)).cuda(), torch.from_numpy(g.indices.astype(np.int32)).cuda(),
-            torch.from_numpy(g.data.astype(np.float32)).cuda())
-
-
-def _gpu_epochs(dev, y, t0, t1, n_epochs, seed, **kw):
-    import torch
-
-    from infercnvpy_amd import _engine
-
-    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).cuda()
-    _engine.umap_epochs(*dev, yd, a=A, b=B, n_epochs=n_epochs, epoch_begin=t0, epoch_end=t1, random_state=seed, **kw)
-    return yd.cpu().numpy()
-
-
 def _activations(og, t, n_epochs):
     e = np.flatnonzero(og.fires(n_epochs))
     return int(np.floor((t - 1) / (og.w_max / og.w[e])).sum()) if t > 1 and len(e) else 0
@@ -87,31 +73,6 @@ def _snapshots(name, dev, n_epochs, c, seed, epochs):
         if t not in snaps:
             snaps[t] = _gpu_epochs(dev, y0, 0, t, n_epochs, seed)
     return snaps
-
-
-def _check_epoch(og, dev, y, t, n_epochs, seed, what):
-    ref, m = uo.epoch(og, y, t, n_epochs=n_epochs, a=A, b=B, seed=seed)
-    got = _gpu_epochs(dev, y, t, t + 1, n_epochs, seed)
-    if t == 0:
-        assert got.tobytes() == y.tobytes(), what
-        return
-    # derived, not measured: pow may differ in its last bit, which moves a contribution to the neighbouring multiple
-    # of 2^-32 (m_i contributions, alpha <= 1), and then the final float32 rounding may fall to the other side
-    tol = np.spacing(np.abs(ref)).astype(np.float64) + m[:, None] * 2.0 ** -32
-    err = np.abs(got.astype(np.float64) - ref.astype(np.float64))
-    assert np.isfinite(got).all(), what
-    assert (err <= tol).all(), (what, float((err - tol).max()), int((err > tol).sum()))
-    assert np.array_equal(got[m == 0], y[m == 0]), what
-
-
-def _coincident(og, y):
-    """Both ends of some entries (and hence the rows of those entries) at the same point: d2 == 0."""
-    y = y.copy()
-    if len(og.w):
-        e = np.arange(0, len(og.w), max(len(og.w) // 50, 1))
-        y[og.indices[e]] = y[og.rows[e]]
-    y[-1] = y[0]
-    return y
 
 
 NAMES = tuple(lo.small_graphs()) + ("mix2000", "isolated_vertex", "mix2000_hub", "n7")

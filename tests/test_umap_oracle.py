@@ -213,3 +213,197 @@ def test_workspace_bytes_are_linear_and_validated():
         assert need(*bad)[0] == _lib.ICV_ERR_INVALID
         assert b"umap_workspace" in lib.icv_last_error()
     assert lib.icv_umap_workspace(5, 0, 2, None) == _lib.ICV_ERR_INVALID
+
+
+# ---- the edge builders: the oracle alone reaches every branch that tests/test_gpu_umap_edges.py relies on -------------
+N30 = 30
+EDGE_EPOCHS = (1, 2, 7, 15, 29)
+SETTINGS = ((2, 0), (3, 1))  # (n_components, random_state), as in the GPU tests
+
+
+@pytest.fixture(scope="module", params=(1030, 1031))
+def hubs(request):
+    g = uo.hubs_mixed(leaves=request.param)
+    return g, uo.Graph(g), uo.hub_rows(g, request.param)
+
+
+@pytest.fixture(scope="module")
+def split():
+    g = uo.split_mixed()
+    return g, uo.Graph(g)
+
+
+def test_hubs_mixed_is_what_it_says(hubs):
+    g, og, rows = hubs
+    leaves = rows[0]
+    assert og.n == leaves + 14 and len(og.w) == 10_512 + 2 * (leaves - 1030) and og.n % 4 == leaves - 1030
+    assert tuple(np.diff(og.indptr)[rows]) == uo.HUBS and og.w_max == 1.0
+    assert (g != g.T).nnz == 0 and np.array_equal(og.w * 64, np.rint(og.w * 64))
+    assert 50 < (og.w == 0).sum() < 300  # the zeros are stored
+    for v in rows:
+        assert np.array_equal(og.indices[og.indptr[v]:og.indptr[v + 1]], np.arange(np.diff(og.indptr)[v]))
+
+
+def test_hub_chunks_mix_active_and_inactive_entries(hubs):
+    _, og, rows = hubs
+    short = [v for v in rows if np.diff(og.indptr)[v] <= uo.LDS_ROW]
+    assert len(short) == 11
+    single_seen = set()
+    for t in (2, 7, 15, 29):
+        for v in short:
+            na, size = uo.chunk_counts(og, v, t, N30)
+            assert ((na > 0) & (na < size))[size >= 2].all(), (t, v, na)  # a chunk of one entry cannot mix
+            if size[-1] == 1 and na[-1] == 1 and na[:-1].sum() % uo.CHUNK != 0:
+                single_seen.add(v)
+    # the rows of 65, 129 and 193 entries end in a chunk of one entry: it is written behind a partial carry
+    assert single_seen == {v for v in short if np.diff(og.indptr)[v] % uo.CHUNK == 1} and len(single_seen) == 3
+    # epoch 1: only the weights 1 are active
+    counts = {int(np.diff(og.indptr)[v]): uo.chunk_counts(og, v, 1, N30)[0] for v in short}
+    assert counts[127].sum() == 0  # a non-empty row that copies its position
+    assert sum(int((na == 0).sum()) for na in counts.values()) >= 5  # chunks that are wholly inactive
+    assert any(((na[:-1] == 0) & (np.cumsum(na[::-1])[::-1][1:] > 0)).any() for na in counts.values())
+    assert counts[512][0] == 0 and counts[512][1] > 0  # ... ahead of a chunk that is not
+
+
+def test_hub_rows_above_the_split_have_mixed_activity(hubs):
+    _, og, rows = hubs
+    long_rows = [v for v in rows if np.diff(og.indptr)[v] > uo.LDS_ROW]
+    assert [int(np.diff(og.indptr)[v]) for v in long_rows] == [513, 514, 1025]
+    for t in EDGE_EPOCHS:
+        for v in long_rows:
+            na, size = uo.chunk_counts(og, v, t, N30)
+            assert 0 < na.sum() < size.sum()
+
+
+def test_split_mixed_is_what_it_says(split):
+    g, og = split
+    length = np.diff(og.indptr)
+    assert og.n == 1539 and len(og.w) == 787_976 and (g != g.T).nnz == 0 and og.w_max == 1.0
+    assert set(length) == {511, 512, 513, 514}
+    assert (length > uo.LDS_ROW).sum() >= 500 and (length <= uo.LDS_ROW).sum() >= 500
+    assert np.array_equal(og.w * 8, np.rint(og.w * 8)) and (og.w == 0).sum() > 10_000
+    for t in (1, 7, 29):
+        na = np.bincount(og.rows[og.active(t, N30)], minlength=og.n)
+        assert ((na > 0) & (na < length)).all(), t  # every row, whatever its length, has mixed activity
+
+
+def _clip_counts(q):
+    return {s * k: int((q == s * k * 2 ** 32).sum()) for k in (4, 8) for s in (-1, 1)}
+
+
+def test_contributions_reach_all_four_clip_values(hubs):
+    _, og, _ = hubs
+    for c, seed in SETTINGS:
+        y = uo.random_init(og.n, c, seed)
+        _, q = uo.contributions(og, y * np.float32(0.01), 7, n_epochs=N30, a=100.0, b=1.0, seed=seed)
+        counts = _clip_counts(q)
+        assert min(counts.values()) >= 1000, counts
+        assert np.abs(q).max() == 8 * 2 ** 32
+        _, q = uo.contributions(og, y * np.float32(0.01), 7, n_epochs=N30, a=30.0, b=0.4, seed=seed)
+        assert min(_clip_counts(q).values()) > 0
+        # with the default (a, b) the attraction stays below the clip (its maximum over d is about 1.1): only +-4
+        for scale in (1.0, 0.01):
+            _, q = uo.contributions(og, y * np.float32(scale), 7, n_epochs=N30, a=A, b=B, seed=seed)
+            counts = _clip_counts(q)
+            assert counts[-8] == counts[8] == 0 and np.abs(q).max() == 4 * 2 ** 32, counts
+            assert counts[-4] + counts[4] > 0, counts
+
+
+@pytest.mark.parametrize("n_epochs", (32, 30))
+def test_threshold_weights_sit_on_the_limits_of_the_schedule(n_epochs):
+    g = uo.threshold_weights(n_epochs)
+    og = uo.Graph(g)
+    names = list(uo.threshold_values(n_epochs))
+    val = uo.threshold_values(n_epochs)
+    assert og.w_max == 1.0 and (g != g.T).nnz == 0 and g.data.dtype == np.float32
+    exact = float(val["at"]) == 1.0 / n_epochs  # float32(1 / 32) is 1 / 32; float32(1 / 30) lies above 1 / 30
+    assert exact == (n_epochs == 32) and float(val["at"]) >= 1.0 / n_epochs
+    assert float(val["below"]) < 1.0 / n_epochs < float(val["above"]) and float(val["subnormal"]) == 2.0 ** -149
+    e = {name: int(og.indptr[0]) + q for q, name in enumerate(names)}  # the centre's row holds them in this order
+    assert np.array_equal(og.w[[e[k] for k in names]], [float(val[k]) for k in names])
+    assert np.signbit(g.data[e["minus_zero"]]) and not np.signbit(g.data[e["zero"]])
+    fires = og.fires(n_epochs)
+    assert [bool(fires[e[k]]) for k in names] == [True, True, True, False, False, False, True, False]
+    assert fires.sum() == 2 * (4 + 4)
+    seen = np.zeros(len(og.w), dtype=np.int64)
+    for t in range(n_epochs):
+        seen[og.active(t, n_epochs)] += 1
+    # the boundary weight fires, but its period is n_epochs (up to float32's rounding): not before the schedule ends
+    assert seen[e["at"]] == 0 and seen[e["above"]] == 0 and seen[e["below"]] == 0
+    assert seen[e["zero"]] == seen[e["minus_zero"]] == seen[e["subnormal"]] == 0
+    assert seen[e["one"]] == n_epochs - 1 and seen[e["third"]] == (n_epochs - 1) // 3
+    # rows with a firing and a never-firing entry, and rows whose only entry never becomes active
+    length = np.diff(og.indptr)
+    per_row = np.bincount(og.rows, weights=seen, minlength=og.n)
+    assert ((per_row == 0) & (length > 0)).sum() == 5 and (per_row[length == 2] > 0).all()
+
+
+def test_zero_weights_never_fire():
+    g = uo.zero_weights()
+    og = uo.Graph(g)
+    assert len(og.w) == 40 and og.w_max == 0.0 and np.signbit(g.data).sum() == 20 and not g.data.any()
+    assert not og.fires(N30).any() and all(len(og.active(t, N30)) == 0 for t in range(N30))
+    y = uo.random_init(og.n, 2, 0)
+    new, m = uo.epoch(og, y, 7, n_epochs=N30, a=A, b=B)
+    assert new.tobytes() == y.tobytes() and not m.any()
+
+
+def test_negative_samples_hit_the_row_itself_and_coincident_points(hubs):
+    from _umap_checks import coincident
+
+    _, og, _ = hubs
+    for c, seed in SETTINGS:
+        y = coincident(og, uo.random_init(og.n, c, seed))
+        own = other = 0
+        for t in EDGE_EPOCHS:
+            i, k, d2 = uo.negatives(og, y, t, n_epochs=N30, seed=seed)
+            own += int((k == i).sum())
+            other += int(((k != i) & (d2 == 0)).sum())
+        assert own > 0 and other > 0, (c, seed, own, other)
+
+
+def _moved(og, y, t, seed, drop, scale_kw):
+    full, m = uo.epoch(og, y, t, seed=seed, **scale_kw)
+    less, _ = uo.epoch(og, y, t, seed=seed, drop=drop, **scale_kw)
+    return (np.abs(full.astype(np.float64) - less.astype(np.float64)) > uo.tolerance(full, m)).any(axis=1)
+
+
+@pytest.mark.parametrize("kw, epochs", ((dict(a=A, b=B), EDGE_EPOCHS), (dict(a=100.0, b=1.0), EDGE_EPOCHS),
+                                        (dict(a=A, b=B, negative_sample_rate=1), (1, 7)),
+                                        (dict(a=A, b=B, negative_sample_rate=64), (7,))),
+                         ids=("default", "clipped", "r1", "r64"))
+def test_the_tolerance_cannot_hide_a_lost_entry_at_a_chunk_boundary(hubs, kw, epochs):
+    """Drop ONE active entry of a hub row from the oracle: the one at the compacted position 0, 63, 64 or the last one
+    (rows up to 512 entries), the first or the last (longer rows).  Rows are independent, so one oracle call drops the
+    entry of that position from every hub row at once.  Each row then moves by more than the tolerance of a
+    comparison: a kernel that loses, doubles or misplaces an entry across a ballot cannot pass."""
+    _, og, rows = hubs
+    length = np.diff(og.indptr)
+    for c, seed in SETTINGS:
+        y0 = uo.random_init(og.n, c, seed)
+        for scale in (1.0, 0.01):
+            y = y0 * np.float32(scale)
+            for t in epochs:
+                act = og.active(t, N30)
+                per_row = {v: act[og.rows[act] == v] for v in rows}
+                for pos in (0, 63, 64, -1):
+                    if pos >= 0 and length.max() > uo.LDS_ROW:
+                        who = [v for v in rows if len(per_row[v]) > pos and (length[v] <= uo.LDS_ROW or pos == 0)]
+                    else:
+                        who = [v for v in rows if len(per_row[v]) > 0]
+                    if not who:
+                        continue
+                    drop = np.array([per_row[v][pos] for v in who])
+                    moved = _moved(og, y, t, seed, drop, dict(n_epochs=N30, **kw))
+                    assert moved[who].all(), (c, seed, scale, t, pos, [int(length[v]) for v in who if not moved[v]])
+                    assert moved.sum() == len(who)  # and no other row
+
+
+def test_the_tolerance_cannot_hide_a_lost_entry_of_split_mixed(split):
+    _, og = split
+    y = uo.random_init(og.n, 2, 0)
+    act = og.active(7, N30)
+    first = act[np.unique(og.rows[act], return_index=True)[1]]
+    last = act[len(act) - 1 - np.unique(og.rows[act][::-1], return_index=True)[1]]
+    for drop in (first, last):
+        assert _moved(og, y, 7, 0, drop, dict(n_epochs=N30, a=A, b=B)).all()
