@@ -611,6 +611,26 @@ int icv_tsne_iterations(const int64_t *indptr, const int32_t *indices, const flo
                         double learning_rate, int32_t iter_begin, int32_t iter_end, float *y, float *update,
                         float *gains, void *workspace, float *stage_ms, void *stream);
 
+/* ---- tl.cnv_states: loss / neutral / gain calls of X_cnv by a Viterbi chain per chromosome -------------
+ * The matrix m (dense or CSR, float32 or float64, device pointers; a CSR with unique column indices inside
+ * [0, n_cols) in every row) is read as float64, an entry that is not stored is 0.0.
+ * icv_states_rowsq: rowsq[i] = the float64 sum of v v over row i's stored entries in stored order (every element of a
+ * dense row), one sequential sum per row; *nonfinite (device int32) is set to 0 and then to 1 where a value is not
+ * finite.  No synchronisation.
+ * icv_states_viterbi: rules 2-5 of the contract.  chr_start (device int32, n_chr + 1 ascending window numbers from 0 to
+ * n_cols) bounds the chains; amplitude > 0, h = 1 / (2 sigma^2) > 0, stay = log(1 - p) and sw = log(p / 2) are the
+ * host's doubles, all finite.  states (device int8, n_rows x n_cols row-major, no padding) receives -1 / 0 / +1,
+ * nonneutral[i] (device int32) the number of windows of row i that are not 0.  One wavefront per row, 9 bytes of LDS
+ * per window: 1 <= n_cols <= ICV_STATES_MAX_WINDOWS (ICV_ERR_INVALID beyond).  The result is a pure function of the
+ * arguments.  No synchronisation.
+ * icv_states_fraction: fraction[i] (device float64) = nonneutral[i] / n_cols, the correctly rounded quotient of the two
+ * integers (what the host's float64 division gives).  No synchronisation. */
+#define ICV_STATES_MAX_WINDOWS 16384
+int icv_states_rowsq(const icv_matrix *m, double *rowsq, int32_t *nonfinite, void *stream);
+int icv_states_viterbi(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, double amplitude, double h,
+                       double stay, double sw, int8_t *states, int32_t *nonneutral, void *stream);
+int icv_states_fraction(const int32_t *nonneutral, int64_t n_rows, int32_t n_cols, double *fraction, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

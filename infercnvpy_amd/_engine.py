@@ -1836,3 +1836,72 @@ def tsne_iterations(indptr, indices, data, y, update, gains, *, early_exaggerati
             stage_ms["validation_ms"] = stage_ms.get("validation_ms", 0.0) + float(ms[0])
             stage_ms["iterations_ms"] = stage_ms.get("iterations_ms", 0.0) + float(ms[1])
     return y, update, gains
+
+
+# ---- tl.cnv_states: sums of squares and the per-chromosome Viterbi chains on the device (icv_states_*) -------------------
+def states_input(x):
+    """The matrix tl.cnv_states reads, as one DeviceMatrix: a PackedCsr is read where it lies, a host CSR / CSC sends
+    indptr / indices / stored values once (canonical CSR: ascending unique columns), a CUDA tensor is used as it is, a
+    host dense array is uploaded.  Values stay float32 or float64; any other dtype becomes float64."""
+    torch = _torch()
+    if isinstance(x, PackedCsr):
+        return DeviceMatrix(indptr=x.indptr, indices=x.indices, data=x.data, shape=x.shape,
+                            indptr_host=np.zeros(x.n_rows + 1, dtype=np.int64), validate=False)
+    if isinstance(x, torch.Tensor):
+        if x.dim() != 2:
+            raise ValueError("tl.cnv_states: X must be 2-D")
+        t = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float64)
+        return DeviceMatrix(dense=t.cuda().contiguous())
+    if sp.issparse(x):
+        x = x.tocsr()
+        if x.data.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64)
+        return to_device_matrix(x)
+    a = np.asarray(x)
+    if a.ndim != 2:
+        raise ValueError("tl.cnv_states: X must be 2-D")
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    return to_device_matrix(a)
+
+
+def states_rowsq(dm: DeviceMatrix):
+    """(q, nonfinite): the device float64 vector of the per-row sums of v v over the stored entries in stored order
+    (DESIGN.md 4.13 rule 1) and a device int32 flag that is 1 when a value is not finite.  No synchronisation."""
+    torch = _torch()
+    lib = _lib.load()
+    with torch.cuda.device(dm.device):
+        q = torch.empty(max(dm.shape[0], 1), dtype=torch.float64, device="cuda")[:dm.shape[0]]
+        flag = torch.empty(1, dtype=torch.int32, device="cuda")
+        m = dm.c_struct()
+        _lib.check(lib.icv_states_rowsq(C.byref(m), _ptr(q), _ptr(flag), _stream_ptr(torch)))
+    return q, flag
+
+
+def states_viterbi(dm: DeviceMatrix, chr_start, *, amplitude, h, stay, sw):
+    """(states, nonneutral): device int8 ``n x W`` of -1 / 0 / +1 and device int32 counts of the windows that are not 0
+    (DESIGN.md 4.13 rules 2-5).  ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The
+    launch is enqueued on the current stream; nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    n, w = dm.shape
+    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
+    with torch.cuda.device(dm.device):
+        cs = torch.from_numpy(chr_start).cuda()
+        states = torch.empty((n, w), dtype=torch.int8, device="cuda")
+        count = torch.empty(n, dtype=torch.int32, device="cuda")
+        m = dm.c_struct()
+        _lib.check(lib.icv_states_viterbi(C.byref(m), _ptr(cs), int(chr_start.shape[0]) - 1, float(amplitude), float(h),
+                                          float(stay), float(sw), _ptr(states), _ptr(count), _stream_ptr(torch)))
+    return states, count
+
+
+def states_fraction(count, n_windows):
+    """Device float64 vector ``count / n_windows`` of the device int32 counts of :func:`states_viterbi`: the correctly
+    rounded quotient (``icv_states_fraction``), the bits the host's division gives.  Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    with torch.cuda.device(count.device):
+        out = torch.empty(count.shape[0], dtype=torch.float64, device="cuda")
+        _lib.check(lib.icv_states_fraction(_ptr(count), count.shape[0], int(n_windows), _ptr(out), _stream_ptr(torch)))
+    return out

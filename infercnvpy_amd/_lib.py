@@ -21,6 +21,7 @@ ICV_FLAG_TRUNC_TO_INT = 1
 ICV_FLAG_ROUND_F32 = 2
 ICV_FLAG_NO_APPLY = 4
 ICV_GRAM_BLOCK = 8192  # rows per split-K block of icv_gram_f64 (include/infercnv_hip.h)
+ICV_STATES_MAX_WINDOWS = 16384  # windows icv_states_viterbi keeps in LDS per cell (include/infercnv_hip.h)
 (ICV_KERNEL_NONE, ICV_KERNEL_GENERIC, ICV_KERNEL_WS, ICV_KERNEL_WS_CSR, ICV_KERNEL_X16, ICV_KERNEL_SD,
  ICV_KERNEL_SPLIT) = range(7)
 
@@ -43,6 +44,7 @@ EXPORTS = (
     "icv_umap_workspace", "icv_umap_epochs",
     "icv_tsne_affinities", "icv_tsne_symmetrize_count", "icv_tsne_symmetrize_fill", "icv_tsne_workspace",
     "icv_tsne_iterations",
+    "icv_states_rowsq", "icv_states_viterbi", "icv_states_fraction",
 )
 
 
@@ -181,6 +183,9 @@ def load():
     lib.icv_tsne_workspace.argtypes = [i64, i64, i32, P(i64)]
     lib.icv_tsne_iterations.argtypes = [vp, vp, vp, i64, i64, i32, dbl, i32, dbl, i32, i32, vp, vp, vp, vp, P(C.c_float),
                                         vp]
+    lib.icv_states_rowsq.argtypes = [P(Matrix), vp, vp, vp]
+    lib.icv_states_viterbi.argtypes = [P(Matrix), vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp]
+    lib.icv_states_fraction.argtypes = [vp, i64, i32, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -41,6 +41,7 @@
 #include "icv_leiden.hpp"
 #include "icv_umap.hpp"
 #include "icv_tsne.hpp"
+#include "icv_states.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -4028,6 +4029,82 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
     }
     HIP_TRY(toc(1));
     if (stage_ms) stage_ms[0] = ms[0], stage_ms[1] = ms[1];
+    return ICV_OK;
+}
+
+// ---- tl.cnv_states ---------------------------------------------------------------------------------------
+static_assert(icv::kStMaxWindows == ICV_STATES_MAX_WINDOWS, "the header's window cap is the kernel's");
+static_assert((size_t)icv::kStMaxWindows * icv::kStLdsPerWindow <= (size_t)icv::kLdsLimit, "one cell fits a CU's LDS");
+
+int icv_states_rowsq(const icv_matrix* m, double* rowsq, int32_t* nonfinite, void* stream) {
+    if (!m || !rowsq || !nonfinite || m->n_rows < 0 || m->n_cols < 0 || (m->dtype != ICV_F32 && m->dtype != ICV_F64) ||
+        (m->format != ICV_DENSE && m->format != ICV_CSR) || (m->format == ICV_DENSE && m->ld < m->n_cols))
+        return fail(ICV_ERR_INVALID, "bad states_rowsq arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(nonfinite, 0, sizeof(int32_t), st));
+    if (m->n_rows == 0) return ICV_OK;
+    // (a CSR without stored entries may come with null indices / values: they are never read then)
+    if (m->format == ICV_DENSE ? (!m->values && m->n_cols > 0) : !m->indptr)
+        return fail(ICV_ERR_INVALID, "states_rowsq: incomplete matrix");
+    const dim3 grid((unsigned)((m->n_rows + 255) / 256)), block(256);
+#define ICV_ROWSQ(T)                                                                                                   \
+    if (m->format == ICV_CSR)                                                                                          \
+        hipLaunchKernelGGL(icv::k_states_rowsq_csr<T>, grid, block, 0, st, (const T*)m->values, m->indptr, m->n_rows,  \
+                           rowsq, nonfinite);                                                                          \
+    else                                                                                                               \
+        hipLaunchKernelGGL(icv::k_states_rowsq_dense<T>, grid, block, 0, st, (const T*)m->values, m->ld, m->n_rows,    \
+                           m->n_cols, rowsq, nonfinite);
+    if (m->dtype == ICV_F32) { ICV_ROWSQ(float) }
+    else { ICV_ROWSQ(double) }
+#undef ICV_ROWSQ
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_states_viterbi(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, double amplitude, double h,
+                       double stay, double sw, int8_t* states, int32_t* nonneutral, void* stream) {
+    if (!m || !chr_start || !states || !nonneutral || n_chr < 1 || m->n_rows < 0 ||
+        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR))
+        return fail(ICV_ERR_INVALID, "bad states_viterbi arguments");
+    if (m->n_cols < 1 || m->n_cols > ICV_STATES_MAX_WINDOWS)
+        return fail(ICV_ERR_INVALID, "states_viterbi: n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
+                                         std::to_string(ICV_STATES_MAX_WINDOWS) + "] (9 bytes of LDS per window)");
+    if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, "states_viterbi: more chromosomes than windows");
+    if (!(std::isfinite(amplitude) && amplitude > 0.0 && std::isfinite(h) && h > 0.0 && std::isfinite(stay) &&
+          std::isfinite(sw)))
+        return fail(ICV_ERR_INVALID, "states_viterbi: amplitude and h must be finite and > 0, stay and sw finite");
+    if (m->format == ICV_DENSE ? (m->ld < m->n_cols || !m->values) : !m->indptr)
+        return fail(ICV_ERR_INVALID, "states_viterbi: incomplete matrix");
+    if (m->n_rows == 0) return ICV_OK;
+    if (m->n_rows > 0x7fffffffLL) return fail(ICV_ERR_UNSUPPORTED, "states_viterbi: more than 2^31 - 1 rows in one call");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = icv::st_lds_bytes(m->n_cols);
+    const icv::StParams P{amplitude, h, stay, sw};
+    const dim3 grid((unsigned)m->n_rows), block(64);
+#define ICV_VITERBI(T, CSR)                                                                                            \
+    {                                                                                                                  \
+        auto kern = icv::k_states_viterbi<T, CSR>;                                                                     \
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                    (int)lds));                                                                        \
+        hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)m->values, m->indptr, m->indices, m->ld, m->n_cols,   \
+                           chr_start, n_chr, P, states, nonneutral);                                                   \
+    }
+    if (m->format == ICV_CSR) {
+        if (m->dtype == ICV_F32) ICV_VITERBI(float, true) else ICV_VITERBI(double, true)
+    } else {
+        if (m->dtype == ICV_F32) ICV_VITERBI(float, false) else ICV_VITERBI(double, false)
+    }
+#undef ICV_VITERBI
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_states_fraction(const int32_t* nonneutral, int64_t n_rows, int32_t n_cols, double* fraction, void* stream) {
+    if (!nonneutral || !fraction || n_rows < 0 || n_cols < 1) return fail(ICV_ERR_INVALID, "bad states_fraction arguments");
+    if (n_rows == 0) return ICV_OK;
+    hipLaunchKernelGGL(icv::k_states_fraction, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), nonneutral, n_rows, n_cols, fraction);
+    HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
 
