@@ -631,6 +631,39 @@ int icv_states_viterbi(const icv_matrix *m, const int32_t *chr_start, int32_t n_
                        double stay, double sw, int8_t *states, int32_t *nonneutral, void *stream);
 int icv_states_fraction(const int32_t *nonneutral, int64_t n_rows, int32_t n_cols, double *fraction, void *stream);
 
+/* ---- tl.cnv_segments: segment tables of the int8 call matrix of tl.cnv_states ------------------------------
+ * states (device int8, n_rows x n_cols row-major, no padding, any alignment) holds -1 / 0 / +1; chr_start (device int32,
+ * n_chr + 1 ascending window numbers from 0 to n_cols, 1 <= n_chr <= n_cols) bounds the chromosomes.  Window t starts a
+ * run iff states[i,t] != 0 and (t is a chromosome start or states[i,t-1] differs); it ends one iff states[i,t] != 0 and
+ * (t + 1 == n_cols or t + 1 is a chromosome start or states[i,t+1] differs).  Everything is integer arithmetic: the
+ * results are a pure function of the arguments.  n_cols has no limit below int32.  No synchronisation anywhere.
+ * icv_segments_count: counts[i] (device int64) = the runs of row i; *bad (device int32) is set to 0 and then to 1 where a
+ * value is not -1 / 0 / +1.  icv_row_offsets turns counts into offsets (n_rows + 1).
+ * icv_segments_fill: segment offsets[i] + k (row i's k-th run, by start) gets seg_row (int64), seg_start, seg_end
+ * (int32, exclusive) and seg_state (int8); the four tables hold n_segments = offsets[n_rows] entries and nothing is
+ * written outside them.
+ * icv_state_votes: rows (device int64, n_listed row numbers, sorted by group) and group_ptr (device int64, n_groups + 1
+ * ascending positions from 0 to n_listed) list the rows of every group; loss / gain (device int32, n_groups x n_cols) are
+ * zeroed and receive the number of listed rows of the group with -1 / +1 at the window (integer atomic adds).  A row
+ * number outside [0, n_rows) is skipped; *bad as above, for the rows that are listed.  n_groups has no limit.
+ * icv_state_consensus: consensus (device int8, n_groups x n_cols) = +1 where gain >= need[g] and gain > loss, -1 where
+ * loss >= need[g] and loss > gain, else 0 (need: device int32 per group).
+ * icv_segments_support: for every segment of the consensus matrix (the tables of icv_segments_fill, seg_row = the group)
+ * cells_min (int32) / cells_sum (int64) = the minimum / the sum over its windows of the winning state's count; a segment
+ * outside the n_groups x n_cols tables gets 0 / 0. */
+int icv_segments_count(const int8_t *states, int64_t n_rows, int32_t n_cols, const int32_t *chr_start, int32_t n_chr,
+                       int64_t *counts, int32_t *bad, void *stream);
+int icv_segments_fill(const int8_t *states, int64_t n_rows, int32_t n_cols, const int32_t *chr_start, int32_t n_chr,
+                      const int64_t *offsets, int64_t n_segments, int64_t *seg_row, int32_t *seg_start, int32_t *seg_end,
+                      int8_t *seg_state, void *stream);
+int icv_state_votes(const int8_t *states, int64_t n_rows, int32_t n_cols, const int64_t *rows, int64_t n_listed,
+                    const int64_t *group_ptr, int64_t n_groups, int32_t *loss, int32_t *gain, int32_t *bad, void *stream);
+int icv_state_consensus(const int32_t *loss, const int32_t *gain, const int32_t *need, int64_t n_groups, int32_t n_cols,
+                        int8_t *consensus, void *stream);
+int icv_segments_support(const int64_t *seg_row, const int32_t *seg_start, const int32_t *seg_end, const int8_t *seg_state,
+                         int64_t n_segments, const int32_t *loss, const int32_t *gain, int64_t n_groups, int32_t n_cols,
+                         int32_t *cells_min, int64_t *cells_sum, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -1905,3 +1905,96 @@ def states_fraction(count, n_windows):
         out = torch.empty(count.shape[0], dtype=torch.float64, device="cuda")
         _lib.check(lib.icv_states_fraction(_ptr(count), count.shape[0], int(n_windows), _ptr(out), _stream_ptr(torch)))
     return out
+
+
+# ---- tl.cnv_segments: runs of the int8 call matrix, group votes and consensus on the device (icv_segments_*, icv_state_*) --
+def segments_input(x):
+    """The int8 call matrix tl.cnv_segments reads, as a contiguous CUDA tensor: a CUDA tensor is read where it lies, a
+    host array is uploaded once.  (The caller checked shape and dtype.)"""
+    torch = _torch()
+    if isinstance(x, torch.Tensor):
+        return x.cuda().contiguous()
+    a = np.ascontiguousarray(x)
+    if not a.flags.writeable:  # (torch does not wrap a read-only array)
+        a = a.copy()
+    return torch.from_numpy(a).cuda()
+
+
+def segments_tables(states, chr_start):
+    """The runs of every row of ``states`` (device int8 n x W; DESIGN.md 4.14 rules 1-2) as device tensors
+    ``(counts int64 n, offsets int64 n + 1, row int64, start int32, end int32, state int8, bad int32 flag)``.
+    ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  One scalar (the number of segments)
+    is read back between the count and the fill."""
+    torch = _torch()
+    lib = _lib.load()
+    assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
+    n, w = int(states.shape[0]), int(states.shape[1])
+    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
+    n_chr = int(chr_start.shape[0]) - 1
+    with torch.cuda.device(states.device):
+        st = _stream_ptr(torch)
+        cs = torch.from_numpy(chr_start).cuda()
+        counts = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")[:n]
+        bad = torch.empty(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.icv_segments_count(_ptr(states), n, w, _ptr(cs), n_chr, _ptr(counts), _ptr(bad), st))
+        offsets = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+        _lib.check(lib.icv_row_offsets(_ptr(counts), n, _ptr(offsets), st))
+        n_seg = int(offsets[-1].item())
+        row = torch.empty(max(n_seg, 1), dtype=torch.int64, device="cuda")[:n_seg]
+        start = torch.empty(max(n_seg, 1), dtype=torch.int32, device="cuda")[:n_seg]
+        end = torch.empty(max(n_seg, 1), dtype=torch.int32, device="cuda")[:n_seg]
+        state = torch.empty(max(n_seg, 1), dtype=torch.int8, device="cuda")[:n_seg]
+        _lib.check(lib.icv_segments_fill(_ptr(states), n, w, _ptr(cs), n_chr, _ptr(offsets), n_seg, _ptr(row), _ptr(start),
+                                         _ptr(end), _ptr(state), st))
+    return counts, offsets, row, start, end, state, bad
+
+
+def state_votes(states, rows, group_ptr):
+    """(loss, gain, bad): device int32 ``G x W`` counts of the listed rows of every group with -1 / +1 at each window
+    (rule 4) and the device int32 bad-value flag.  ``rows``: host int64 row numbers sorted by group, ``group_ptr``: host
+    int64 G + 1 positions.  Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
+    n, w = int(states.shape[0]), int(states.shape[1])
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    group_ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
+    g = int(group_ptr.shape[0]) - 1
+    assert g >= 0 and int(group_ptr[0]) == 0 and int(group_ptr[-1]) == rows.shape[0]
+    with torch.cuda.device(states.device):
+        d_rows = torch.from_numpy(rows).cuda()
+        d_ptr = torch.from_numpy(group_ptr).cuda()
+        loss = torch.empty((g, w), dtype=torch.int32, device="cuda")
+        gain = torch.empty((g, w), dtype=torch.int32, device="cuda")
+        bad = torch.empty(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.icv_state_votes(_ptr(states), n, w, _ptr(d_rows), int(rows.shape[0]), _ptr(d_ptr), g, _ptr(loss),
+                                       _ptr(gain), _ptr(bad), _stream_ptr(torch)))
+    return loss, gain, bad
+
+
+def state_consensus(loss, gain, need):
+    """Device int8 ``G x W`` consensus of rule 5; ``need``: host int32 per group."""
+    torch = _torch()
+    lib = _lib.load()
+    g, w = int(loss.shape[0]), int(loss.shape[1])
+    need = np.ascontiguousarray(need, dtype=np.int32)
+    assert need.shape == (g,) and loss.dtype == torch.int32 and gain.dtype == torch.int32 and gain.shape == loss.shape
+    with torch.cuda.device(loss.device):
+        d_need = torch.from_numpy(need).cuda()
+        consensus = torch.empty((g, w), dtype=torch.int8, device="cuda")
+        _lib.check(lib.icv_state_consensus(_ptr(loss), _ptr(gain), _ptr(d_need), g, w, _ptr(consensus), _stream_ptr(torch)))
+    return consensus
+
+
+def segments_support(row, start, end, state, loss, gain):
+    """(cells_min int32, cells_sum int64) of rule 6 for the segments of the consensus matrix, device tensors."""
+    torch = _torch()
+    lib = _lib.load()
+    n_seg = int(row.shape[0])
+    g, w = int(loss.shape[0]), int(loss.shape[1])
+    with torch.cuda.device(loss.device):
+        cells_min = torch.empty(max(n_seg, 1), dtype=torch.int32, device="cuda")[:n_seg]
+        cells_sum = torch.empty(max(n_seg, 1), dtype=torch.int64, device="cuda")[:n_seg]
+        _lib.check(lib.icv_segments_support(_ptr(row), _ptr(start), _ptr(end), _ptr(state), n_seg, _ptr(loss), _ptr(gain), g,
+                                            w, _ptr(cells_min), _ptr(cells_sum), _stream_ptr(torch)))
+    return cells_min, cells_sum

@@ -45,6 +45,7 @@ EXPORTS = (
     "icv_tsne_affinities", "icv_tsne_symmetrize_count", "icv_tsne_symmetrize_fill", "icv_tsne_workspace",
     "icv_tsne_iterations",
     "icv_states_rowsq", "icv_states_viterbi", "icv_states_fraction",
+    "icv_segments_count", "icv_segments_fill", "icv_state_votes", "icv_state_consensus", "icv_segments_support",
 )
 
 
@@ -186,6 +187,11 @@ def load():
     lib.icv_states_rowsq.argtypes = [P(Matrix), vp, vp, vp]
     lib.icv_states_viterbi.argtypes = [P(Matrix), vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp]
     lib.icv_states_fraction.argtypes = [vp, i64, i32, vp, vp]
+    lib.icv_segments_count.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp]
+    lib.icv_segments_fill.argtypes = [vp, i64, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp]
+    lib.icv_state_votes.argtypes = [vp, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.icv_state_consensus.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    lib.icv_segments_support.argtypes = [vp, vp, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -42,6 +42,7 @@
 #include "icv_umap.hpp"
 #include "icv_tsne.hpp"
 #include "icv_states.hpp"
+#include "icv_segments.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -4104,6 +4105,115 @@ int icv_states_fraction(const int32_t* nonneutral, int64_t n_rows, int32_t n_col
     if (n_rows == 0) return ICV_OK;
     hipLaunchKernelGGL(icv::k_states_fraction, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), nonneutral, n_rows, n_cols, fraction);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_segments -------------------------------------------------------------------------------------
+namespace {
+
+// the chromosome-start bit mask of one call (rules 1 of the contract), in a temporary of the stream
+int seg_chr_mask(const int32_t* chr_start, int32_t n_chr, int32_t n_cols, AsyncBuf& mask, hipStream_t st) {
+    const size_t bytes = icv::seg_mask_words(n_cols) * sizeof(uint32_t);
+    HIP_TRY(mask.alloc(bytes, st));
+    HIP_TRY(hipMemsetAsync(mask.p, 0, bytes, st));
+    hipLaunchKernelGGL(icv::k_seg_chr_mask, dim3((unsigned)((n_chr + 255) / 256)), dim3(256), 0, st, chr_start, n_chr,
+                       n_cols, mask.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+bool seg_bad_shape(const void* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start, int32_t n_chr) {
+    return !states || !chr_start || n_rows < 0 || n_cols < 1 || n_chr < 1 || n_chr > n_cols;
+}
+
+constexpr int64_t kSegMaxBlocks = 0x7fffffffLL;
+
+}  // namespace
+
+int icv_segments_count(const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start, int32_t n_chr,
+                       int64_t* counts, int32_t* bad, void* stream) {
+    if (seg_bad_shape(states, n_rows, n_cols, chr_start, n_chr) || !counts || !bad)
+        return fail(ICV_ERR_INVALID, "bad segments_count arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return ICV_OK;
+    const int64_t blocks = (n_rows + icv::kSegRowsPerBlock - 1) / icv::kSegRowsPerBlock;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "segments_count: too many rows for one call");
+    AsyncBuf mask;
+    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
+    hipLaunchKernelGGL(icv::k_seg_rows<false>, dim3((unsigned)blocks), dim3(64 * icv::kSegRowsPerBlock), 0, st, states,
+                       n_rows, n_cols, mask.as<uint32_t>(), counts, bad, (const int64_t*)nullptr, (int64_t)0,
+                       (int64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int8_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_segments_fill(const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start, int32_t n_chr,
+                      const int64_t* offsets, int64_t n_segments, int64_t* seg_row, int32_t* seg_start, int32_t* seg_end,
+                      int8_t* seg_state, void* stream) {
+    if (seg_bad_shape(states, n_rows, n_cols, chr_start, n_chr) || !offsets || n_segments < 0 ||
+        (n_segments > 0 && (!seg_row || !seg_start || !seg_end || !seg_state)))
+        return fail(ICV_ERR_INVALID, "bad segments_fill arguments");
+    if (n_rows == 0 || n_segments == 0) return ICV_OK;
+    const int64_t blocks = (n_rows + icv::kSegRowsPerBlock - 1) / icv::kSegRowsPerBlock;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "segments_fill: too many rows for one call");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AsyncBuf mask;
+    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
+    hipLaunchKernelGGL(icv::k_seg_rows<true>, dim3((unsigned)blocks), dim3(64 * icv::kSegRowsPerBlock), 0, st, states,
+                       n_rows, n_cols, mask.as<uint32_t>(), (int64_t*)nullptr, (int32_t*)nullptr, offsets, n_segments,
+                       seg_row, seg_start, seg_end, seg_state);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_state_votes(const int8_t* states, int64_t n_rows, int32_t n_cols, const int64_t* rows, int64_t n_listed,
+                    const int64_t* group_ptr, int64_t n_groups, int32_t* loss, int32_t* gain, int32_t* bad, void* stream) {
+    if (!states || n_rows < 0 || n_cols < 1 || n_listed < 0 || (n_listed > 0 && !rows) || !group_ptr || n_groups < 0 ||
+        (n_groups > 0 && (!loss || !gain)) || !bad)
+        return fail(ICV_ERR_INVALID, "bad state_votes arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    if (n_groups == 0) return ICV_OK;
+    const size_t table = (size_t)n_groups * (size_t)n_cols * sizeof(int32_t);
+    HIP_TRY(hipMemsetAsync(loss, 0, table, st));
+    HIP_TRY(hipMemsetAsync(gain, 0, table, st));
+    if (n_listed == 0 || n_rows == 0) return ICV_OK;
+    const int64_t n_tiles = ((int64_t)n_cols + icv::kVoteTile - 1) / icv::kVoteTile;
+    const int64_t blocks = (n_listed + icv::kVoteRows - 1) / icv::kVoteRows * n_tiles;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "state_votes: too many rows x windows for one call");
+    hipLaunchKernelGGL(icv::k_state_votes, dim3((unsigned)blocks), dim3(256), 0, st, states, n_rows, n_cols, rows, n_listed,
+                       group_ptr, n_groups, (uint32_t)n_tiles, loss, gain, bad);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_state_consensus(const int32_t* loss, const int32_t* gain, const int32_t* need, int64_t n_groups, int32_t n_cols,
+                        int8_t* consensus, void* stream) {
+    if (n_groups < 0 || n_cols < 1 || (n_groups > 0 && (!loss || !gain || !need || !consensus)))
+        return fail(ICV_ERR_INVALID, "bad state_consensus arguments");
+    if (n_groups == 0) return ICV_OK;
+    const int64_t blocks = (n_groups * (int64_t)n_cols + 255) / 256;
+    if (n_groups > kSegMaxBlocks || blocks > kSegMaxBlocks)
+        return fail(ICV_ERR_UNSUPPORTED, "state_consensus: too many groups x windows for one call");
+    hipLaunchKernelGGL(icv::k_state_consensus, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), loss,
+                       gain, need, n_groups, n_cols, consensus);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_segments_support(const int64_t* seg_row, const int32_t* seg_start, const int32_t* seg_end, const int8_t* seg_state,
+                         int64_t n_segments, const int32_t* loss, const int32_t* gain, int64_t n_groups, int32_t n_cols,
+                         int32_t* cells_min, int64_t* cells_sum, void* stream) {
+    if (n_segments < 0 || n_groups < 0 || n_cols < 1 ||
+        (n_segments > 0 && (!seg_row || !seg_start || !seg_end || !seg_state || !loss || !gain || !cells_min || !cells_sum)))
+        return fail(ICV_ERR_INVALID, "bad segments_support arguments");
+    if (n_segments == 0) return ICV_OK;
+    const int64_t blocks = (n_segments + 255) / 256;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "segments_support: too many segments for one call");
+    hipLaunchKernelGGL(icv::k_seg_support, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), seg_row,
+                       seg_start, seg_end, seg_state, n_segments, loss, gain, n_groups, n_cols, cells_min, cells_sum);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
