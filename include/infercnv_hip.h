@@ -664,6 +664,31 @@ int icv_segments_support(const int64_t *seg_row, const int32_t *seg_start, const
                          int64_t n_segments, const int32_t *loss, const int32_t *gain, int64_t n_groups, int32_t n_cols,
                          int32_t *cells_min, int64_t *cells_sum, void *stream);
 
+/* ---- tl.cnv_posteriors and tl.cnv_states_filter: posteriors of the model of tl.cnv_states -------------------
+ * icv_posterior_chains: forward-backward along every chromosome of every row of m (the matrix, chr_start, amplitude and
+ * h as for icv_states_viterbi; ps = 1 - p and pw = p / 2 are the host's doubles for a p in (0, 1), pw a normal float64).
+ * Emissions b(s) = exp_(e_s - max e) with e_s of 4.13 and the written exponential of 4.12; forward al_t = u_t / c_t with
+ * u_t(s) = (((al(0) A(0,s)) + (al(1) A(1,s))) + (al(2) A(2,s))) b_t(s), c_t = (u(0) + u(1)) + u(2); backward
+ * be_t(r) = (((A(r,0) g(0)) + (A(r,1) g(1))) + (A(r,2) g(2))) / c_{t+1} with g = b_{t+1} be_{t+1}; the posterior is
+ * (al_t be_t) / ((w(0) + w(1)) + w(2)).  Float64, no fused multiply-add, every division correctly rounded: the result is a
+ * pure function of the arguments.  neutral (device float64, n_rows x n_cols row-major, no padding) receives P(neutral);
+ * loss and gain are either both null or receive P(loss) and P(gain).  One wavefront per row, 32 bytes of LDS per window:
+ * 1 <= n_cols <= ICV_POSTERIOR_MAX_WINDOWS (ICV_ERR_INVALID beyond).  No synchronisation.
+ * icv_states_filter: states (device int8) and p_neutral (device float64), both n_rows x n_cols row-major without padding;
+ * runs as in 4.14.  With q_t = int64(rint(p_neutral[i,t] 2^40)), a run [s, e) is reset to 0 in filtered (device int8,
+ * n_rows x n_cols) iff double(sum of its q_t) / (double(e - s) 2^40) > max_p_normal (in [0, 1]); every other window is
+ * copied.  nonneutral[i] / removed[i] (device int32) = the windows of filtered's row i that are not 0 / the runs of row i
+ * that were reset.  *bad (device int32) is set to 0 and then to 1 where a state is not -1 / 0 / +1 or a posterior is not a
+ * number in [0, 1].  Integer sums: a pure function of the arguments.  No row is held in LDS; n_cols <=
+ * ICV_FILTER_MAX_WINDOWS keeps a run's sum inside int64 (ICV_ERR_UNSUPPORTED beyond).  No synchronisation. */
+#define ICV_POSTERIOR_MAX_WINDOWS 4096
+#define ICV_FILTER_MAX_WINDOWS 4194304
+int icv_posterior_chains(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, double amplitude, double h,
+                         double ps, double pw, double *neutral, double *loss, double *gain, void *stream);
+int icv_states_filter(const int8_t *states, const double *p_neutral, int64_t n_rows, int32_t n_cols,
+                      const int32_t *chr_start, int32_t n_chr, double max_p_normal, int8_t *filtered, int32_t *nonneutral,
+                      int32_t *removed, int32_t *bad, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -1907,6 +1907,50 @@ def states_fraction(count, n_windows):
     return out
 
 
+# ---- tl.cnv_posteriors / tl.cnv_states_filter: forward-backward chains and the posterior filter --------
+def posterior_chains(dm: DeviceMatrix, chr_start, *, amplitude, h, ps, pw, all_states=False):
+    """(neutral, loss, gain): device float64 ``n x W`` posteriors of DESIGN.md 4.15 rules 2-5; ``loss`` and ``gain`` are
+    None unless ``all_states``.  ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The
+    launch is enqueued on the current stream; nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    n, w = dm.shape
+    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
+    with torch.cuda.device(dm.device):
+        cs = torch.from_numpy(chr_start).cuda()
+        neutral = torch.empty((n, w), dtype=torch.float64, device="cuda")
+        loss = torch.empty((n, w), dtype=torch.float64, device="cuda") if all_states else None
+        gain = torch.empty((n, w), dtype=torch.float64, device="cuda") if all_states else None
+        m = dm.c_struct()
+        _lib.check(lib.icv_posterior_chains(C.byref(m), _ptr(cs), int(chr_start.shape[0]) - 1, float(amplitude), float(h),
+                                            float(ps), float(pw), _ptr(neutral), _ptr(loss) if all_states else None,
+                                            _ptr(gain) if all_states else None, _stream_ptr(torch)))
+    return neutral, loss, gain
+
+
+def states_filter(states, p_neutral, chr_start, max_p_normal):
+    """(filtered int8 n x W, nonneutral int32 n, removed int32 n, bad int32 flag), device tensors: the calls of
+    ``states`` (device int8) with every run whose mean ``p_neutral`` (device float64) is above ``max_p_normal`` reset to
+    0 (the filter's rules 1-3).  Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
+    assert p_neutral.is_cuda and p_neutral.dtype == torch.float64 and p_neutral.is_contiguous()
+    assert p_neutral.shape == states.shape and p_neutral.device == states.device
+    n, w = int(states.shape[0]), int(states.shape[1])
+    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
+    with torch.cuda.device(states.device):
+        cs = torch.from_numpy(chr_start).cuda()
+        filtered = torch.empty((n, w), dtype=torch.int8, device="cuda")
+        count = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        removed = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        bad = torch.empty(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.icv_states_filter(_ptr(states), _ptr(p_neutral), n, w, _ptr(cs), int(chr_start.shape[0]) - 1,
+                                         float(max_p_normal), _ptr(filtered), _ptr(count), _ptr(removed), _ptr(bad),
+                                         _stream_ptr(torch)))
+    return filtered, count, removed, bad
+
+
 # ---- tl.cnv_segments: runs of the int8 call matrix, group votes and consensus on the device (icv_segments_*, icv_state_*) --
 def segments_input(x):
     """The int8 call matrix tl.cnv_segments reads, as a contiguous CUDA tensor: a CUDA tensor is read where it lies, a

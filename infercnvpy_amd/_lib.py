@@ -22,6 +22,8 @@ ICV_FLAG_ROUND_F32 = 2
 ICV_FLAG_NO_APPLY = 4
 ICV_GRAM_BLOCK = 8192  # rows per split-K block of icv_gram_f64 (include/infercnv_hip.h)
 ICV_STATES_MAX_WINDOWS = 16384  # windows icv_states_viterbi keeps in LDS per cell (include/infercnv_hip.h)
+ICV_POSTERIOR_MAX_WINDOWS = 4096  # windows icv_posterior_chains keeps in LDS per cell (include/infercnv_hip.h)
+ICV_FILTER_MAX_WINDOWS = 1 << 22  # windows per row of icv_states_filter: a run's int64 sum (include/infercnv_hip.h)
 (ICV_KERNEL_NONE, ICV_KERNEL_GENERIC, ICV_KERNEL_WS, ICV_KERNEL_WS_CSR, ICV_KERNEL_X16, ICV_KERNEL_SD,
  ICV_KERNEL_SPLIT) = range(7)
 
@@ -46,6 +48,7 @@ EXPORTS = (
     "icv_tsne_iterations",
     "icv_states_rowsq", "icv_states_viterbi", "icv_states_fraction",
     "icv_segments_count", "icv_segments_fill", "icv_state_votes", "icv_state_consensus", "icv_segments_support",
+    "icv_posterior_chains", "icv_states_filter",
 )
 
 
@@ -192,6 +195,8 @@ def load():
     lib.icv_state_votes.argtypes = [vp, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.icv_state_consensus.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     lib.icv_segments_support.argtypes = [vp, vp, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]
+    lib.icv_posterior_chains.argtypes = [P(Matrix), vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp, vp]
+    lib.icv_states_filter.argtypes = [vp, vp, i64, i32, vp, i32, dbl, vp, vp, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -43,6 +43,7 @@
 #include "icv_tsne.hpp"
 #include "icv_states.hpp"
 #include "icv_segments.hpp"
+#include "icv_posterior.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -4214,6 +4215,72 @@ int icv_segments_support(const int64_t* seg_row, const int32_t* seg_start, const
     if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "segments_support: too many segments for one call");
     hipLaunchKernelGGL(icv::k_seg_support, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), seg_row,
                        seg_start, seg_end, seg_state, n_segments, loss, gain, n_groups, n_cols, cells_min, cells_sum);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_posteriors and tl.cnv_states_filter -------------------------------------------------------------
+static_assert(icv::kPoMaxWindows == ICV_POSTERIOR_MAX_WINDOWS, "the header's window cap is the kernel's");
+static_assert((size_t)icv::kPoMaxWindows * icv::kPoLdsPerWindow <= (size_t)icv::kLdsLimit, "one cell fits a CU's LDS");
+static_assert(icv::kFiMaxWindows == ICV_FILTER_MAX_WINDOWS, "the header's window cap is the kernel's");
+
+int icv_posterior_chains(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, double amplitude, double h,
+                         double ps, double pw, double* neutral, double* loss, double* gain, void* stream) {
+    if (!m || !chr_start || !neutral || (loss == nullptr) != (gain == nullptr) || n_chr < 1 || m->n_rows < 0 ||
+        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR))
+        return fail(ICV_ERR_INVALID, "bad posterior_chains arguments");
+    if (m->n_cols < 1 || m->n_cols > ICV_POSTERIOR_MAX_WINDOWS)
+        return fail(ICV_ERR_INVALID, "posterior_chains: n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
+                                         std::to_string(ICV_POSTERIOR_MAX_WINDOWS) + "] (32 bytes of LDS per window)");
+    if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, "posterior_chains: more chromosomes than windows");
+    if (!(std::isfinite(amplitude) && amplitude > 0.0 && std::isfinite(h) && h > 0.0 && std::isnormal(pw) && pw > 0.0 &&
+          ps > 0.0 && ps < 1.0 && pw < 0.5))
+        return fail(ICV_ERR_INVALID, "posterior_chains: amplitude and h must be finite and > 0, ps = 1 - p and pw = p / 2 "
+                                     "for a p in (0, 1) with pw a normal float64");
+    if (m->format == ICV_DENSE ? (m->ld < m->n_cols || !m->values) : !m->indptr)
+        return fail(ICV_ERR_INVALID, "posterior_chains: incomplete matrix");
+    if (m->n_rows == 0) return ICV_OK;
+    if (m->n_rows > 0x7fffffffLL) return fail(ICV_ERR_UNSUPPORTED, "posterior_chains: more than 2^31 - 1 rows in one call");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = icv::po_lds_bytes(m->n_cols);
+    const icv::PoParams P{amplitude, h, ps, pw};
+    const dim3 grid((unsigned)m->n_rows), block(64);
+#define ICV_POSTERIOR(T, CSR)                                                                                          \
+    {                                                                                                                  \
+        auto kern = icv::k_posterior_chains<T, CSR>;                                                                   \
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                    (int)lds));                                                                        \
+        hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)m->values, m->indptr, m->indices, m->ld, m->n_cols,   \
+                           chr_start, n_chr, P, neutral, loss, gain);                                                  \
+    }
+    if (m->format == ICV_CSR) {
+        if (m->dtype == ICV_F32) ICV_POSTERIOR(float, true) else ICV_POSTERIOR(double, true)
+    } else {
+        if (m->dtype == ICV_F32) ICV_POSTERIOR(float, false) else ICV_POSTERIOR(double, false)
+    }
+#undef ICV_POSTERIOR
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_states_filter(const int8_t* states, const double* p_neutral, int64_t n_rows, int32_t n_cols,
+                      const int32_t* chr_start, int32_t n_chr, double max_p_normal, int8_t* filtered, int32_t* nonneutral,
+                      int32_t* removed, int32_t* bad, void* stream) {
+    if (seg_bad_shape(states, n_rows, n_cols, chr_start, n_chr) || !p_neutral || !filtered || !nonneutral || !removed ||
+        !bad || !(max_p_normal >= 0.0 && max_p_normal <= 1.0))
+        return fail(ICV_ERR_INVALID, "bad states_filter arguments");
+    if (n_cols > ICV_FILTER_MAX_WINDOWS)
+        return fail(ICV_ERR_UNSUPPORTED, "states_filter: n_cols = " + std::to_string(n_cols) + " is above " +
+                                             std::to_string(ICV_FILTER_MAX_WINDOWS) + " (the int64 sum of a run)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return ICV_OK;
+    const int64_t blocks = (n_rows + icv::kFiRowsPerBlock - 1) / icv::kFiRowsPerBlock;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "states_filter: too many rows for one call");
+    AsyncBuf mask;
+    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
+    hipLaunchKernelGGL(icv::k_states_filter, dim3((unsigned)blocks), dim3(64 * icv::kFiRowsPerBlock), 0, st, states,
+                       p_neutral, n_rows, n_cols, mask.as<uint32_t>(), max_p_normal, filtered, nonneutral, removed, bad);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }

@@ -1,0 +1,260 @@
+// tl.cnv_posteriors and tl.cnv_states_filter: the posterior probabilities of the three-state model of
+// tl.cnv_states by forward-backward along every chromosome, and the filter that resets to neutral every called segment
+// whose mean P(neutral) exceeds a threshold (R inferCNV's BayesMaxPNormal).  tests/_posterior_oracle.py restates both
+// contracts.
+//
+// Posteriors, float64 throughout, every operation one correctly rounded IEEE operation in the written order (the
+// library is built -ffp-contract=off):
+//   1. host scalars, passed as doubles: h = 1.0 / (2.0 sigma sigma), ps = 1.0 - p, pw = p / 2.0 (a normal float64);
+//      A(r, s) = ps for r = s and pw otherwise.
+//   2. emissions: t = x - mu_s, e_s = -(t t) h (rule 2 of 4.13); m = max(e_0, e_1, e_2); b(s) = exp_(e_s - m) with the
+//      written exponential ts_exp of icv_tsne.hpp.  The largest b is exactly 1.0.
+//   3. forward: u_0(s) = b_0(s); for t >= 1 pred(s) = ((al(0) A(0,s)) + (al(1) A(1,s))) + (al(2) A(2,s)) over al_{t-1}
+//      and u_t(s) = pred(s) b_t(s); c_t = (u(0) + u(1)) + u(2), al_t(s) = u_t(s) / c_t.
+//   4. backward: be_{T-1}(s) = 1.0; g(s) = b_{t+1}(s) be_{t+1}(s), v(r) = ((A(r,0) g(0)) + (A(r,1) g(1))) + (A(r,2) g(2)),
+//      be_t(r) = v(r) / c_{t+1}.
+//   5. w(s) = al_t(s) be_t(s), z = (w(0) + w(1)) + w(2), gamma_t(s) = w(s) / z.
+//   6. chains never cross a chromosome boundary; an entry that is not stored is 0.0.
+//
+// Geometry: that of k_states_viterbi, one wavefront (a 64-thread workgroup) per cell, lane c running the chromosomes
+// c, c + 64, ... sequentially.  LDS holds the row as W doubles and three planes of W doubles: the forward pass leaves
+// al_t there, the backward pass reads al_t, recomputes b_{t+1} and c_{t+1} (the same operations on the same operands,
+// hence the same bits) and overwrites al_t with gamma_t; the planes then leave in coalesced 8-byte stores.  32 bytes of
+// LDS per window and resident cell.
+//
+// Filter, integers after one rounding per window:
+//   1. q_t = int64(rint(P[i,t] 2^40)).
+//   2. a run [s, e) (rule 1 of 4.14) has S = the int64 sum of its q_t and mean = double(S) / (double(e - s) 2^40).
+//   3. the run is reset to 0 iff mean > max_p_normal.
+// Geometry: one wavefront per row, four rows per workgroup, one window per lane and step of 64 windows.  A wavefront
+// prefix sum of q plus the ballots of the run starts and ends give every run's sum at its last window; the carry of a
+// run that is open at the end of a step is one (start, sum) pair.  A window of a run is written when the run's end has
+// been seen: by its own lane if that is in the same step, by the whole wavefront otherwise.  Every output byte is
+// written exactly once; no row is held in LDS.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "icv_segments.hpp"  // kSegMaskShift, k_seg_chr_mask
+#include "icv_tsne.hpp"      // ts_exp
+
+namespace icv {
+
+constexpr int kPoMaxWindows = 4096;  // = ICV_POSTERIOR_MAX_WINDOWS: 32 x 4096 = 128 KiB of the CU's 160 KiB
+constexpr int kPoLdsPerWindow = 32;  // the float64 value + three float64 planes
+constexpr int kFiRowsPerBlock = 4;   // wavefronts (rows) per workgroup of k_states_filter
+constexpr int kFiMaxWindows = 1 << 22;  // 2^22 terms of at most 2^40 fit an int64
+
+inline size_t po_lds_bytes(int32_t n_windows) { return (size_t)n_windows * kPoLdsPerWindow; }
+
+struct PoParams {
+    double a, h, ps, pw;
+};
+
+// rule 2 for the three states
+__device__ __forceinline__ void po_emit(double x, const PoParams& P, double& b0, double& b1, double& b2) {
+    const double t0 = x - (-P.a), t1 = x - 0.0, t2 = x - P.a;
+    const double e0 = -(t0 * t0) * P.h, e1 = -(t1 * t1) * P.h, e2 = -(t2 * t2) * P.h;
+    double m = e0;
+    if (e1 > m) m = e1;
+    if (e2 > m) m = e2;
+    b0 = ts_exp(e0 - m);
+    b1 = ts_exp(e1 - m);
+    b2 = ts_exp(e2 - m);
+}
+
+// pred of rule 3 from al_{t-1}
+__device__ __forceinline__ void po_pred(double a0, double a1, double a2, const PoParams& P, double& p0, double& p1,
+                                        double& p2) {
+    p0 = ((a0 * P.ps) + (a1 * P.pw)) + (a2 * P.pw);
+    p1 = ((a0 * P.pw) + (a1 * P.ps)) + (a2 * P.pw);
+    p2 = ((a0 * P.pw) + (a1 * P.pw)) + (a2 * P.ps);
+}
+
+// chr_start: C + 1 ascending window numbers, chr_start[0] = 0, chr_start[C] = W (the host checked them; they are clamped
+// to [0, W] here all the same, so no LDS access leaves the row).  neutral: n x W; loss / gain: n x W or both null.
+template <typename T, bool CSR>
+__global__ __launch_bounds__(64) void k_posterior_chains(const T* __restrict__ val, const int64_t* __restrict__ indptr,
+                                                         const int32_t* __restrict__ indices, int64_t ld, int32_t W,
+                                                         const int32_t* __restrict__ chr_start, int32_t C, PoParams P,
+                                                         double* __restrict__ neutral, double* __restrict__ loss,
+                                                         double* __restrict__ gain) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char po_lds[];
+    double* x = reinterpret_cast<double*>(po_lds);
+    double* g0 = x + W;       // al_t(0), then gamma_t(0)
+    double* g1 = x + 2 * (size_t)W;
+    double* g2 = x + 3 * (size_t)W;
+    const int lane = threadIdx.x;
+    const int64_t row = blockIdx.x;
+
+    // (a window no chromosome covers is neutral)
+    for (int32_t j = lane; j < W; j += 64) g0[j] = 0.0, g1[j] = 1.0, g2[j] = 0.0;
+    if (CSR) {
+        for (int32_t j = lane; j < W; j += 64) x[j] = 0.0;
+        __syncthreads();
+        const int64_t b = indptr[row], e = indptr[row + 1];
+        for (int64_t k = b + lane; k < e; k += 64) {
+            const int32_t c = indices[k];
+            if ((uint32_t)c < (uint32_t)W) x[c] = (double)val[k];
+        }
+    } else {
+        const T* src = val + row * ld;
+        for (int32_t j = lane; j < W; j += 64) x[j] = (double)src[j];
+    }
+    __syncthreads();
+
+    for (int32_t c = lane; c < C; c += 64) {
+        const int32_t s0 = min(max(chr_start[c], 0), W), s1 = min(max(chr_start[c + 1], 0), W);
+        if (s1 <= s0) continue;
+        double b0, b1, b2, a0, a1, a2;
+        // rule 3
+        po_emit(x[s0], P, b0, b1, b2);
+        {
+            const double cc = (b0 + b1) + b2;
+            a0 = b0 / cc, a1 = b1 / cc, a2 = b2 / cc;
+        }
+        g0[s0] = a0, g1[s0] = a1, g2[s0] = a2;
+        for (int32_t t = s0 + 1; t < s1; ++t) {
+            double p0, p1, p2;
+            po_emit(x[t], P, b0, b1, b2);
+            po_pred(a0, a1, a2, P, p0, p1, p2);
+            const double u0 = p0 * b0, u1 = p1 * b1, u2 = p2 * b2;
+            const double cc = (u0 + u1) + u2;
+            a0 = u0 / cc, a1 = u1 / cc, a2 = u2 / cc;
+            g0[t] = a0, g1[t] = a1, g2[t] = a2;
+        }
+        // rules 4-5: (a0, a1, a2) = al_{T-1}; (b0, b1, b2) = b_{t+1} from the second step on
+        double be0 = 1.0, be1 = 1.0, be2 = 1.0;
+        for (int32_t t = s1 - 1;; --t) {
+            const double w0 = a0 * be0, w1 = a1 * be1, w2 = a2 * be2;
+            const double z = (w0 + w1) + w2;
+            g0[t] = w0 / z, g1[t] = w1 / z, g2[t] = w2 / z;
+            if (t == s0) break;
+            po_emit(x[t], P, b0, b1, b2);  // b_t: the window the step t - 1 looks ahead to
+            a0 = g0[t - 1], a1 = g1[t - 1], a2 = g2[t - 1];
+            double p0, p1, p2;
+            po_pred(a0, a1, a2, P, p0, p1, p2);
+            const double cc = ((p0 * b0) + (p1 * b1)) + (p2 * b2);  // c_t, as the forward pass formed it
+            const double q0 = b0 * be0, q1 = b1 * be1, q2 = b2 * be2;
+            const double v0 = ((P.ps * q0) + (P.pw * q1)) + (P.pw * q2);
+            const double v1 = ((P.pw * q0) + (P.ps * q1)) + (P.pw * q2);
+            const double v2 = ((P.pw * q0) + (P.pw * q1)) + (P.ps * q2);
+            be0 = v0 / cc, be1 = v1 / cc, be2 = v2 / cc;
+        }
+    }
+    __syncthreads();
+
+    double* out = neutral + row * (int64_t)W;
+    for (int32_t j = lane; j < W; j += 64) out[j] = g1[j];
+    if (loss != nullptr && gain != nullptr) {
+        double* ol = loss + row * (int64_t)W;
+        double* og = gain + row * (int64_t)W;
+        for (int32_t j = lane; j < W; j += 64) ol[j] = g0[j], og[j] = g2[j];
+    }
+}
+
+// ---- the filter -------------------------------------------------------------------------------------------------------
+// S, P, out: n_rows x W row-major without padding; mask: the chromosome-start bits of k_seg_chr_mask (bit kSegMaskShift + t
+// is window t; seg_mask_words(W) words).  nonneutral[row] = the windows of out's row that are not 0, removed[row] = the
+// runs that were reset.  *bad |= 1 where a state is not -1 / 0 / +1 or a posterior is not a number in [0, 1] (such a
+// posterior counts as 0).  W <= kFiMaxWindows.
+__global__ __launch_bounds__(64 * kFiRowsPerBlock) void k_states_filter(
+    const int8_t* __restrict__ S, const double* __restrict__ Pn, int64_t n_rows, int32_t W,
+    const uint32_t* __restrict__ mask, double thr, int8_t* __restrict__ out, int32_t* __restrict__ nonneutral,
+    int32_t* __restrict__ removed, int32_t* __restrict__ bad) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * kFiRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= n_rows) return;  // (whole wavefronts leave; there is no barrier below)
+    const int8_t* s_row = S + row * (int64_t)W;
+    const double* p_row = Pn + row * (int64_t)W;
+    int8_t* o_row = out + row * (int64_t)W;
+
+    int32_t carry_state = 0;   // the state of the window in front of this step
+    int32_t open_start = 0;    // the first window of the run that was open at the end of the step before
+    int64_t open_sum = 0;      // its sum so far
+    int32_t kept = 0, gone = 0;
+    bool invalid = false;
+
+    for (int32_t v0 = 0; v0 < W; v0 += 64) {
+        const int32_t t = v0 + lane;
+        const bool in = t < W;
+        const int s = in ? (int)s_row[t] : 0;
+        const double pv = in ? p_row[t] : 0.0;
+        const bool p_ok = pv >= 0.0 && pv <= 1.0;  // (false for NaN)
+        invalid |= s < -1 || s > 1 || !p_ok;
+        int prev = __shfl_up(s, 1, 64);
+        if (lane == 0) prev = carry_state;
+        int next = __shfl_down(s, 1, 64);
+        if (lane == 63) next = (t + 1 < W) ? (int)s_row[t + 1] : 0;
+        carry_state = __shfl(s, 63, 64);
+
+        // is window t / t + 1 a chromosome start?  (bit kSegMaskShift + W is never set; the mask has the word)
+        const uint32_t qb = (uint32_t)(in ? t : 0) + kSegMaskShift;
+        const bool cs0 = (mask[qb >> 5] >> (qb & 31)) & 1u;
+        const bool cs1 = (mask[(qb + 1) >> 5] >> ((qb + 1) & 31)) & 1u;
+        const bool sf = s != 0 && (cs0 || prev != s);
+        const bool ef = s != 0 && (cs1 || next != s);  // (t + 1 == W: next = 0)
+
+        const int64_t q = (s != 0 && p_ok) ? (int64_t)rint(pv * 1099511627776.0) : 0;
+        int64_t incl = q;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int64_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        const int64_t excl = incl - q;
+        const uint64_t smask = __ballot(sf), emask = __ballot(ef);
+
+        // the lane of this window's run start (-1: the run was open when the step began) and of its end (64: it stays open)
+        const uint64_t below = smask & (~0ull >> (63 - lane));
+        const int sl = below ? 63 - __builtin_clzll(below) : -1;
+        const uint64_t above = emask >> lane;
+        const int el = above ? lane + __builtin_ctzll(above) : 64;
+        const int64_t excl_at_start = __shfl(excl, sl < 0 ? 0 : sl, 64);
+
+        // the verdict, formed at the run's last window
+        bool reset = false;
+        if (ef) {
+            const int64_t sum = sl >= 0 ? incl - excl_at_start : open_sum + incl;
+            const int32_t first = sl >= 0 ? v0 + sl : open_start;
+            const int32_t len = t + 1 - first;
+            const double mean = (double)sum / ((double)len * 1099511627776.0);
+            reset = mean > thr;
+            if (reset) ++gone;
+            else kept += len;
+        }
+        const bool my_reset = __shfl((int)reset, el & 63, 64) != 0;
+        if (in) {
+            if (s == 0) o_row[t] = 0;
+            else if (el < 64) o_row[t] = my_reset ? (int8_t)0 : (int8_t)s;
+        }
+        // the windows of the steps before that belong to a run ending in this step (the run of lane 0, if it was open)
+        const int s_first = __shfl(s, 0, 64);
+        const bool first_open = __shfl((int)(sl < 0 && s != 0 && el < 64), 0, 64) != 0;
+        if (first_open) {
+            const int8_t v = __shfl((int)my_reset, 0, 64) != 0 ? (int8_t)0 : (int8_t)s_first;
+            for (int32_t k = open_start + lane; k < v0; k += 64) o_row[k] = v;
+        }
+        // the run that stays open: lane 63's, if it has not ended
+        const bool stays = __shfl((int)(s != 0 && el == 64), 63, 64) != 0;
+        if (stays) {
+            const int sl63 = __shfl(sl, 63, 64);
+            const int64_t total = __shfl(incl, 63, 64);
+            if (sl63 >= 0) {
+                open_start = v0 + sl63;
+                open_sum = total - __shfl(excl, sl63, 64);
+            } else {
+                open_sum += total;
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        kept += __shfl_down(kept, off, 64);
+        gone += __shfl_down(gone, off, 64);
+    }
+    if (lane == 0) nonneutral[row] = kept, removed[row] = gone;
+    if (__ballot(invalid) != 0 && lane == 0) atomicOr(bad, 1);
+}
+
+}  // namespace icv
