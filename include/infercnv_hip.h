@@ -689,6 +689,18 @@ int icv_states_filter(const int8_t *states, const double *p_neutral, int64_t n_r
                       const int32_t *chr_start, int32_t n_chr, double max_p_normal, int8_t *filtered, int32_t *nonneutral,
                       int32_t *removed, int32_t *bad, void *stream);
 
+/* ---- tl.cnv_states_fit: the E-step of the Baum-Welch fit of the model of tl.cnv_states ----------------------
+ * icv_posterior_stats: forward-backward exactly as icv_posterior_chains (the same arguments, rules and bits of b, al_t,
+ * c_t, be_t, z_t and gamma_t), reduced per row to stats[i] = (G, D, K) (device float64, n_rows x 3).  Per chromosome three
+ * sums start at 0.0 and take their terms for t = T-1 down to 0: G += (gamma_t(0) + gamma_t(2));
+ * D += (gamma_t(2) - gamma_t(0)) x_t; for t <= T-2, K += (st / c_{t+1}) / z_t with m(s) = (al_t(s) ps) g(s),
+ * g = b_{t+1} be_{t+1} and st = (m(0) + m(1)) + m(2).  The row's G, D and K start at 0.0 and add the chromosome sums in
+ * ascending chromosome order.  Float64, no fused multiply-add, no atomics: a pure function of the arguments.  One
+ * wavefront per row, 32 bytes of LDS per window: 1 <= n_cols <= ICV_POSTERIOR_MAX_WINDOWS (ICV_ERR_INVALID beyond).  No
+ * synchronisation. */
+int icv_posterior_stats(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, double amplitude, double h, double ps,
+                        double pw, double *stats, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -1928,6 +1928,23 @@ def posterior_chains(dm: DeviceMatrix, chr_start, *, amplitude, h, ps, pw, all_s
     return neutral, loss, gain
 
 
+def posterior_stats(dm: DeviceMatrix, chr_start, *, amplitude, h, ps, pw):
+    """Device float64 ``n x 3``: per cell the sums (G, D, K) of DESIGN.md 4.16, the E-step of ``tl.cnv_states_fit``.
+    ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The launch is enqueued on the current
+    stream; nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    n = dm.shape[0]
+    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
+    with torch.cuda.device(dm.device):
+        cs = torch.from_numpy(chr_start).cuda()
+        stats = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+        m = dm.c_struct()
+        _lib.check(lib.icv_posterior_stats(C.byref(m), _ptr(cs), int(chr_start.shape[0]) - 1, float(amplitude), float(h),
+                                           float(ps), float(pw), _ptr(stats), _stream_ptr(torch)))
+    return stats
+
+
 def states_filter(states, p_neutral, chr_start, max_p_normal):
     """(filtered int8 n x W, nonneutral int32 n, removed int32 n, bad int32 flag), device tensors: the calls of
     ``states`` (device int8) with every run whose mean ``p_neutral`` (device float64) is above ``max_p_normal`` reset to

@@ -43,6 +43,7 @@
 #include "icv_tsne.hpp"
 #include "icv_states.hpp"
 #include "icv_segments.hpp"
+#include "icv_hmmfit.hpp"
 #include "icv_posterior.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
@@ -4281,6 +4282,47 @@ int icv_states_filter(const int8_t* states, const double* p_neutral, int64_t n_r
     ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
     hipLaunchKernelGGL(icv::k_states_filter, dim3((unsigned)blocks), dim3(64 * icv::kFiRowsPerBlock), 0, st, states,
                        p_neutral, n_rows, n_cols, mask.as<uint32_t>(), max_p_normal, filtered, nonneutral, removed, bad);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+
+// ---- tl.cnv_states_fit: the E-step of the Baum-Welch fit ----------------------------------------------------
+int icv_posterior_stats(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, double amplitude, double h, double ps,
+                        double pw, double* stats, void* stream) {
+    if (!m || !chr_start || !stats || n_chr < 1 || m->n_rows < 0 || (m->dtype != ICV_F32 && m->dtype != ICV_F64) ||
+        (m->format != ICV_DENSE && m->format != ICV_CSR))
+        return fail(ICV_ERR_INVALID, "bad posterior_stats arguments");
+    if (m->n_cols < 1 || m->n_cols > ICV_POSTERIOR_MAX_WINDOWS)
+        return fail(ICV_ERR_INVALID, "posterior_stats: n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
+                                         std::to_string(ICV_POSTERIOR_MAX_WINDOWS) + "] (32 bytes of LDS per window)");
+    if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, "posterior_stats: more chromosomes than windows");
+    if (!(std::isfinite(amplitude) && amplitude > 0.0 && std::isfinite(h) && h > 0.0 && std::isnormal(pw) && pw > 0.0 &&
+          ps > 0.0 && ps < 1.0 && pw < 0.5))
+        return fail(ICV_ERR_INVALID, "posterior_stats: amplitude and h must be finite and > 0, ps = 1 - p and pw = p / 2 "
+                                     "for a p in (0, 1) with pw a normal float64");
+    if (m->format == ICV_DENSE ? (m->ld < m->n_cols || !m->values) : !m->indptr)
+        return fail(ICV_ERR_INVALID, "posterior_stats: incomplete matrix");
+    if (m->n_rows == 0) return ICV_OK;
+    if (m->n_rows > 0x7fffffffLL) return fail(ICV_ERR_UNSUPPORTED, "posterior_stats: more than 2^31 - 1 rows in one call");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = icv::po_lds_bytes(m->n_cols);
+    const icv::PoParams P{amplitude, h, ps, pw};
+    const dim3 grid((unsigned)m->n_rows), block(64);
+#define ICV_POSTERIOR_STATS(T, CSR)                                                                                    \
+    {                                                                                                                  \
+        auto kern = icv::k_posterior_stats<T, CSR>;                                                                    \
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                    (int)lds));                                                                        \
+        hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)m->values, m->indptr, m->indices, m->ld, m->n_cols,   \
+                           chr_start, n_chr, P, stats);                                                                \
+    }
+    if (m->format == ICV_CSR) {
+        if (m->dtype == ICV_F32) ICV_POSTERIOR_STATS(float, true) else ICV_POSTERIOR_STATS(double, true)
+    } else {
+        if (m->dtype == ICV_F32) ICV_POSTERIOR_STATS(float, false) else ICV_POSTERIOR_STATS(double, false)
+    }
+#undef ICV_POSTERIOR_STATS
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
