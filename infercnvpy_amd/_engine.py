@@ -1878,6 +1878,31 @@ def states_rowsq(dm: DeviceMatrix):
     return q, flag
 
 
+def states_absmax(values):
+    """Device float64 tensor of one element: the largest ``|v|`` of a CUDA tensor of values (0.0 for an empty one, NaN
+    where one is NaN), the ``m`` of DESIGN.md 4.13 rule 6.  Two reductions that allocate nothing of the tensor's size;
+    nothing is read back."""
+    torch = _torch()
+    with torch.cuda.device(values.device):
+        if values.numel() == 0:
+            return torch.zeros(1, dtype=torch.float64, device="cuda")
+        lo, hi = torch.aminmax(values)
+        return torch.maximum(-lo, hi).to(torch.float64).reshape(1)
+
+
+def states_stored_values(dm: DeviceMatrix):
+    """The CUDA tensor that holds the stored values of ``dm``: the dense matrix, or the whole data buffer of a CSR one."""
+    return dm.dense if dm.format == _lib.ICV_DENSE else dm.data
+
+
+def states_flag_and_absmax(flag, absmax):
+    """(non-finite flag as a bool, largest |v| as a float) of :func:`states_rowsq` and :func:`states_absmax`: the two
+    device scalars in one copy to the host (the one synchronisation the flag needs anyway)."""
+    torch = _torch()
+    both = torch.cat([flag.to(torch.float64).reshape(1), absmax]).cpu().tolist()
+    return bool(both[0]), float(both[1])
+
+
 def states_viterbi(dm: DeviceMatrix, chr_start, *, amplitude, h, stay, sw):
     """(states, nonneutral): device int8 ``n x W`` of -1 / 0 / +1 and device int32 counts of the windows that are not 0
     (DESIGN.md 4.13 rules 2-5).  ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The

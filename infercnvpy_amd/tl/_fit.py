@@ -16,7 +16,7 @@ import time
 import warnings
 
 from .. import _engine, _lib
-from ._states import _positive, chromosome_bounds
+from ._states import _positive, check_emissions, chromosome_bounds
 
 _NAMES = ("amplitude", "sigma", "switch_prob")
 _P_MIN, _P_MAX = 1e-9, 0.5
@@ -95,7 +95,9 @@ def cnv_states_fit(adata, use_rep="cnv", key_added="cnv_states_fit", inplace=Tru
     None when ``inplace`` or else the params dict, followed by the info dict when ``return_info``.  A step that would
     leave a variance that is not finite and > 0 (every stored value sits exactly on a mean) ends the fit with the
     parameters of the iteration before, ``converged=False`` and a ``RuntimeWarning``.  Each iteration reads n x 3 float64
-    sums back; nothing of size n x W is allocated.  A non-finite value raises ``ValueError``.
+    sums back; nothing of size n x W is allocated.  A non-finite value raises ``ValueError``, and so does a finite one
+    whose emission overflows under the start values: ``(|x| + amplitude)^2 / (2 sigma^2)`` must be finite for the stored
+    value of the largest magnitude.
     """
     key = f"X_{use_rep}"
     if key not in adata.obsm:
@@ -147,8 +149,10 @@ def cnv_states_fit(adata, use_rep="cnv", key_added="cnv_states_fit", inplace=Tru
     dm = _engine.states_input(x)
     t0 = time.perf_counter()
     q, flag = _engine.states_rowsq(dm)
+    absmax = _engine.states_absmax(_engine.states_stored_values(dm))
     q_host = q.cpu().numpy()
-    if int(flag.item()):
+    nonfinite, m = _engine.states_flag_and_absmax(flag, absmax)
+    if nonfinite:
         raise ValueError(f"tl.cnv_states_fit: {key} has non-finite values")
     try:
         qs = math.fsum(q_host.tolist())
@@ -171,6 +175,7 @@ def cnv_states_fit(adata, use_rep="cnv", key_added="cnv_states_fit", inplace=Tru
         if not (math.isfinite(h) and h > 0.0 and math.isfinite(amp) and amp > 0.0):
             raise ValueError(f"tl.cnv_states_fit: sigma={sig!r} / amplitude={amp!r} leave float64's range "
                              "(1 / (2 sigma^2) must be finite and > 0)")
+        check_emissions("tl.cnv_states_fit", key, x, m, amp, h, sig)  # (later steps end as degenerate ones)
         n_steps = n * sum(max(int(b) - int(a) - 1, 0) for a, b in zip(bounds[:-1], bounds[1:]))
         for _ in range(max_iter):
             a_, s_, p_ = cur

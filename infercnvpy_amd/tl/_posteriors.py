@@ -16,7 +16,7 @@ import time
 import numpy as np
 
 from .. import _engine, _lib
-from ._states import chromosome_bounds
+from ._states import check_emissions, chromosome_bounds
 
 
 def _positive(name, value):
@@ -69,7 +69,9 @@ def cnv_posteriors(adata, use_rep="cnv", key_added="cnv_posterior", inplace=True
     None when ``inplace`` (and not ``return_info``); else ``neutral`` or, with ``all_states``,
     ``(loss, neutral, gain)``, followed by the info dict when ``return_info``.  Host input gives host numpy arrays;
     device input (``PackedCsr``, CUDA tensor) leaves CUDA float64 tensors and nothing is read back after the
-    non-finite flag.  A non-finite value raises ``ValueError``.
+    non-finite flag.  A non-finite value raises ``ValueError``, and so does a finite one whose emission overflows:
+    ``(|x| + amplitude)^2 / (2 sigma^2)`` must be finite for the stored value of the largest magnitude (read back with
+    the flag); the posteriors of its chromosome would be 0 / 0 otherwise.
     """
     key = f"X_{use_rep}"
     if key not in adata.obsm:
@@ -114,9 +116,11 @@ def cnv_posteriors(adata, use_rep="cnv", key_added="cnv_posterior", inplace=True
     dm = _engine.states_input(x)
     t0 = time.perf_counter()
     q, flag = _engine.states_rowsq(dm)
+    absmax = _engine.states_absmax(_engine.states_stored_values(dm))
     if sig is None:
         q_host = q.cpu().numpy()
-    if int(flag.item()):
+    nonfinite, m = _engine.states_flag_and_absmax(flag, absmax)
+    if nonfinite:
         raise ValueError(f"tl.cnv_posteriors: {key} has non-finite values")
     if sig is None:
         try:
@@ -138,6 +142,7 @@ def cnv_posteriors(adata, use_rep="cnv", key_added="cnv_posterior", inplace=True
             if not (math.isfinite(h) and h > 0.0 and math.isfinite(amp) and amp > 0.0):
                 raise ValueError(f"tl.cnv_posteriors: sigma={sig!r} / amplitude={amp!r} leave float64's range "
                                  "(1 / (2 sigma^2) must be finite and > 0)")
+            check_emissions("tl.cnv_posteriors", key, x, m, amp, h, sig)
             neutral, loss, gain = _engine.posterior_chains(dm, bounds, amplitude=amp, h=h, ps=ps, pw=pw,
                                                            all_states=all_states)
         info = None

@@ -55,6 +55,30 @@ def _positive(name, value):
     return v
 
 
+def check_emissions(who, key, x, m, amp, h, sig):
+    """Rule 6 of DESIGN.md 4.13: ``ValueError`` when the emission of the stored value of the largest magnitude overflows.
+
+    ``m`` is that magnitude, ``t = m + amp``; the state ``-amp`` forms this ``t`` for a positive value and the state
+    ``+amp`` for a negative one, and no other ``t`` of the matrix is larger, so every emission ``-(t t) h`` is finite
+    exactly when ``(t t) h`` is.  Without the check all three emissions of such a window are ``-inf``: the posteriors of
+    its chromosome become 0 / 0 and the Viterbi chain calls it neutral.  The ``m`` of a ``PackedCsr`` covers the unused
+    tail of its buffers; only where that fails the rule (or is NaN) are the stored entries looked at alone, which reads
+    their number back."""
+    def overflows(v):
+        t = v + amp
+        return not math.isfinite((t * t) * h)
+
+    if not overflows(m):
+        return
+    if isinstance(x, _engine.PackedCsr):
+        m = float(_engine.states_absmax(x.data[:x.nnz()]).item())
+        if not overflows(m):
+            return
+    raise ValueError(f"{who}: sigma={sig!r} and amplitude={amp!r} overflow float64 on the value of magnitude {m!r} in "
+                     f"{key}: (|x| + amplitude)^2 / (2 sigma^2) is not finite, so no state could be told from another; "
+                     "rescale the matrix or clip the value")
+
+
 def cnv_states(adata, use_rep="cnv", key_added="cnv_states", inplace=True, *, amplitude=None, sigma=None,
                switch_prob=1e-3, return_info=False):
     """Call every window of every cell lost (-1), neutral (0) or gained (+1).
@@ -95,7 +119,9 @@ def cnv_states(adata, use_rep="cnv", key_added="cnv_states", inplace=True, *, am
     ``return_info``.  Host input gives host numpy arrays.  Device input (``PackedCsr``, CUDA tensor) leaves ``states`` on
     the device as a CUDA int8 tensor; with ``inplace=False`` the fraction is a CUDA float64 tensor as well and the call
     returns without waiting for the chains, while ``inplace=True`` copies the n counts back for ``adata.obs``.  A
-    non-finite value raises ``ValueError`` (one flag read back from the device before the chains are launched).
+    non-finite value raises ``ValueError`` (one flag read back from the device before the chains are launched), and so
+    does a finite one so large that its emission overflows: ``(|x| + amplitude)^2 / (2 sigma^2)`` must be finite for the
+    stored value of the largest magnitude, which is read back with the flag.
     """
     key = f"X_{use_rep}"
     if key not in adata.obsm:
@@ -129,9 +155,11 @@ def cnv_states(adata, use_rep="cnv", key_added="cnv_states", inplace=True, *, am
     dm = _engine.states_input(x)
     t0 = time.perf_counter()
     q, flag = _engine.states_rowsq(dm)
+    absmax = _engine.states_absmax(_engine.states_stored_values(dm))
     if sig is None:
         q_host = q.cpu().numpy()
-    if int(flag.item()):
+    nonfinite, m = _engine.states_flag_and_absmax(flag, absmax)
+    if nonfinite:
         raise ValueError(f"tl.cnv_states: {key} has non-finite values")
     if sig is None:
         try:
@@ -152,6 +180,7 @@ def cnv_states(adata, use_rep="cnv", key_added="cnv_states", inplace=True, *, am
             if not (math.isfinite(h) and h > 0.0 and math.isfinite(amp) and amp > 0.0):
                 raise ValueError(f"tl.cnv_states: sigma={sig!r} / amplitude={amp!r} leave float64's range "
                                  "(1 / (2 sigma^2) must be finite and > 0)")
+            check_emissions("tl.cnv_states", key, x, m, amp, h, sig)
             states, count = _engine.states_viterbi(dm, bounds, amplitude=amp, h=h, stay=stay, sw=sw)
         info = None
         if return_info:

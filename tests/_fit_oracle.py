@@ -24,6 +24,8 @@ M-step, in Python floats.  ``Gs = fsum(G_i)``, ``Ds``, ``Ks`` likewise, ``Qs = f
 A step whose ``var`` is not finite or not ``> 0`` (or whose ``a'`` or ``1 / (2 sigma' sigma')`` is not finite) is
 degenerate: the fit stops with the parameters of the iteration before.  ``delta`` is the largest ``|new - old| / old``
 over the fitted parameters; ``delta <= tol`` ends the loop converged.
+
+Start values whose emission overflows (rule 6 of ``_states_oracle``) are a ``ValueError``.
 """
 import math
 
@@ -82,14 +84,15 @@ def chain_stats(xs, a, h, ps, pw):
     return G, D, K
 
 
-def stats(x, chr_pos, a, sigma, p):
-    """The n x 3 float64 array of (G, D, K) per cell."""
+def stats(x, chr_pos, a, sigma, p, bounds=None):
+    """The n x 3 float64 array of (G, D, K) per cell; ``bounds=`` takes the kernel's own ``chr_start`` array in place of
+    ``chr_pos`` (a chromosome with ``s1 <= s0`` adds nothing, nor does a window that no chromosome covers)."""
     x = so.canonical(x)
     n, w = x.shape
     h, ps, pw = po.scalars(float(sigma), float(p))
     dense = x.toarray()
     out = np.zeros((n, 3), dtype=np.float64)
-    edges = so.bounds(chr_pos, w)
+    edges = [int(v) for v in bounds] if bounds is not None else so.bounds(chr_pos, w)
     with np.errstate(all="ignore"):
         for s0, s1 in zip(edges[:-1], edges[1:]):
             if s1 <= s0:
@@ -148,6 +151,7 @@ def cnv_states_fit(x, chr_pos, amplitude=None, sigma=None, switch_prob=None, fit
     out = {"params": _dict(*cur), "history": [_dict(*cur)], "n_iter": 0, "converged": False, "fit": fit}
     if cur[1] == 0.0:
         return out
+    so.check_emissions(x, cur[0], cur[1], "cnv_states_fit")  # the start values; later steps end as degenerate ones
     Qs, N, NT = math.fsum(q), float(n) * float(w), steps(chr_pos, n, w)
     for _ in range(max_iter):
         s = stats(x, chr_pos, *cur)

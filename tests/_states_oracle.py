@@ -13,9 +13,17 @@ windows and ``math.fsum``:
    the largest value, ties go to r = s first, then to the lower r.
 4. The last window takes the s with the largest d; ties go to neutral, then loss, then gain.  Then backtrack.
 5. Output = state - 1.  An entry that is not stored is 0.0; chains never cross a chromosome boundary.
+6. Overflow: with ``m`` the largest ``|v|`` over the stored values and ``t = m + a``, a ``(t t) h`` that is not finite is
+   a ``ValueError``: the state ``-a`` sees that ``t`` for a positive value and the state ``+a`` for a negative one, and
+   every other emission is smaller in magnitude, so all emissions are finite exactly when this one is.
+
+``bounds=`` takes the kernel's own ``chr_start`` array (C + 1 ascending window numbers inside [0, W]) in place of
+``chr_pos``: a chromosome with ``s1 <= s0`` is skipped, a window that no chromosome covers stays neutral.
 """
+import fractions
 import functools
 import math
+import random
 
 import numpy as np
 import scipy.sparse as sp
@@ -69,6 +77,42 @@ def bounds(chr_pos, n_windows):
     return starts + [int(n_windows)]
 
 
+_bounds_of = bounds  # (cnv_states has a keyword of that name)
+
+
+def check_emissions(x, amplitude, sigma, who="cnv_states"):
+    """rule 6 on a canonical CSR matrix."""
+    m = max((abs(v) for v in x.data.tolist()), default=0.0)
+    h = 1.0 / (2.0 * sigma * sigma)
+    t = m + amplitude
+    if not math.isfinite((t * t) * h):
+        raise ValueError(f"{who}: sigma={sigma!r} and amplitude={amplitude!r} overflow the emission of the value of "
+                         f"magnitude {m!r}")
+
+
+def overflow_case():
+    """(x, chr_pos, kwargs): one stored value of 1e160 under sigma = 0.1, amplitude = 0.2, where every emission of its
+    window is -inf."""
+    x = sp.csr_matrix(np.array([[0.0, 0.3, 1e160, -0.2, 0.0, 0.1]]))
+    return x, {"chr1": 0}, {"sigma": 0.1, "amplitude": 0.2}
+
+
+def largest_value_that_does_not_overflow(amplitude, sigma):
+    """The largest float64 m with ((m + a) (m + a)) h finite, by bisection on rule 6 itself."""
+    h = 1.0 / (2.0 * sigma * sigma)
+
+    def ok(m):
+        t = m + amplitude
+        return math.isfinite((t * t) * h)
+
+    lo, hi = 1.0, 1e160
+    assert ok(lo) and not ok(hi)
+    while math.nextafter(lo, math.inf) < hi:
+        mid = lo + (hi - lo) / 2.0
+        lo, hi = (mid, hi) if ok(mid) else (lo, mid)
+    return lo
+
+
 # ---- rules 2-4 -----------------------------------------------------------------------------------------------------------
 def emissions(x, a, h):
     """rule 2: (e_0, e_1, e_2) of one value."""
@@ -83,14 +127,49 @@ def transition(r, s, stay, sw):
     return stay if r == s else sw
 
 
-def viterbi_chain(xs, a, h, stay, sw):
-    """rules 3-4 on the values of one chromosome: the list of states (0 loss, 1 neutral, 2 gain)."""
-    d = emissions(xs[0], a, h)
+VARIANTS = ("assoc", "emul", "fma")  # deviations from rules 2-3 that a compiler or a rewrite could introduce
+
+
+def _emissions_emul(x, a, h):
+    """not rule 2: -(t (t h))."""
+    out = []
+    for mu in (-a, 0.0, a):
+        t = x - mu
+        out.append(-(t * (t * h)))
+    return out
+
+
+def _fma_add(best, x, mu, h):
+    """not rule 3: best + e with the product -(t t) h left unrounded (one fused multiply-add), exactly."""
+    t = x - mu
+    return float(fractions.Fraction(best) - fractions.Fraction(t * t) * fractions.Fraction(h))
+
+
+def viterbi_chain(xs, a, h, stay, sw, variant=None):
+    """rules 3-4 on the values of one chromosome: the list of states (0 loss, 1 neutral, 2 gain).
+
+    ``variant`` names a deviation that the tests show to be visible (never the contract): ``"assoc"`` adds
+    ``d(r) + (T + e)``, ``"emul"`` forms ``-(t (t h))``, ``"fma"`` fuses the product ``-(t t) h`` into the add."""
+    assert variant is None or variant in VARIANTS
+    emit = _emissions_emul if variant == "emul" else emissions
+    mus = (-a, 0.0, a)
+    d = emit(xs[0], a, h)
     back = []
     for x in xs[1:]:
-        e = emissions(x, a, h)
+        e = emit(x, a, h)
         nd, arg = [], []
         for s in range(3):
+            if variant == "assoc":
+                best, who = d[s] + (stay + e[s]), s
+                for r in range(3):
+                    if r == s:
+                        continue
+                    cand = d[r] + (sw + e[s])
+                    if cand > best:
+                        best, who = cand, r
+                nd.append(best)
+                arg.append(who)
+                continue
             best, who = d[s] + stay, s  # r = s first
             for r in range(3):  # then the others, the lower r first; only a strictly larger value replaces
                 if r == s:
@@ -98,7 +177,7 @@ def viterbi_chain(xs, a, h, stay, sw):
                 cand = d[r] + sw
                 if cand > best:
                     best, who = cand, r
-            nd.append(best + e[s])
+            nd.append(_fma_add(best, x, mus[s], h) if variant == "fma" else best + e[s])
             arg.append(who)
         d = nd
         back.append(arg)
@@ -123,8 +202,8 @@ def path_score(xs, path, a, h, stay, sw):
 
 
 # ---- the whole function ----------------------------------------------------------------------------------------------------
-def cnv_states(x, chr_pos, amplitude=None, sigma=None, switch_prob=1e-3):
-    """(states int8 n x W, fraction float64 n, params dict) of rules 1-5."""
+def cnv_states(x, chr_pos, amplitude=None, sigma=None, switch_prob=1e-3, bounds=None):
+    """(states int8 n x W, fraction float64 n, params dict) of rules 1-6."""
     x = canonical(x)
     n, w = x.shape
     if sigma is None:
@@ -137,16 +216,16 @@ def cnv_states(x, chr_pos, amplitude=None, sigma=None, switch_prob=1e-3):
         return out, np.zeros(n, dtype=np.float64), params
     h, stay, sw = scalars(float(sigma), float(switch_prob))
     a = float(amplitude)
-    edges = bounds(chr_pos, w)
+    check_emissions(x, a, float(sigma))
+    edges = [int(v) for v in bounds] if bounds is not None else _bounds_of(chr_pos, w)
     data, indices, indptr = x.data.tolist(), x.indices.tolist(), x.indptr.tolist()
     for i in range(n):
         row = [0.0] * w
         for k in range(indptr[i], indptr[i + 1]):
             row[indices[k]] = data[k]
-        calls = []
         for s0, s1 in zip(edges[:-1], edges[1:]):
-            calls.extend(viterbi_chain(row[s0:s1], a, h, stay, sw))
-        out[i] = np.asarray(calls, dtype=np.int8) - 1
+            if s1 > s0:
+                out[i, s0:s1] = np.asarray(viterbi_chain(row[s0:s1], a, h, stay, sw), dtype=np.int8) - 1
     count = (out != 0).sum(axis=1)
     return out, count.astype(np.float64) / float(w), params
 
@@ -219,6 +298,72 @@ def ties():
     return {"x": x, "chr_pos": chr_pos_of(TIES_LENGTHS), "kwargs": dict(TIES_KWARGS)}
 
 
+ROUNDING_LENGTHS = (2, 3, 6)
+ROUNDING_CHAINS = 400  # per length
+ROUNDING_ROWS = 4
+ROUNDING_SEED = 1
+ROUNDING_KWARGS = {"amplitude": 0.23, "sigma": 0.1, "switch_prob": 1e-3}  # nothing dyadic: every operation rounds
+
+
+def rounding_ties(seed=ROUNDING_SEED):
+    """Chains in which the last bit of the sums decides the call.  A chain of L windows has L - 1 values
+    ``a / 2 + N(0, sigma / 2)`` and a last value of ``L a / 2`` minus their sum: in exact arithmetic the all-neutral and
+    the all-gain path score the same.  400 chains of each L in (2, 3, 6), 100 of each per row (300 chromosomes a row:
+    the lanes take several each); the odd rows are mirrored (-x), where loss takes the place of gain.
+    dict(x, chr_pos, kwargs, chains={L: [(row, first window)]})."""
+    rng = random.Random(seed)
+    a, sigma = ROUNDING_KWARGS["amplitude"], ROUNDING_KWARGS["sigma"]
+    per_row = ROUNDING_CHAINS // ROUNDING_ROWS
+    lengths = [L for L in ROUNDING_LENGTHS for _ in range(per_row)]
+    w = sum(lengths)
+    dense = np.zeros((ROUNDING_ROWS, w))
+    chains = {L: [] for L in ROUNDING_LENGTHS}
+    for i in range(ROUNDING_ROWS):
+        t = 0
+        for L in lengths:
+            xs = [a / 2 + rng.gauss(0.0, sigma / 2) for _ in range(L - 1)]
+            xs.append(L * a / 2 - sum(xs))
+            dense[i, t:t + L] = xs
+            chains[L].append((i, t))
+            t += L
+    dense[1::2] *= -1.0
+    return {"x": canonical(dense), "chr_pos": chr_pos_of(lengths), "kwargs": dict(ROUNDING_KWARGS), "chains": chains}
+
+
+def rounding_differences(c, variant):
+    """{L: the number of the case's chains of L windows whose calls under ``variant`` are not the contract's}."""
+    dense = c["x"].toarray()
+    kw = c["kwargs"]
+    h, stay, sw = scalars(kw["sigma"], kw["switch_prob"])
+    out = {}
+    for L, where in c["chains"].items():
+        n = 0
+        for i, t in where:
+            xs = dense[i, t:t + L].tolist()
+            n += viterbi_chain(xs, kw["amplitude"], h, stay, sw) != viterbi_chain(xs, kw["amplitude"], h, stay, sw, variant)
+        out[L] = n
+    return out
+
+
+SPLIT_WIDTHS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 63, 64, 65)
+SPLIT_ROWS = 9
+SPLIT_KWARGS = {"amplitude": TIES_A, "sigma": 0.25, "switch_prob": 0.3}
+
+
+def output_split(w):
+    """9 rows of w windows from {0, +a, -a}, the first and the last window never 0, under switch_prob = 0.3 (one switch
+    costs 1.54, a window on a state's mean is worth 2 over neutral): most calls are not 0, and rows follow each other
+    w bytes apart, so the int8 row's single-byte head, its 4-byte words and its tail take every split.
+    dict(x, chr_pos, kwargs)."""
+    rng = np.random.default_rng(1000 + w)
+    a = SPLIT_KWARGS["amplitude"]
+    dense = rng.choice([0.0, a, -a], size=(SPLIT_ROWS, w), p=[0.2, 0.4, 0.4])
+    dense[:, 0] = np.where(rng.random(SPLIT_ROWS) < 0.5, a, -a)
+    dense[:, -1] = np.where(rng.random(SPLIT_ROWS) < 0.5, a, -a) if w > 1 else dense[:, 0]
+    lengths = [w] if w < 6 else [w // 2, 1, w - w // 2 - 1]
+    return {"x": canonical(dense), "chr_pos": chr_pos_of(lengths), "kwargs": dict(SPLIT_KWARGS)}
+
+
 def shapes():
     """Chromosome layouts at which the kernel takes another path: {name: case}."""
     rng = np.random.default_rng(11)
@@ -254,6 +399,10 @@ def case(name):
     """The named case with its expected output, computed once: dict(x, chr_pos, kwargs, states, fraction, params)."""
     if name == "ties":
         c = ties()
+    elif name == "rounding_ties":
+        c = rounding_ties()
+    elif name.startswith("output_split_"):
+        c = output_split(int(name[len("output_split_"):]))
     elif name == "planted777":
         c = planted(777, [40, 1, 25, 60], 0)
     elif name == "full_and_empty":

@@ -306,3 +306,24 @@ def test_missing_keys_and_bad_arguments_raise_before_anything_touches_a_device()
     with pytest.raises(KeyError, match="chr_pos not found"):
         cnv.tl.cnv_states_fit(ad)
     assert "cnv_states_fit" not in ad.uns
+
+
+def test_start_values_whose_emission_overflows_raise():
+    x, pos, kw = so.overflow_case()
+    with pytest.raises(ValueError, match="overflow"):
+        fo.cnv_states_fit(x, pos, **kw)
+    x.data[x.data == 1e160] = 1e154  # the sum of squares is finite, the emission is not
+    assert math.isfinite(math.fsum(so.rowsq(x)))
+    with pytest.raises(ValueError, match="overflow"):
+        fo.cnv_states_fit(x, pos, **kw)
+    x.data[x.data == 1e154] = so.largest_value_that_does_not_overflow(kw["amplitude"], kw["sigma"])
+    assert fo.cnv_states_fit(x, pos, max_iter=1, **kw)["n_iter"] == 1
+
+
+def test_stats_bounds_entry_point_adds_nothing_for_an_empty_chromosome():
+    c = so.planted(6, [10, 7, 13], 19)
+    want = fo.stats(c["x"], c["chr_pos"], 0.2, 0.1, 1e-3)
+    assert _bits(fo.stats(c["x"], None, 0.2, 0.1, 1e-3, bounds=[0, 10, 10, 17, 30])) == _bits(want)
+    part = fo.stats(c["x"], None, 0.2, 0.1, 1e-3, bounds=[3, 9, 28])
+    alone = fo.stats(c["x"][:, 3:28], {"a": 0, "b": 6}, 0.2, 0.1, 1e-3)
+    assert _bits(part) == _bits(alone)

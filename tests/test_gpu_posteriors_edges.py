@@ -1,0 +1,197 @@
+"""tl.cnv_posteriors and the E-step of tl.cnv_states_fit at the limits of k_posterior_chains / k_posterior_stats
+("limits pinned"): dense input with a leading dimension above W, chr_start layouts that only the
+C ABI reaches, the cutoff of the written exponential in float32 input, and the emission overflow check."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import _fit_oracle as fo
+import _posterior_oracle as po
+import _states_oracle as so
+
+pytestmark = pytest.mark.gpu
+
+PADS = (1, 64)
+PAD_VALUE = 1e30  # finite in float32 and float64: a kernel that reads the padding changes every result
+
+
+def _adata(x, chr_pos):
+    from infercnvpy_amd._compat import SimpleAnnData
+
+    ad = SimpleAnnData(np.zeros((x.shape[0], 2), dtype=np.float32))
+    ad.obsm["X_cnv"] = x
+    ad.uns["cnv"] = {"chr_pos": dict(chr_pos)}
+    return ad
+
+
+def _same(got, want, what):
+    got = got.cpu().numpy()
+    assert got.dtype == np.float64 and got.shape == want.shape, what
+    differ = int((got.view(np.uint64) != want.view(np.uint64)).sum())
+    print(f"{what}: {want.shape}, {differ} values differ from the oracle")
+    assert got.tobytes() == want.tobytes(), what
+
+
+def _padded(dense, pad, dtype):
+    import torch
+
+    from infercnvpy_amd import _engine
+
+    n, w = dense.shape
+    buf = torch.full((n, w + pad), PAD_VALUE, dtype=dtype, device="cuda")
+    buf[:, :w] = torch.from_numpy(dense).cuda().to(dtype)
+    dm = _engine.DeviceMatrix(dense=buf[:, :w])
+    assert dm.c_struct().ld == w + pad
+    return dm
+
+
+# ---- B: dense input whose rows are further apart than W -----------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_padded_dense_rows_equal_the_contiguous_matrix_and_the_oracle(dtype):
+    import torch
+
+    from infercnvpy_amd import _engine
+    from infercnvpy_amd.tl._states import chromosome_bounds
+
+    c = so.planted(13, [33, 1, 70, 7], 21)
+    dense = c["x"].toarray().astype(np.float32).astype(np.float64)  # float32 numbers: the same matrix in both types
+    w = dense.shape[1]
+    sigma, a, p = 0.1, 0.2, 1e-3
+    loss, neutral, gain, _ = po.cnv_posteriors(dense, c["chr_pos"], amplitude=a, sigma=sigma, switch_prob=p)
+    stats = fo.stats(dense, c["chr_pos"], a, sigma, p)
+    h, ps, pw = po.scalars(sigma, p)
+    bounds = chromosome_bounds(c["chr_pos"], w)
+    kw = dict(amplitude=a, h=h, ps=ps, pw=pw)
+    tdtype = getattr(torch, dtype)
+    plain = _engine.DeviceMatrix(dense=torch.from_numpy(dense).cuda().to(tdtype))
+    for dm, ld in [(plain, w)] + [(_padded(dense, pad, tdtype), w + pad) for pad in PADS]:
+        only, none_l, none_g = _engine.posterior_chains(dm, bounds, **kw)
+        assert none_l is None and none_g is None
+        _same(only, neutral, f"ld = {ld}: neutral alone")
+        n3, l3, g3 = _engine.posterior_chains(dm, bounds, all_states=True, **kw)
+        _same(n3, neutral, f"ld = {ld}: neutral")
+        _same(l3, loss, f"ld = {ld}: loss")
+        _same(g3, gain, f"ld = {ld}: gain")
+        _same(_engine.posterior_stats(dm, bounds, **kw), stats, f"ld = {ld}: statistics")
+
+
+# ---- B: chr_start layouts that the wrapper refuses and the C ABI documents ------------------------------------------------------
+@pytest.mark.parametrize("layout", ["empty_chromosome", "uncovered_ends"])
+@pytest.mark.parametrize("kind", ["csr", "dense"])
+def test_chr_start_with_an_empty_chromosome_and_uncovered_windows(layout, kind):
+    import torch
+
+    from infercnvpy_amd import _engine
+
+    c = so.planted(9, [10, 7, 13], 19, keep=0.5)
+    sigma, a, p = 0.1, 0.2, 1e-3
+    dense = c["x"].toarray()
+    w = dense.shape[1]
+    dense[:, :3], dense[:, w - 2:] = 3 * a, -3 * a  # a chain that covered these windows would not call them neutral
+    x = sp.csr_matrix(dense)
+    bounds = [0, 10, 10, 17, w] if layout == "empty_chromosome" else [3, 9, w - 2]
+    loss, neutral, gain, _ = po.cnv_posteriors(x, None, amplitude=a, sigma=sigma, switch_prob=p, bounds=bounds)
+    stats = fo.stats(x, None, a, sigma, p, bounds=bounds)
+    h, ps, pw = po.scalars(sigma, p)
+    kw = dict(amplitude=a, h=h, ps=ps, pw=pw)
+    dm = _engine.states_input(x) if kind == "csr" else _engine.DeviceMatrix(dense=torch.from_numpy(dense).cuda())
+    cs = np.asarray(bounds, dtype=np.int32)
+    only, _, _ = _engine.posterior_chains(dm, cs, **kw)
+    _same(only, neutral, "neutral alone")
+    n3, l3, g3 = _engine.posterior_chains(dm, cs, all_states=True, **kw)
+    _same(n3, neutral, "neutral")
+    _same(l3, loss, "loss")
+    _same(g3, gain, "gain")
+    _same(_engine.posterior_stats(dm, cs, **kw), stats, "statistics")
+    covered = po.cnv_posteriors(x, c["chr_pos"], amplitude=a, sigma=sigma, switch_prob=p)
+    if layout == "uncovered_ends":
+        for lo, hi in ((0, 3), (w - 2, w)):
+            assert (neutral[:, lo:hi] == 1.0).all() and not loss[:, lo:hi].any() and not gain[:, lo:hi].any()
+            assert (covered[1][:, lo:hi] < 0.5).all()
+        assert not np.array_equal(stats, fo.stats(x, c["chr_pos"], a, sigma, p))
+    else:  # the empty chromosome adds nothing
+        assert np.array_equal(neutral, covered[1])
+        assert stats.tobytes() == fo.stats(x, c["chr_pos"], a, sigma, p).tobytes()
+
+
+# ---- C: the cutoff of the written exponential, from float32 input ------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["csr_float32", "dense_float32", "cuda_float32"])
+def test_exp_cutoff_case_in_float32_equals_the_oracle(kind):
+    import torch
+
+    import infercnvpy_amd as cnv
+    from infercnvpy_amd import _engine
+    from infercnvpy_amd.tl._states import chromosome_bounds
+
+    c = po.case("exp_cutoff")
+    x = {"csr_float32": lambda: c["x"].astype(np.float32), "dense_float32": lambda: c["x"].toarray().astype(np.float32),
+         "cuda_float32": lambda: torch.from_numpy(c["x"].toarray().astype(np.float32)).cuda()}[kind]()
+    loss, neutral, gain = cnv.tl.cnv_posteriors(_adata(x, c["chr_pos"]), inplace=False, all_states=True, **c["kwargs"])
+    if not torch.is_tensor(neutral):
+        loss, neutral, gain = (torch.from_numpy(v) for v in (loss, neutral, gain))
+    _same(neutral, c["neutral"], kind + " neutral")
+    _same(loss, c["loss"], kind + " loss")
+    _same(gain, c["gain"], kind + " gain")
+    p = c["params"]
+    h, ps, pw = po.scalars(p["sigma"], p["switch_prob"])
+    got = _engine.posterior_stats(_engine.states_input(x), chromosome_bounds(c["chr_pos"], c["x"].shape[1]),
+                                  amplitude=p["amplitude"], h=h, ps=ps, pw=pw)
+    _same(got, fo.stats(c["x"], c["chr_pos"], p["amplitude"], p["sigma"], p["switch_prob"]), kind + " statistics")
+
+
+# ---- E: a finite value whose emission overflows ----------------------------------------------------------------------------------
+def _inputs(x):
+    import torch
+
+    return {"csr": x, "dense": x.toarray(), "cuda": torch.from_numpy(x.toarray()).cuda()}
+
+
+def test_emission_overflow_raises_and_nothing_is_launched(monkeypatch):
+    import infercnvpy_amd as cnv
+    from infercnvpy_amd import _engine
+
+    launched = []
+    for name in ("posterior_chains", "posterior_stats"):
+        real = getattr(_engine, name)
+        monkeypatch.setattr(_engine, name, lambda *a, _real=real, **k: launched.append(1) or _real(*a, **k))
+    x, pos, kw = so.overflow_case()
+    for sign in (1.0, -1.0):
+        for name, xin in _inputs(sp.csr_matrix(sign * x.toarray())).items():
+            ad = _adata(xin, pos)
+            with pytest.raises(ValueError, match=r"sigma=0\.1 and amplitude=0\.2 overflow.*1e\+160"):
+                cnv.tl.cnv_posteriors(ad, **kw)
+            with pytest.raises(ValueError, match="sum of squares of X_cnv overflows"):  # (1e160 squared is not finite)
+                cnv.tl.cnv_states_fit(ad, **kw)
+            assert not [k for k in ad.obsm if k != "X_cnv"] and set(ad.uns) == {"cnv"}, name
+            smaller = sign * x.toarray()
+            smaller[np.abs(smaller) == 1e160] = sign * 1e154  # the sum of squares is finite, the emission is not
+            ad = _adata(_inputs(sp.csr_matrix(smaller))[name], pos)
+            with pytest.raises(ValueError, match=r"sigma=0\.1 and amplitude=0\.2 overflow.*1e\+154"):
+                cnv.tl.cnv_states_fit(ad, **kw)
+            assert not [k for k in ad.obsm if k != "X_cnv"] and set(ad.uns) == {"cnv"}, name
+    assert not launched
+
+
+def test_largest_value_that_does_not_overflow_still_runs():
+    import torch
+
+    import infercnvpy_amd as cnv
+
+    x, pos, kw = so.overflow_case()
+    m = so.largest_value_that_does_not_overflow(kw["amplitude"], kw["sigma"])
+    x.data[x.data == 1e160] = m
+    want = po.cnv_posteriors(x, pos, **kw)
+    assert all(np.isfinite(v).all() for v in want[:3])
+    for name, xin in _inputs(x).items():
+        got = cnv.tl.cnv_posteriors(_adata(xin, pos), inplace=False, all_states=True, **kw)
+        for g, w_, what in zip(got, want, ("loss", "neutral", "gain")):
+            _same(g if torch.is_tensor(g) else torch.from_numpy(g), w_, f"{name} {what}")
+    # the fit takes the same start values; its later steps end as the oracle's do
+    fit = fo.cnv_states_fit(x, pos, max_iter=2, **kw)
+    import warnings
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        params, info = cnv.tl.cnv_states_fit(_adata(x, pos), inplace=False, return_info=True, max_iter=2, **kw)
+    assert repr(params) == repr(fit["params"]) and repr(info["history"]) == repr(fit["history"])
+    assert info.get("stopped") == fit.get("stopped") and info["n_iter"] == fit["n_iter"]

@@ -46,6 +46,41 @@ def test_crafted_verdicts(name):
     assert np.array_equal(got, c["want"])
 
 
+# ---- the kernel's step boundaries and integer rules ("limits pinned") -------------------------------------------
+@pytest.mark.parametrize("neighbourhood", po.SWEEP_NEIGHBOURHOODS)
+def test_runs_that_start_end_or_stay_open_at_every_step_boundary(neighbourhood):
+    """Every run [s, e) around the lanes 0 and 63 of the 64-window steps, alone, behind a run of the other sign and in
+    front of a same-sign run of the next chromosome; the run's integer sum is 0 or 1 above L 2^39, so one window lost or
+    counted twice flips the verdict (tests/test_posterior_oracle.py measures it)."""
+    removed = 0
+    for c in po.sweep_cases(neighbourhood):
+        removed += int(_check(c["states"], c["p"], c["chr_pos"], c["max_p_normal"])[1].sum())
+    assert removed > 50
+
+
+def test_half_integer_posteriors_round_half_to_even():
+    c = po.half_integer_case()
+    got, removed = _check(c["states"], c["p"], c["chr_pos"], c["max_p_normal"])
+    assert removed.tolist() == [0, 0, 7] and np.array_equal(got[0], c["states"][0])
+
+
+def test_sums_above_2_to_53_are_converted_with_one_rounding():
+    c = po.big_sum_case()
+    assert c["states"].shape[1] == po.BIG_W > po.MAX_WINDOWS
+    for i, mean in enumerate(c["means"]):
+        got, removed = _check(c["states"], c["p"], c["chr_pos"], mean)
+        assert got[i].any() and removed[i] == 0
+        got, removed = _check(c["states"], c["p"], c["chr_pos"], float(np.nextafter(mean, 0.0)))
+        assert not got[i].any() and removed[i] == 1
+
+
+def test_thresholds_at_a_runs_own_mean_and_its_float64_neighbours():
+    verdicts = []
+    for c in po.own_mean_cases():
+        verdicts.append(tuple(int(_check(c["states"], c["p"], c["chr_pos"], thr)[1][0]) for thr in c["thresholds"]))
+    assert set(verdicts) == {(1, 0, 0)}
+
+
 def test_more_than_64_runs_in_a_row():
     rng = np.random.default_rng(5)
     w = 431

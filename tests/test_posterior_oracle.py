@@ -139,6 +139,127 @@ def test_chains_do_not_cross_chromosomes_and_all_zero_is_neutral():
     assert (zn == 1.0).all() and not zl.any() and not zg.any() and zp["sigma"] == 0.0
 
 
+def test_exp_cutoff_case_sits_on_the_cutoff_of_the_written_exponential():
+    from _tsne_oracle import exp_
+
+    assert float(exp_(np.float64(-708.0))) > 0.0 and float(exp_(np.nextafter(np.float64(-708.0), -np.inf))) == 0.0
+    c = po.case("exp_cutoff")
+    kw = c["kwargs"]
+    h = po.scalars(kw["sigma"], kw["switch_prob"])[0]
+    assert h == 8.0
+    for v, want in zip(po.CUTOFF_VALUES, (-707.0, -708.0, -709.0)):
+        e = [-((v - mu) * (v - mu)) * h for mu in (-kw["amplitude"], 0.0, kw["amplitude"])]
+        assert e[1] - e[2] == want and np.float32(v) == v
+    for k in ("loss", "neutral", "gain"):
+        assert np.isfinite(c[k]).all() and (c[k] >= 0.0).all() and (c[k] <= 1.0).all()
+    seen = {v: [] for v in po.CUTOFF_VALUES}
+    for row, t, v in c["probes"]:
+        seen[v].append(float(c["neutral"][row, t]))
+    print({v: (min(p), max(p)) for v, p in seen.items()})
+    assert all(len(p) == 2 * len(po.CUTOFF_PROBES) for p in seen.values())
+    assert all(0.0 < p < 1e-300 for p in seen[88.625]) and all(0.0 < p < 1e-300 for p in seen[88.75])
+    assert all(p == 0.0 for p in seen[88.875])
+    assert any(p < 2.2250738585072014e-308 for p in seen[88.75])  # pred b went subnormal on the way
+    starts = sorted(c["chr_pos"].values())
+    assert [po.CUTOFF_PROBES[i] in starts for i in range(4)] == [True, False, False, True]
+    assert po.CUTOFF_PROBES[2] + 1 == c["x"].shape[1] and starts[1] == 9 and starts[2] == 10  # window 9 is alone
+
+
+def test_posterior_bounds_entry_point_and_overflow():
+    c = so.planted(6, [10, 7, 13], 19)
+    x = c["x"]
+    kw = {"amplitude": 0.2, "sigma": 0.1, "switch_prob": 1e-3}
+    want = po.cnv_posteriors(x, c["chr_pos"], **kw)
+    for b in ([0, 10, 17, 30], [0, 10, 10, 17, 30]):
+        got = po.cnv_posteriors(x, None, bounds=b, **kw)
+        assert all(np.array_equal(g, w) for g, w in zip(got[:3], want[:3]))
+    loss, neutral, gain, _ = po.cnv_posteriors(x, None, bounds=[3, 9, 28], **kw)
+    for lo, hi in ((0, 3), (28, 30)):
+        assert (neutral[:, lo:hi] == 1.0).all() and not loss[:, lo:hi].any() and not gain[:, lo:hi].any()
+    assert np.array_equal(neutral[:, 9:28], po.cnv_posteriors(x[:, 9:28], {"c": 0}, **kw)[1])
+    # the defect the overflow rule closes: rules 1-6 alone give 0 / 0 on the whole chromosome
+    x, pos, kw = so.overflow_case()
+    h, ps, pw = po.scalars(kw["sigma"], 1e-3)
+    with np.errstate(all="ignore"):
+        assert np.isnan(po.chain(x.toarray(), kw["amplitude"], h, ps, pw)).all()
+    with pytest.raises(ValueError, match="overflow"):
+        po.cnv_posteriors(x, pos, **kw)
+    m = so.largest_value_that_does_not_overflow(kw["amplitude"], kw["sigma"])
+    x.data[x.data == 1e160] = m
+    assert all(np.isfinite(v).all() for v in po.cnv_posteriors(x, pos, **kw)[:3])
+
+
+# ---- the filter's crafted cases have the power they are meant to have --------------------------------------------------------
+def _rows_changed(c, variant, thr=None):
+    thr = c["max_p_normal"] if thr is None else thr
+    want = po.states_filter(c["states"], c["p"], c["chr_pos"], thr)[0]
+    got = po.states_filter(c["states"], c["p"], c["chr_pos"], thr, variant)[0]
+    return int((got != want).any(axis=1).sum())
+
+
+@pytest.mark.parametrize("neighbourhood", po.SWEEP_NEIGHBOURHOODS)
+def test_step_boundary_sweep_has_both_verdicts_and_sees_a_lost_window(neighbourhood):
+    """Rows whose filtered calls change when a window is lost, measured on the CPU for drop_first / drop_first_sum /
+    drop_64 / drop_64_sum: alone 85 / 85 / 51 / 70 of 171, behind_other_sign 79 / 109 / 67 / 81 of 153,
+    before_same_sign_chromosome 112 / 153 / 80 / 75 of 153."""
+    cases = po.sweep_cases(neighbourhood)
+    rows = sum(len(c["main"]) for c in cases)
+    goes = stays = 0
+    for c in cases:
+        assert c["states"].shape[1] == po.SWEEP_W
+        k = (c["p"] - 0.5) * 2.0 ** 40
+        assert np.array_equal(k, np.rint(k)) and np.abs(k).max() <= 3
+        want = po.states_filter(c["states"], c["p"], c["chr_pos"], 0.5)[0]
+        for i, (s, e) in enumerate(c["main"]):
+            assert (c["states"][i, s:e] != 0).all() and (want[i, s:e] != 0).all() == (k[i, s:e].sum() <= 0)
+            goes += int(want[i, s] == 0)
+            stays += int(want[i, s] != 0)
+    print(f"{neighbourhood}: {rows} rows, the run goes in {goes} and stays in {stays}")
+    assert rows in (171, 153) and goes >= rows // 4 and stays >= rows // 4
+    for variant in ("drop_first", "drop_first_sum", "drop_64", "drop_64_sum"):
+        changed = sum(_rows_changed(c, variant) for c in cases)
+        print(f"{neighbourhood}: {variant} changes {changed} of {rows} rows")
+        assert 5 * changed >= rows, (neighbourhood, variant, changed, rows)
+
+
+def test_half_integer_posteriors_tell_half_even_from_half_up():
+    c = po.half_integer_case()
+    scaled = c["p"] * po.TWO40
+    assert np.array_equal(scaled - np.floor(scaled), np.full(scaled.shape, 0.5))
+    want, _, removed = po.states_filter(c["states"], c["p"], c["chr_pos"], 0.5)
+    up, _, removed_up = po.states_filter(c["states"], c["p"], c["chr_pos"], 0.5, "half_up")
+    assert removed.tolist() == [0, 0, 7] and removed_up.tolist() == [7, 0, 7]
+    assert np.array_equal(want[0], c["states"][0]) and not up[0].any()
+
+
+def test_sums_above_2_to_53_tell_the_rounded_conversion_from_others():
+    c = po.big_sum_case()
+    wrong = {"truncate": 0, "float_sum": 0}
+    for i, ((s, e), mean) in enumerate(zip(po.BIG_RUNS, c["means"])):
+        assert e - s >= 16385
+        total = sum(np.rint(c["p"][i, s:e] * po.TWO40).astype(np.int64).tolist())
+        assert total > 2 ** 53 and total % 4 == i + 1 and float(total) != total
+        for thr, stays in ((mean, True), (float(np.nextafter(mean, 0.0)), False)):
+            got = po.states_filter(c["states"], c["p"], c["chr_pos"], thr)[0]
+            assert bool(got[i, s:e].all()) == stays and (stays or not got[i].any())
+            for variant in wrong:
+                other = po.states_filter(c["states"], c["p"], c["chr_pos"], thr, variant)[0]
+                wrong[variant] += int(not np.array_equal(other[i], got[i]))
+    print(f"verdicts of 6 that the deviating conversions get wrong: {wrong}")
+    assert wrong["truncate"] >= 1 and wrong["float_sum"] >= 1
+
+
+def test_own_mean_thresholds_keep_at_and_above_the_mean_and_drop_below():
+    cases = po.own_mean_cases()
+    lengths = sorted(int((c["states"] != 0).sum()) for c in cases)
+    assert len(cases) == 50 and lengths[0] == 1 and lengths[-1] == 130 and {63, 64, 65} <= set(lengths)
+    for c in cases:
+        below, mean, above = c["thresholds"]
+        assert below < mean < above
+        removed = [int(po.states_filter(c["states"], c["p"], c["chr_pos"], t)[2][0]) for t in c["thresholds"]]
+        assert removed == [1, 0, 0]
+
+
 @pytest.mark.parametrize("name", list(po.crafted_filter_cases()))
 def test_filter_oracle_on_the_crafted_cases(name):
     c = po.crafted_filter_cases()[name]

@@ -92,6 +92,86 @@ def test_random_chains_select_the_ruled_path_among_all_paths():
         _check_chain(xs, a, h, stay, sw)
 
 
+@pytest.mark.parametrize("variant", so.VARIANTS)
+def test_rounding_ties_tell_every_deviating_order_of_operations_from_the_contract(variant):
+    """The power of the case, measured on the CPU (seed 1, chains of 400 whose calls differ from the contract's, at
+    L = 2 / 3 / 6): assoc 54 / 61 / 92, emul 27 / 79 / 45, fma 67 / 62 / 46.  The bound is a condition on the inputs: a
+    kernel that evaluates rule 2 or rule 3 in the variant's order cannot equal the contract's bytes on this case."""
+    c = so.case("rounding_ties")
+    assert c["x"].shape[0] == so.ROUNDING_ROWS and len(c["chr_pos"]) == 3 * so.ROUNDING_CHAINS // so.ROUNDING_ROWS > 64
+    assert all(len(v) == so.ROUNDING_CHAINS for v in c["chains"].values())
+    differ = so.rounding_differences(c, variant)
+    print(f"{variant}: chains of {so.ROUNDING_CHAINS} whose calls differ from the contract's: {differ}")
+    assert set(differ) == set(so.ROUNDING_LENGTHS)
+    for L, n in differ.items():
+        assert n >= 10, (variant, L, n)
+
+
+def test_rounding_ties_reach_all_three_calls_and_the_variants_are_valid_chains():
+    c = so.case("rounding_ties")
+    st = c["states"]
+    share = [float((st == v).mean()) for v in (-1, 0, 1)]
+    print(f"loss / neutral / gain share of the calls: {share}")
+    assert min(share) >= 0.1
+    assert (st[0::2] == 1).mean() > 0.3 and (st[1::2] == -1).mean() > 0.3  # the mirrored rows lose where the others gain
+    # away from a tie the variants are the contract: they deviate in rounding only
+    p = so.planted(12, [20, 1, 9], 4)
+    dense = p["x"].toarray()
+    h, stay, sw = so.scalars(0.1, 1e-3)
+    for row in dense:
+        for s0, s1 in ((0, 20), (20, 21), (21, 30)):
+            xs = row[s0:s1].tolist()
+            want = so.viterbi_chain(xs, 0.2, h, stay, sw)
+            assert all(so.viterbi_chain(xs, 0.2, h, stay, sw, v) == want for v in so.VARIANTS)
+
+
+@pytest.mark.parametrize("w", so.SPLIT_WIDTHS)
+def test_output_split_cases_have_calls_at_both_ends_of_every_row_offset(w):
+    c = so.case(f"output_split_{w}")
+    st = c["states"]
+    assert st.shape == (so.SPLIT_ROWS, w)
+    offsets = {(i * w) % 4 for i in range(so.SPLIT_ROWS)}
+    ends = {(i * w) % 4 for i in range(so.SPLIT_ROWS) if st[i, 0] != 0 and st[i, -1] != 0}
+    assert ends == offsets, (w, offsets, ends)
+    assert (st != 0).mean() > 0.5
+
+
+def test_bounds_entry_point_skips_empty_chromosomes_and_leaves_uncovered_windows_neutral():
+    c = so.planted(6, [10, 7, 13], 19)
+    x, pos = c["x"], c["chr_pos"]
+    kw = {"amplitude": 0.2, "sigma": 0.1}
+    want = so.cnv_states(x, pos, **kw)
+    same = so.cnv_states(x, None, bounds=[0, 10, 17, 30], **kw)
+    assert np.array_equal(same[0], want[0]) and np.array_equal(same[1], want[1])
+    empty = so.cnv_states(x, None, bounds=[0, 10, 10, 17, 30], **kw)
+    assert np.array_equal(empty[0], want[0])
+    part, fraction, _ = so.cnv_states(x, None, bounds=[3, 9, 28], **kw)
+    assert not part[:, :3].any() and not part[:, 28:].any()
+    assert np.array_equal(part[:, 3:9], so.cnv_states(x[:, 3:9], {"c": 0}, **kw)[0])
+    assert np.array_equal(part[:, 9:28], so.cnv_states(x[:, 9:28], {"c": 0}, **kw)[0])
+    assert np.array_equal(fraction, (part != 0).sum(axis=1) / 30.0)
+
+
+def test_emission_overflow_is_an_error_and_the_largest_value_below_it_is_not():
+    x, pos, kw = so.overflow_case()
+    h, stay, sw = so.scalars(kw["sigma"], 1e-3)
+    assert so.emissions(1e160, kw["amplitude"], h) == [-np.inf] * 3
+    # what rules 1-5 alone make of it: every d is -inf from that window on and the tie rules call the whole row neutral
+    assert so.viterbi_chain(x.toarray()[0].tolist(), kw["amplitude"], h, stay, sw) == [1] * 6
+    with pytest.raises(ValueError, match="overflow"):
+        so.cnv_states(x, pos, **kw)
+    with pytest.raises(ValueError, match="overflow"):
+        so.cnv_states(-x, pos, **kw)
+    m = so.largest_value_that_does_not_overflow(kw["amplitude"], kw["sigma"])
+    assert 1e153 < m < 1e154
+    fine = x.copy()
+    fine.data[fine.data == 1e160] = m
+    assert so.cnv_states(fine, pos, **kw)[0].shape == (1, 6)
+    fine.data[fine.data == m] = -float(np.nextafter(m, np.inf))
+    with pytest.raises(ValueError, match="overflow"):
+        so.cnv_states(fine, pos, **kw)
+
+
 def test_boundaries_and_default_parameters():
     c = so.planted(20, [12, 1, 9], 3)
     x, pos = c["x"], c["chr_pos"]
