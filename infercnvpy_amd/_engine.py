@@ -1903,22 +1903,29 @@ def states_flag_and_absmax(flag, absmax):
     return bool(both[0]), float(both[1])
 
 
+def _hmm_call(entry, dm: DeviceMatrix, chr_start, scalars, outputs):
+    """The call shape of the three chain kernels: ``chr_start`` (host int32 array of C + 1 ascending window numbers from 0
+    to W) is uploaded, ``outputs(torch)`` allocates the tuple of result tensors (None for one that is not wanted) on
+    ``dm``'s device, and ``entry(matrix, chr_start, C, *scalars, *outputs, stream)`` is enqueued on the current stream.
+    Returns the outputs; nothing is read back."""
+    torch = _torch()
+    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
+    with torch.cuda.device(dm.device):
+        cs = torch.from_numpy(chr_start).cuda()
+        out = outputs(torch)
+        m = dm.c_struct()
+        _lib.check(entry(C.byref(m), _ptr(cs), int(chr_start.shape[0]) - 1, *(float(v) for v in scalars),
+                         *(_ptr(t) for t in out), _stream_ptr(torch)))
+    return out
+
+
 def states_viterbi(dm: DeviceMatrix, chr_start, *, amplitude, h, stay, sw):
     """(states, nonneutral): device int8 ``n x W`` of -1 / 0 / +1 and device int32 counts of the windows that are not 0
     (DESIGN.md 4.13 rules 2-5).  ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The
     launch is enqueued on the current stream; nothing is read back."""
-    torch = _torch()
-    lib = _lib.load()
     n, w = dm.shape
-    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
-    with torch.cuda.device(dm.device):
-        cs = torch.from_numpy(chr_start).cuda()
-        states = torch.empty((n, w), dtype=torch.int8, device="cuda")
-        count = torch.empty(n, dtype=torch.int32, device="cuda")
-        m = dm.c_struct()
-        _lib.check(lib.icv_states_viterbi(C.byref(m), _ptr(cs), int(chr_start.shape[0]) - 1, float(amplitude), float(h),
-                                          float(stay), float(sw), _ptr(states), _ptr(count), _stream_ptr(torch)))
-    return states, count
+    return _hmm_call(_lib.load().icv_states_viterbi, dm, chr_start, (amplitude, h, stay, sw), lambda torch: (
+        torch.empty((n, w), dtype=torch.int8, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")))
 
 
 def states_fraction(count, n_windows):
@@ -1937,37 +1944,17 @@ def posterior_chains(dm: DeviceMatrix, chr_start, *, amplitude, h, ps, pw, all_s
     """(neutral, loss, gain): device float64 ``n x W`` posteriors of DESIGN.md 4.15 rules 2-5; ``loss`` and ``gain`` are
     None unless ``all_states``.  ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The
     launch is enqueued on the current stream; nothing is read back."""
-    torch = _torch()
-    lib = _lib.load()
-    n, w = dm.shape
-    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
-    with torch.cuda.device(dm.device):
-        cs = torch.from_numpy(chr_start).cuda()
-        neutral = torch.empty((n, w), dtype=torch.float64, device="cuda")
-        loss = torch.empty((n, w), dtype=torch.float64, device="cuda") if all_states else None
-        gain = torch.empty((n, w), dtype=torch.float64, device="cuda") if all_states else None
-        m = dm.c_struct()
-        _lib.check(lib.icv_posterior_chains(C.byref(m), _ptr(cs), int(chr_start.shape[0]) - 1, float(amplitude), float(h),
-                                            float(ps), float(pw), _ptr(neutral), _ptr(loss) if all_states else None,
-                                            _ptr(gain) if all_states else None, _stream_ptr(torch)))
-    return neutral, loss, gain
+    shape, wanted = tuple(dm.shape), (True, all_states, all_states)
+    return _hmm_call(_lib.load().icv_posterior_chains, dm, chr_start, (amplitude, h, ps, pw), lambda torch: tuple(
+        torch.empty(shape, dtype=torch.float64, device="cuda") if k else None for k in wanted))
 
 
 def posterior_stats(dm: DeviceMatrix, chr_start, *, amplitude, h, ps, pw):
     """Device float64 ``n x 3``: per cell the sums (G, D, K) of DESIGN.md 4.16, the E-step of ``tl.cnv_states_fit``.
     ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The launch is enqueued on the current
     stream; nothing is read back."""
-    torch = _torch()
-    lib = _lib.load()
-    n = dm.shape[0]
-    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
-    with torch.cuda.device(dm.device):
-        cs = torch.from_numpy(chr_start).cuda()
-        stats = torch.empty((n, 3), dtype=torch.float64, device="cuda")
-        m = dm.c_struct()
-        _lib.check(lib.icv_posterior_stats(C.byref(m), _ptr(cs), int(chr_start.shape[0]) - 1, float(amplitude), float(h),
-                                           float(ps), float(pw), _ptr(stats), _stream_ptr(torch)))
-    return stats
+    return _hmm_call(_lib.load().icv_posterior_stats, dm, chr_start, (amplitude, h, ps, pw), lambda torch: (
+        torch.empty((dm.shape[0], 3), dtype=torch.float64, device="cuda"),))[0]
 
 
 def states_filter(states, p_neutral, chr_start, max_p_normal):

@@ -4035,6 +4035,66 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
     return ICV_OK;
 }
 
+}  // extern "C"
+
+// ---- the chain kernels of the three-state model (csrc/icv_hmm.hpp): what their three entry points share ---------------------
+namespace {
+
+// The argument checks of icv_states_viterbi, icv_posterior_chains and icv_posterior_stats, in the order they are reported.
+// who: the entry point without icv_; outputs_ok: its own pointers; cap, lds_per_window: its window cap and the LDS bytes a
+// window takes; params_ok, params_rule: its verdict on the model's scalars and the words for it.
+int hmm_check(const std::string& who, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, bool outputs_ok, int cap,
+              int lds_per_window, bool params_ok, const char* params_rule) {
+    if (!m || !chr_start || !outputs_ok || n_chr < 1 || m->n_rows < 0 || (m->dtype != ICV_F32 && m->dtype != ICV_F64) ||
+        (m->format != ICV_DENSE && m->format != ICV_CSR))
+        return fail(ICV_ERR_INVALID, "bad " + who + " arguments");
+    if (m->n_cols < 1 || m->n_cols > cap)
+        return fail(ICV_ERR_INVALID, who + ": n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
+                                         std::to_string(cap) + "] (" + std::to_string(lds_per_window) +
+                                         " bytes of LDS per window)");
+    if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, who + ": more chromosomes than windows");
+    if (!params_ok) return fail(ICV_ERR_INVALID, who + ": " + params_rule);
+    if (m->format == ICV_DENSE ? (m->ld < m->n_cols || !m->values) : !m->indptr)
+        return fail(ICV_ERR_INVALID, who + ": incomplete matrix");
+    if (m->n_rows > 0x7fffffffLL) return fail(ICV_ERR_UNSUPPORTED, who + ": more than 2^31 - 1 rows in one call");
+    return ICV_OK;
+}
+
+// the rule of icv_posterior_chains and icv_posterior_stats for (amplitude, h, ps, pw)
+bool po_params_ok(double amplitude, double h, double ps, double pw) {
+    return std::isfinite(amplitude) && amplitude > 0.0 && std::isfinite(h) && h > 0.0 && std::isnormal(pw) && pw > 0.0 &&
+           ps > 0.0 && ps < 1.0 && pw < 0.5;
+}
+constexpr const char* kPoParamsRule =
+    "amplitude and h must be finite and > 0, ps = 1 - p and pw = p / 2 for a p in (0, 1) with pw a normal float64";
+
+// one instantiation of a chain kernel over the rows of m, one wavefront per row, with lds bytes of dynamic LDS; args: what
+// the kernel takes after (val, indptr, indices, ld, W, chr_start, C)
+template <typename T, typename Kernel, typename... Args>
+int hmm_launch(Kernel kern, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, size_t lds, void* stream,
+               Args... args) {
+    if (m->n_rows == 0) return ICV_OK;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)m->n_rows), dim3(64), lds, static_cast<hipStream_t>(stream), (const T*)m->values,
+                       m->indptr, m->indices, m->ld, m->n_cols, chr_start, n_chr, args...);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// KERNEL<float | double, CSR | dense> by m's dtype and format
+#define ICV_HMM_LAUNCH(KERNEL, lds, ...)                                                                               \
+    (m->format == ICV_CSR                                                                                              \
+         ? (m->dtype == ICV_F32                                                                                        \
+                ? hmm_launch<float>(icv::KERNEL<float, true>, m, chr_start, n_chr, lds, stream, __VA_ARGS__)           \
+                : hmm_launch<double>(icv::KERNEL<double, true>, m, chr_start, n_chr, lds, stream, __VA_ARGS__))        \
+         : (m->dtype == ICV_F32                                                                                        \
+                ? hmm_launch<float>(icv::KERNEL<float, false>, m, chr_start, n_chr, lds, stream, __VA_ARGS__)          \
+                : hmm_launch<double>(icv::KERNEL<double, false>, m, chr_start, n_chr, lds, stream, __VA_ARGS__)))
+
+}  // namespace
+
+extern "C" {
+
 // ---- tl.cnv_states ---------------------------------------------------------------------------------------
 static_assert(icv::kStMaxWindows == ICV_STATES_MAX_WINDOWS, "the header's window cap is the kernel's");
 static_assert((size_t)icv::kStMaxWindows * icv::kStLdsPerWindow <= (size_t)icv::kLdsLimit, "one cell fits a CU's LDS");
@@ -4066,40 +4126,12 @@ int icv_states_rowsq(const icv_matrix* m, double* rowsq, int32_t* nonfinite, voi
 
 int icv_states_viterbi(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, double amplitude, double h,
                        double stay, double sw, int8_t* states, int32_t* nonneutral, void* stream) {
-    if (!m || !chr_start || !states || !nonneutral || n_chr < 1 || m->n_rows < 0 ||
-        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR))
-        return fail(ICV_ERR_INVALID, "bad states_viterbi arguments");
-    if (m->n_cols < 1 || m->n_cols > ICV_STATES_MAX_WINDOWS)
-        return fail(ICV_ERR_INVALID, "states_viterbi: n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
-                                         std::to_string(ICV_STATES_MAX_WINDOWS) + "] (9 bytes of LDS per window)");
-    if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, "states_viterbi: more chromosomes than windows");
-    if (!(std::isfinite(amplitude) && amplitude > 0.0 && std::isfinite(h) && h > 0.0 && std::isfinite(stay) &&
-          std::isfinite(sw)))
-        return fail(ICV_ERR_INVALID, "states_viterbi: amplitude and h must be finite and > 0, stay and sw finite");
-    if (m->format == ICV_DENSE ? (m->ld < m->n_cols || !m->values) : !m->indptr)
-        return fail(ICV_ERR_INVALID, "states_viterbi: incomplete matrix");
-    if (m->n_rows == 0) return ICV_OK;
-    if (m->n_rows > 0x7fffffffLL) return fail(ICV_ERR_UNSUPPORTED, "states_viterbi: more than 2^31 - 1 rows in one call");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = icv::st_lds_bytes(m->n_cols);
-    const icv::StParams P{amplitude, h, stay, sw};
-    const dim3 grid((unsigned)m->n_rows), block(64);
-#define ICV_VITERBI(T, CSR)                                                                                            \
-    {                                                                                                                  \
-        auto kern = icv::k_states_viterbi<T, CSR>;                                                                     \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                    (int)lds));                                                                        \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)m->values, m->indptr, m->indices, m->ld, m->n_cols,   \
-                           chr_start, n_chr, P, states, nonneutral);                                                   \
-    }
-    if (m->format == ICV_CSR) {
-        if (m->dtype == ICV_F32) ICV_VITERBI(float, true) else ICV_VITERBI(double, true)
-    } else {
-        if (m->dtype == ICV_F32) ICV_VITERBI(float, false) else ICV_VITERBI(double, false)
-    }
-#undef ICV_VITERBI
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    const bool params_ok = std::isfinite(amplitude) && amplitude > 0.0 && std::isfinite(h) && h > 0.0 &&
+                           std::isfinite(stay) && std::isfinite(sw);
+    ICV_TRY(hmm_check("states_viterbi", m, chr_start, n_chr, states && nonneutral, ICV_STATES_MAX_WINDOWS,
+                      icv::kStLdsPerWindow, params_ok, "amplitude and h must be finite and > 0, stay and sw finite"));
+    return ICV_HMM_LAUNCH(k_states_viterbi, icv::st_lds_bytes(m->n_cols), icv::StParams{amplitude, h, stay, sw}, states,
+                          nonneutral);
 }
 
 int icv_states_fraction(const int32_t* nonneutral, int64_t n_rows, int32_t n_cols, double* fraction, void* stream) {
@@ -4227,41 +4259,10 @@ static_assert(icv::kFiMaxWindows == ICV_FILTER_MAX_WINDOWS, "the header's window
 
 int icv_posterior_chains(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, double amplitude, double h,
                          double ps, double pw, double* neutral, double* loss, double* gain, void* stream) {
-    if (!m || !chr_start || !neutral || (loss == nullptr) != (gain == nullptr) || n_chr < 1 || m->n_rows < 0 ||
-        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR))
-        return fail(ICV_ERR_INVALID, "bad posterior_chains arguments");
-    if (m->n_cols < 1 || m->n_cols > ICV_POSTERIOR_MAX_WINDOWS)
-        return fail(ICV_ERR_INVALID, "posterior_chains: n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
-                                         std::to_string(ICV_POSTERIOR_MAX_WINDOWS) + "] (32 bytes of LDS per window)");
-    if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, "posterior_chains: more chromosomes than windows");
-    if (!(std::isfinite(amplitude) && amplitude > 0.0 && std::isfinite(h) && h > 0.0 && std::isnormal(pw) && pw > 0.0 &&
-          ps > 0.0 && ps < 1.0 && pw < 0.5))
-        return fail(ICV_ERR_INVALID, "posterior_chains: amplitude and h must be finite and > 0, ps = 1 - p and pw = p / 2 "
-                                     "for a p in (0, 1) with pw a normal float64");
-    if (m->format == ICV_DENSE ? (m->ld < m->n_cols || !m->values) : !m->indptr)
-        return fail(ICV_ERR_INVALID, "posterior_chains: incomplete matrix");
-    if (m->n_rows == 0) return ICV_OK;
-    if (m->n_rows > 0x7fffffffLL) return fail(ICV_ERR_UNSUPPORTED, "posterior_chains: more than 2^31 - 1 rows in one call");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = icv::po_lds_bytes(m->n_cols);
-    const icv::PoParams P{amplitude, h, ps, pw};
-    const dim3 grid((unsigned)m->n_rows), block(64);
-#define ICV_POSTERIOR(T, CSR)                                                                                          \
-    {                                                                                                                  \
-        auto kern = icv::k_posterior_chains<T, CSR>;                                                                   \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                    (int)lds));                                                                        \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)m->values, m->indptr, m->indices, m->ld, m->n_cols,   \
-                           chr_start, n_chr, P, neutral, loss, gain);                                                  \
-    }
-    if (m->format == ICV_CSR) {
-        if (m->dtype == ICV_F32) ICV_POSTERIOR(float, true) else ICV_POSTERIOR(double, true)
-    } else {
-        if (m->dtype == ICV_F32) ICV_POSTERIOR(float, false) else ICV_POSTERIOR(double, false)
-    }
-#undef ICV_POSTERIOR
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    ICV_TRY(hmm_check("posterior_chains", m, chr_start, n_chr, neutral && (loss == nullptr) == (gain == nullptr),
+                      ICV_POSTERIOR_MAX_WINDOWS, icv::kPoLdsPerWindow, po_params_ok(amplitude, h, ps, pw), kPoParamsRule));
+    return ICV_HMM_LAUNCH(k_posterior_chains, icv::po_lds_bytes(m->n_cols), icv::PoParams{amplitude, h, ps, pw}, neutral,
+                          loss, gain);
 }
 
 int icv_states_filter(const int8_t* states, const double* p_neutral, int64_t n_rows, int32_t n_cols,
@@ -4290,41 +4291,10 @@ int icv_states_filter(const int8_t* states, const double* p_neutral, int64_t n_r
 // ---- tl.cnv_states_fit: the E-step of the Baum-Welch fit ----------------------------------------------------
 int icv_posterior_stats(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, double amplitude, double h, double ps,
                         double pw, double* stats, void* stream) {
-    if (!m || !chr_start || !stats || n_chr < 1 || m->n_rows < 0 || (m->dtype != ICV_F32 && m->dtype != ICV_F64) ||
-        (m->format != ICV_DENSE && m->format != ICV_CSR))
-        return fail(ICV_ERR_INVALID, "bad posterior_stats arguments");
-    if (m->n_cols < 1 || m->n_cols > ICV_POSTERIOR_MAX_WINDOWS)
-        return fail(ICV_ERR_INVALID, "posterior_stats: n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
-                                         std::to_string(ICV_POSTERIOR_MAX_WINDOWS) + "] (32 bytes of LDS per window)");
-    if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, "posterior_stats: more chromosomes than windows");
-    if (!(std::isfinite(amplitude) && amplitude > 0.0 && std::isfinite(h) && h > 0.0 && std::isnormal(pw) && pw > 0.0 &&
-          ps > 0.0 && ps < 1.0 && pw < 0.5))
-        return fail(ICV_ERR_INVALID, "posterior_stats: amplitude and h must be finite and > 0, ps = 1 - p and pw = p / 2 "
-                                     "for a p in (0, 1) with pw a normal float64");
-    if (m->format == ICV_DENSE ? (m->ld < m->n_cols || !m->values) : !m->indptr)
-        return fail(ICV_ERR_INVALID, "posterior_stats: incomplete matrix");
-    if (m->n_rows == 0) return ICV_OK;
-    if (m->n_rows > 0x7fffffffLL) return fail(ICV_ERR_UNSUPPORTED, "posterior_stats: more than 2^31 - 1 rows in one call");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = icv::po_lds_bytes(m->n_cols);
-    const icv::PoParams P{amplitude, h, ps, pw};
-    const dim3 grid((unsigned)m->n_rows), block(64);
-#define ICV_POSTERIOR_STATS(T, CSR)                                                                                    \
-    {                                                                                                                  \
-        auto kern = icv::k_posterior_stats<T, CSR>;                                                                    \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                    (int)lds));                                                                        \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)m->values, m->indptr, m->indices, m->ld, m->n_cols,   \
-                           chr_start, n_chr, P, stats);                                                                \
-    }
-    if (m->format == ICV_CSR) {
-        if (m->dtype == ICV_F32) ICV_POSTERIOR_STATS(float, true) else ICV_POSTERIOR_STATS(double, true)
-    } else {
-        if (m->dtype == ICV_F32) ICV_POSTERIOR_STATS(float, false) else ICV_POSTERIOR_STATS(double, false)
-    }
-#undef ICV_POSTERIOR_STATS
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    ICV_TRY(hmm_check("posterior_stats", m, chr_start, n_chr, stats != nullptr, ICV_POSTERIOR_MAX_WINDOWS,
+                      icv::kPoLdsPerWindow, po_params_ok(amplitude, h, ps, pw), kPoParamsRule));
+    return ICV_HMM_LAUNCH(k_posterior_stats, icv::po_lds_bytes(m->n_cols), icv::PoParams{amplitude, h, ps, pw}, stats);
 }
+#undef ICV_HMM_LAUNCH
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // tl.cnv_states_fit: the E-step of the Baum-Welch fit of amplitude, sigma and switch_prob of the
-// three-state model of tl.cnv_states.  Forward-backward along every chromosome of every cell as in k_posterior_chains,
-// but the posteriors are reduced to three sums per cell instead of leaving as n x W planes.  tests/_fit_oracle.py
-// restates the contract.
+// three-state model of tl.cnv_states.  Forward-backward along every chromosome of every cell by the chain that
+// k_posterior_chains runs (hmm_forward_backward of icv_hmm.hpp), but the posteriors are reduced to three sums per cell
+// instead of leaving as n x W planes.  tests/_fit_oracle.py restates the contract.
 //
 // Float64 throughout, every operation one correctly rounded IEEE operation in the written order (the library is built
 // -ffp-contract=off).  Rules 1-5 of 4.15 give b, al_t, c_t, be_t, w, z_t and gamma_t unchanged.  Per chromosome of T
@@ -13,8 +13,8 @@
 // The cell's G, D and K start at 0.0 and add the chromosome sums in ascending chromosome order; a chromosome without
 // windows adds nothing.  stats[i] = (G, D, K).
 //
-// Geometry: that of k_posterior_chains, one wavefront (a 64-thread workgroup) per cell, lane c running the chromosomes
-// c, c + 64, ... sequentially, the row as W doubles and al_t as three planes of W doubles in LDS (32 bytes per window).
+// Geometry: that of icv_hmm.hpp and k_posterior_chains: the row as W doubles and al_t as three planes of W doubles in
+// LDS (32 bytes per window).
 // The backward pass keeps gamma_t in registers.  When a chromosome's chain is finished nothing reads the planes' slots of
 // its first window again: its three sums are parked there, and after a barrier three lanes, one per statistic, add them
 // up along chr_start.  (Per-lane partial sums reduced by shuffles would fix neither the order for more than 64
@@ -24,12 +24,12 @@
 
 #include <cstdint>
 
-#include "icv_posterior.hpp"  // PoParams, po_emit, po_pred, po_lds_bytes, kPoMaxWindows
+#include "icv_hmm.hpp"        // PoParams, hmm_load_row, hmm_chr, hmm_forward_backward
+#include "icv_posterior.hpp"  // po_lds_bytes, kPoMaxWindows
 
 namespace icv {
 
-// chr_start: C + 1 ascending window numbers, chr_start[0] = 0, chr_start[C] = W (the host checked them; they are clamped
-// to [0, W] here all the same, so no LDS access leaves the row).  stats: n x 3.
+// chr_start: see hmm_chr.  stats: n x 3.
 template <typename T, bool CSR>
 __global__ __launch_bounds__(64) void k_posterior_stats(const T* __restrict__ val, const int64_t* __restrict__ indptr,
                                                         const int32_t* __restrict__ indices, int64_t ld, int32_t W,
@@ -43,68 +43,22 @@ __global__ __launch_bounds__(64) void k_posterior_stats(const T* __restrict__ va
     const int lane = threadIdx.x;
     const int64_t row = blockIdx.x;
 
-    if (CSR) {
-        for (int32_t j = lane; j < W; j += 64) x[j] = 0.0;
-        __syncthreads();
-        const int64_t b = indptr[row], e = indptr[row + 1];
-        for (int64_t k = b + lane; k < e; k += 64) {
-            const int32_t c = indices[k];
-            if ((uint32_t)c < (uint32_t)W) x[c] = (double)val[k];
-        }
-    } else {
-        const T* src = val + row * ld;
-        for (int32_t j = lane; j < W; j += 64) x[j] = (double)src[j];
-    }
-    __syncthreads();
+    hmm_load_row<T, CSR>(x, W, val, indptr, indices, ld, row, lane);
 
     for (int32_t c = lane; c < C; c += 64) {
-        const int32_t s0 = min(max(chr_start[c], 0), W), s1 = min(max(chr_start[c + 1], 0), W);
-        if (s1 <= s0) continue;
-        double b0, b1, b2, a0, a1, a2;
-        // rule 3 of 4.15
-        po_emit(x[s0], P, b0, b1, b2);
-        {
-            const double cc = (b0 + b1) + b2;
-            a0 = b0 / cc, a1 = b1 / cc, a2 = b2 / cc;
-        }
-        g0[s0] = a0, g1[s0] = a1, g2[s0] = a2;
-        for (int32_t t = s0 + 1; t < s1; ++t) {
-            double p0, p1, p2;
-            po_emit(x[t], P, b0, b1, b2);
-            po_pred(a0, a1, a2, P, p0, p1, p2);
-            const double u0 = p0 * b0, u1 = p1 * b1, u2 = p2 * b2;
-            const double cc = (u0 + u1) + u2;
-            a0 = u0 / cc, a1 = u1 / cc, a2 = u2 / cc;
-            g0[t] = a0, g1[t] = a1, g2[t] = a2;
-        }
-        // rules 4-5 and the sums: (a0, a1, a2) = al_t; from the second step on (q0, q1, q2) = b_{t+1} be_{t+1} and
-        // cc = c_{t+1}
-        double be0 = 1.0, be1 = 1.0, be2 = 1.0;
-        double q0 = 0.0, q1 = 0.0, q2 = 0.0, cc = 1.0;
+        int32_t s0, s1;
+        if (!hmm_chr(chr_start, c, W, s0, s1)) continue;
         double G = 0.0, D = 0.0, K = 0.0;
-        for (int32_t t = s1 - 1;; --t) {
-            const double w0 = a0 * be0, w1 = a1 * be1, w2 = a2 * be2;
-            const double z = (w0 + w1) + w2;
-            const double ga0 = w0 / z, ga2 = w2 / z;
+        hmm_forward_backward(x, g0, g1, g2, s0, s1, P, [&](const HmmStep& s) {
+            const double ga0 = s.w0 / s.z, ga2 = s.w2 / s.z;
             G += (ga0 + ga2);
-            D += (ga2 - ga0) * x[t];
-            if (t != s1 - 1) {
-                const double m0 = (a0 * P.ps) * q0, m1 = (a1 * P.ps) * q1, m2 = (a2 * P.ps) * q2;
+            D += (ga2 - ga0) * x[s.t];
+            if (s.inner) {
+                const double m0 = (s.a0 * P.ps) * s.q0, m1 = (s.a1 * P.ps) * s.q1, m2 = (s.a2 * P.ps) * s.q2;
                 const double st = (m0 + m1) + m2;
-                K += (st / cc) / z;
+                K += (st / s.cc) / s.z;
             }
-            if (t == s0) break;
-            po_emit(x[t], P, b0, b1, b2);  // b_t: the window the step t - 1 looks ahead to
-            a0 = g0[t - 1], a1 = g1[t - 1], a2 = g2[t - 1];
-            double p0, p1, p2;
-            po_pred(a0, a1, a2, P, p0, p1, p2);
-            cc = ((p0 * b0) + (p1 * b1)) + (p2 * b2);  // c_t, as the forward pass formed it
-            q0 = b0 * be0, q1 = b1 * be1, q2 = b2 * be2;
-            const double v0 = ((P.ps * q0) + (P.pw * q1)) + (P.pw * q2);
-            const double v1 = ((P.pw * q0) + (P.ps * q1)) + (P.pw * q2);
-            const double v2 = ((P.pw * q0) + (P.pw * q1)) + (P.ps * q2);
-            be0 = v0 / cc, be1 = v1 / cc, be2 = v2 / cc;
-        }
+        });
         g0[s0] = G, g1[s0] = D, g2[s0] = K;
     }
     __syncthreads();
@@ -114,9 +68,8 @@ __global__ __launch_bounds__(64) void k_posterior_stats(const T* __restrict__ va
         const double* plane = x + (size_t)(lane + 1) * W;
         double acc = 0.0;
         for (int32_t c = 0; c < C; ++c) {
-            const int32_t s0 = min(max(chr_start[c], 0), W), s1 = min(max(chr_start[c + 1], 0), W);
-            if (s1 <= s0) continue;
-            acc += plane[s0];
+            int32_t s0, s1;
+            if (hmm_chr(chr_start, c, W, s0, s1)) acc += plane[s0];
         }
         stats[row * 3 + lane] = acc;
     }

@@ -16,11 +16,10 @@
 //   5. w(s) = al_t(s) be_t(s), z = (w(0) + w(1)) + w(2), gamma_t(s) = w(s) / z.
 //   6. chains never cross a chromosome boundary; an entry that is not stored is 0.0.
 //
-// Geometry: that of k_states_viterbi, one wavefront (a 64-thread workgroup) per cell, lane c running the chromosomes
-// c, c + 64, ... sequentially.  LDS holds the row as W doubles and three planes of W doubles: the forward pass leaves
-// al_t there, the backward pass reads al_t, recomputes b_{t+1} and c_{t+1} (the same operations on the same operands,
-// hence the same bits) and overwrites al_t with gamma_t; the planes then leave in coalesced 8-byte stores.  32 bytes of
-// LDS per window and resident cell.
+// Geometry: that of icv_hmm.hpp, which also holds the chain (hmm_forward_backward).  LDS holds the row as W doubles and
+// three planes of W doubles: the forward pass leaves al_t there, the backward pass reads al_t, recomputes b_{t+1} and
+// c_{t+1} (the same operations on the same operands, hence the same bits) and overwrites al_t with gamma_t; the planes
+// then leave in coalesced 8-byte stores.  32 bytes of LDS per window and resident cell.
 //
 // Filter, integers after one rounding per window:
 //   1. q_t = int64(rint(P[i,t] 2^40)).
@@ -36,8 +35,8 @@
 
 #include <cstdint>
 
+#include "icv_hmm.hpp"       // PoParams, hmm_load_row, hmm_chr, hmm_forward_backward
 #include "icv_segments.hpp"  // kSegMaskShift, k_seg_chr_mask
-#include "icv_tsne.hpp"      // ts_exp
 
 namespace icv {
 
@@ -48,32 +47,7 @@ constexpr int kFiMaxWindows = 1 << 22;  // 2^22 terms of at most 2^40 fit an int
 
 inline size_t po_lds_bytes(int32_t n_windows) { return (size_t)n_windows * kPoLdsPerWindow; }
 
-struct PoParams {
-    double a, h, ps, pw;
-};
-
-// rule 2 for the three states
-__device__ __forceinline__ void po_emit(double x, const PoParams& P, double& b0, double& b1, double& b2) {
-    const double t0 = x - (-P.a), t1 = x - 0.0, t2 = x - P.a;
-    const double e0 = -(t0 * t0) * P.h, e1 = -(t1 * t1) * P.h, e2 = -(t2 * t2) * P.h;
-    double m = e0;
-    if (e1 > m) m = e1;
-    if (e2 > m) m = e2;
-    b0 = ts_exp(e0 - m);
-    b1 = ts_exp(e1 - m);
-    b2 = ts_exp(e2 - m);
-}
-
-// pred of rule 3 from al_{t-1}
-__device__ __forceinline__ void po_pred(double a0, double a1, double a2, const PoParams& P, double& p0, double& p1,
-                                        double& p2) {
-    p0 = ((a0 * P.ps) + (a1 * P.pw)) + (a2 * P.pw);
-    p1 = ((a0 * P.pw) + (a1 * P.ps)) + (a2 * P.pw);
-    p2 = ((a0 * P.pw) + (a1 * P.pw)) + (a2 * P.ps);
-}
-
-// chr_start: C + 1 ascending window numbers, chr_start[0] = 0, chr_start[C] = W (the host checked them; they are clamped
-// to [0, W] here all the same, so no LDS access leaves the row).  neutral: n x W; loss / gain: n x W or both null.
+// chr_start: see hmm_chr.  neutral: n x W; loss / gain: n x W or both null.
 template <typename T, bool CSR>
 __global__ __launch_bounds__(64) void k_posterior_chains(const T* __restrict__ val, const int64_t* __restrict__ indptr,
                                                          const int32_t* __restrict__ indices, int64_t ld, int32_t W,
@@ -90,58 +64,14 @@ __global__ __launch_bounds__(64) void k_posterior_chains(const T* __restrict__ v
 
     // (a window no chromosome covers is neutral)
     for (int32_t j = lane; j < W; j += 64) g0[j] = 0.0, g1[j] = 1.0, g2[j] = 0.0;
-    if (CSR) {
-        for (int32_t j = lane; j < W; j += 64) x[j] = 0.0;
-        __syncthreads();
-        const int64_t b = indptr[row], e = indptr[row + 1];
-        for (int64_t k = b + lane; k < e; k += 64) {
-            const int32_t c = indices[k];
-            if ((uint32_t)c < (uint32_t)W) x[c] = (double)val[k];
-        }
-    } else {
-        const T* src = val + row * ld;
-        for (int32_t j = lane; j < W; j += 64) x[j] = (double)src[j];
-    }
-    __syncthreads();
+    hmm_load_row<T, CSR>(x, W, val, indptr, indices, ld, row, lane);
 
     for (int32_t c = lane; c < C; c += 64) {
-        const int32_t s0 = min(max(chr_start[c], 0), W), s1 = min(max(chr_start[c + 1], 0), W);
-        if (s1 <= s0) continue;
-        double b0, b1, b2, a0, a1, a2;
-        // rule 3
-        po_emit(x[s0], P, b0, b1, b2);
-        {
-            const double cc = (b0 + b1) + b2;
-            a0 = b0 / cc, a1 = b1 / cc, a2 = b2 / cc;
-        }
-        g0[s0] = a0, g1[s0] = a1, g2[s0] = a2;
-        for (int32_t t = s0 + 1; t < s1; ++t) {
-            double p0, p1, p2;
-            po_emit(x[t], P, b0, b1, b2);
-            po_pred(a0, a1, a2, P, p0, p1, p2);
-            const double u0 = p0 * b0, u1 = p1 * b1, u2 = p2 * b2;
-            const double cc = (u0 + u1) + u2;
-            a0 = u0 / cc, a1 = u1 / cc, a2 = u2 / cc;
-            g0[t] = a0, g1[t] = a1, g2[t] = a2;
-        }
-        // rules 4-5: (a0, a1, a2) = al_{T-1}; (b0, b1, b2) = b_{t+1} from the second step on
-        double be0 = 1.0, be1 = 1.0, be2 = 1.0;
-        for (int32_t t = s1 - 1;; --t) {
-            const double w0 = a0 * be0, w1 = a1 * be1, w2 = a2 * be2;
-            const double z = (w0 + w1) + w2;
-            g0[t] = w0 / z, g1[t] = w1 / z, g2[t] = w2 / z;
-            if (t == s0) break;
-            po_emit(x[t], P, b0, b1, b2);  // b_t: the window the step t - 1 looks ahead to
-            a0 = g0[t - 1], a1 = g1[t - 1], a2 = g2[t - 1];
-            double p0, p1, p2;
-            po_pred(a0, a1, a2, P, p0, p1, p2);
-            const double cc = ((p0 * b0) + (p1 * b1)) + (p2 * b2);  // c_t, as the forward pass formed it
-            const double q0 = b0 * be0, q1 = b1 * be1, q2 = b2 * be2;
-            const double v0 = ((P.ps * q0) + (P.pw * q1)) + (P.pw * q2);
-            const double v1 = ((P.pw * q0) + (P.ps * q1)) + (P.pw * q2);
-            const double v2 = ((P.pw * q0) + (P.pw * q1)) + (P.ps * q2);
-            be0 = v0 / cc, be1 = v1 / cc, be2 = v2 / cc;
-        }
+        int32_t s0, s1;
+        if (!hmm_chr(chr_start, c, W, s0, s1)) continue;
+        hmm_forward_backward(x, g0, g1, g2, s0, s1, P, [&](const HmmStep& s) {  // gamma_t (rule 5) over al_t
+            g0[s.t] = s.w0 / s.z, g1[s.t] = s.w1 / s.z, g2[s.t] = s.w2 / s.z;
+        });
     }
     __syncthreads();
 

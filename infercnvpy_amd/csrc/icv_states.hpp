@@ -11,14 +11,16 @@
 // Only float64 adds, multiplies and compares in a fixed order; the library is built -ffp-contract=off, so the
 // expressions below are evaluated as written and the kernel equals the oracle bit for bit.
 //
-// Geometry: one wavefront (a 64-thread workgroup) per cell.  The row lies in LDS as W doubles (zeroed, then the stored
-// entries scattered on top; a dense row is converted in place), lane c runs the chromosomes c, c + 64, ... sequentially,
-// the back-pointers (2 bits x 3 states) take one LDS byte per window, which the backtrack overwrites with the state.
-// 9 bytes of LDS per window and resident cell; ICV_STATES_MAX_WINDOWS keeps one cell inside a CU's 160 KiB.
+// Geometry: that of icv_hmm.hpp (one wavefront per cell, the row as W doubles in LDS, lane c running the chromosomes
+// c, c + 64, ...); the back-pointers (2 bits x 3 states) take one LDS byte per window, which the backtrack overwrites
+// with the state.  9 bytes of LDS per window and resident cell; ICV_STATES_MAX_WINDOWS keeps one cell inside a CU's
+// 160 KiB.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "icv_hmm.hpp"  // hmm_load_row, hmm_chr
 
 namespace icv {
 
@@ -84,9 +86,7 @@ __device__ __forceinline__ void st_emit(double x, const StParams& P, double& e0,
     e2 = -(t2 * t2) * P.h;
 }
 
-// ---- rules 2-5: one wavefront per cell ------------------------------------------------------------------------------------
-// chr_start: C + 1 ascending window numbers, chr_start[0] = 0, chr_start[C] = W (the host checked them; they are clamped
-// to [0, W] here all the same, so no LDS access leaves the row).
+// ---- rules 2-5: one wavefront per cell (chr_start: see hmm_chr) -----------------------------------------------------------
 template <typename T, bool CSR>
 __global__ __launch_bounds__(64) void k_states_viterbi(const T* __restrict__ val, const int64_t* __restrict__ indptr,
                                                        const int32_t* __restrict__ indices, int64_t ld, int32_t W,
@@ -99,24 +99,12 @@ __global__ __launch_bounds__(64) void k_states_viterbi(const T* __restrict__ val
     const int64_t row = blockIdx.x;
 
     for (int32_t j = lane; j < W; j += 64) bp[j] = 1;  // (a window no chromosome covers stays neutral)
-    if (CSR) {
-        for (int32_t j = lane; j < W; j += 64) x[j] = 0.0;
-        __syncthreads();
-        const int64_t b = indptr[row], e = indptr[row + 1];
-        for (int64_t k = b + lane; k < e; k += 64) {
-            const int32_t c = indices[k];
-            if ((uint32_t)c < (uint32_t)W) x[c] = (double)val[k];
-        }
-    } else {
-        const T* src = val + row * ld;
-        for (int32_t j = lane; j < W; j += 64) x[j] = (double)src[j];
-    }
-    __syncthreads();
+    hmm_load_row<T, CSR>(x, W, val, indptr, indices, ld, row, lane);
 
     int32_t count = 0;
     for (int32_t c = lane; c < C; c += 64) {
-        const int32_t s0 = min(max(chr_start[c], 0), W), s1 = min(max(chr_start[c + 1], 0), W);
-        if (s1 <= s0) continue;
+        int32_t s0, s1;
+        if (!hmm_chr(chr_start, c, W, s0, s1)) continue;
         double d0, d1, d2;
         st_emit(x[s0], P, d0, d1, d2);
         for (int32_t t = s0 + 1; t < s1; ++t) {

@@ -11,12 +11,11 @@ bit.
 from __future__ import annotations
 
 import math
-import sys
 import time
 import warnings
 
 from .. import _engine, _lib
-from ._states import _positive, check_emissions, chromosome_bounds
+from ._hmm import resolve
 
 _NAMES = ("amplitude", "sigma", "switch_prob")
 _P_MIN, _P_MAX = 1e-9, 0.5
@@ -38,6 +37,28 @@ def _m_step(gs, ds, ks, qs, n_total, n_steps, a, sigma, p, fit):
     except ZeroDivisionError:
         ok = False
     return (a, sigma, p) if ok else None
+
+
+def _fit_options(fit, max_iter, tol):
+    """(the fitted names in the order of _NAMES, tol as a float) of the checked ``fit``, ``max_iter`` and ``tol``."""
+    if isinstance(fit, str):
+        fit = (fit,)
+    try:
+        names = list(fit)
+    except TypeError:
+        raise ValueError(f"tl.cnv_states_fit: fit={fit!r} must be a sequence of parameter names") from None
+    unknown = [k for k in names if k not in _NAMES]
+    if unknown or not names:
+        raise ValueError(f"tl.cnv_states_fit: fit={fit!r} must be a non-empty subset of {_NAMES}")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+        raise ValueError(f"tl.cnv_states_fit: max_iter={max_iter!r} must be an int >= 1")
+    try:
+        tol_f = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"tl.cnv_states_fit: tol={tol!r} must be a number") from None
+    if isinstance(tol, bool) or not (math.isfinite(tol_f) and tol_f >= 0.0):
+        raise ValueError(f"tl.cnv_states_fit: tol={tol!r} must be finite and >= 0")
+    return [k for k in _NAMES if k in names], tol_f
 
 
 def _as_dict(a, sigma, p):
@@ -99,83 +120,18 @@ def cnv_states_fit(adata, use_rep="cnv", key_added="cnv_states_fit", inplace=Tru
     whose emission overflows under the start values: ``(|x| + amplitude)^2 / (2 sigma^2)`` must be finite for the stored
     value of the largest magnitude.
     """
-    key = f"X_{use_rep}"
-    if key not in adata.obsm:
-        raise KeyError(f"tl.cnv_states_fit: {key} not found in adata.obsm. Did you run `tl.infercnv`?")
-    if use_rep not in adata.uns or "chr_pos" not in adata.uns[use_rep]:
-        raise KeyError(f"tl.cnv_states_fit: chr_pos not found in adata.uns['{use_rep}']. Did you run `tl.infercnv`?")
-    x = adata.obsm[key]
-    if len(x.shape) != 2:
-        raise ValueError("tl.cnv_states_fit: X must be 2-D")
-    n, w = int(x.shape[0]), int(x.shape[1])
-    if n < 1 or w < 1:
-        raise ValueError(f"tl.cnv_states_fit: empty matrix of shape {(n, w)}")
-    if w > _lib.ICV_POSTERIOR_MAX_WINDOWS:
-        raise ValueError(f"tl.cnv_states_fit: {w} windows; the kernel keeps a cell's windows and forward variables in "
-                         f"LDS and takes at most {_lib.ICV_POSTERIOR_MAX_WINDOWS}")
-    bounds = chromosome_bounds(adata.uns[use_rep]["chr_pos"], w)
-    amp = None if amplitude is None else _positive("amplitude", amplitude)
-    sig = None if sigma is None else _positive("sigma", sigma)
-    if switch_prob is None:
-        switch_prob = 1e-3
-    try:
-        p = float(switch_prob)
-    except (TypeError, ValueError):
-        raise ValueError(f"tl.cnv_states_fit: switch_prob={switch_prob!r} must be a number") from None
-    if isinstance(switch_prob, bool) or not 0.0 < p < 1.0:
-        raise ValueError(f"tl.cnv_states_fit: switch_prob={switch_prob!r} must lie in (0, 1)")
-    if not (p / 2.0 >= sys.float_info.min and 0.0 < 1.0 - p < 1.0):
-        raise ValueError(f"tl.cnv_states_fit: switch_prob={switch_prob!r} is too close to 0 or 1 for float64")
-    if isinstance(fit, str):
-        fit = (fit,)
-    try:
-        names = list(fit)
-    except TypeError:
-        raise ValueError(f"tl.cnv_states_fit: fit={fit!r} must be a sequence of parameter names") from None
-    unknown = [k for k in names if k not in _NAMES]
-    if unknown or not names:
-        raise ValueError(f"tl.cnv_states_fit: fit={fit!r} must be a non-empty subset of {_NAMES}")
-    fitted = [k for k in _NAMES if k in names]
-    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
-        raise ValueError(f"tl.cnv_states_fit: max_iter={max_iter!r} must be an int >= 1")
-    try:
-        tol_f = float(tol)
-    except (TypeError, ValueError):
-        raise ValueError(f"tl.cnv_states_fit: tol={tol!r} must be a number") from None
-    if isinstance(tol, bool) or not (math.isfinite(tol_f) and tol_f >= 0.0):
-        raise ValueError(f"tl.cnv_states_fit: tol={tol!r} must be finite and >= 0")
-
-    torch = _engine._torch()
-    dm = _engine.states_input(x)
-    t0 = time.perf_counter()
-    q, flag = _engine.states_rowsq(dm)
-    absmax = _engine.states_absmax(_engine.states_stored_values(dm))
-    q_host = q.cpu().numpy()
-    nonfinite, m = _engine.states_flag_and_absmax(flag, absmax)
-    if nonfinite:
-        raise ValueError(f"tl.cnv_states_fit: {key} has non-finite values")
-    try:
-        qs = math.fsum(q_host.tolist())
-    except OverflowError:
-        qs = math.inf
-    n_total = float(n) * float(w)
-    if sig is None:
-        sig = math.sqrt(qs / n_total)
-    if not math.isfinite(qs) or not math.isfinite(sig):
-        raise ValueError(f"tl.cnv_states_fit: the sum of squares of {key} overflows float64")
-    if amp is None:
-        amp = 2.0 * sig
-    t1 = time.perf_counter()
+    mo = resolve(adata, use_rep, "tl.cnv_states_fit", max_windows=_lib.ICV_POSTERIOR_MAX_WINDOWS,
+                 keeps="a cell's windows and forward variables", amplitude=amplitude, sigma=sigma,
+                 switch_prob=1e-3 if switch_prob is None else switch_prob, log_switch=False, sum_of_squares=True,
+                 then=lambda: _fit_options(fit, max_iter, tol))
+    fitted, tol_f = mo.rest
+    n, bounds, dm, amp, sig, p, qs, t1 = mo.n, mo.bounds, mo.dm, mo.amp, mo.sig, mo.p, mo.qs, mo.t1
+    n_total = float(n) * float(mo.w)
 
     cur = (amp, sig, p)
     history = [_as_dict(*cur)]
     n_iter, converged, stopped = 0, False, None
-    if sig != 0.0:  # (an all-zero matrix has nothing to fit)
-        h = 1.0 / (2.0 * sig * sig)
-        if not (math.isfinite(h) and h > 0.0 and math.isfinite(amp) and amp > 0.0):
-            raise ValueError(f"tl.cnv_states_fit: sigma={sig!r} / amplitude={amp!r} leave float64's range "
-                             "(1 / (2 sigma^2) must be finite and > 0)")
-        check_emissions("tl.cnv_states_fit", key, x, m, amp, h, sig)  # (later steps end as degenerate ones)
+    if mo.h is not None:  # (an all-zero matrix has nothing to fit; later overflowing steps end as degenerate ones)
         n_steps = n * sum(max(int(b) - int(a) - 1, 0) for a, b in zip(bounds[:-1], bounds[1:]))
         for _ in range(max_iter):
             a_, s_, p_ = cur
@@ -201,7 +157,7 @@ def cnv_states_fit(adata, use_rep="cnv", key_added="cnv_states_fit", inplace=Tru
     info = None
     if return_info:
         info = {"history": history, "n_iter": n_iter, "converged": converged, "fit": fitted,
-                "stage_ms": {"rowsq": (t1 - t0) * 1e3, "e_steps": (t2 - t1) * 1e3}}
+                "stage_ms": {"rowsq": (t1 - mo.t0) * 1e3, "e_steps": (t2 - t1) * 1e3}}
         if stopped is not None:
             info["stopped"] = stopped
     if inplace:

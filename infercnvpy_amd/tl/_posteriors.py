@@ -9,24 +9,10 @@ exponential of ``tl.tsne``), and the filter forms every run's mean P(neutral) fr
 """
 from __future__ import annotations
 
-import math
-import sys
 import time
 
-import numpy as np
-
 from .. import _engine, _lib
-from ._states import check_emissions, chromosome_bounds
-
-
-def _positive(name, value):
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"tl.cnv_posteriors: {name}={value!r} must be a number") from None
-    if isinstance(value, bool) or not (math.isfinite(v) and v > 0):
-        raise ValueError(f"tl.cnv_posteriors: {name}={value!r} must be finite and > 0")
-    return v
+from ._hmm import chromosome_bounds, resolve
 
 
 def cnv_posteriors(adata, use_rep="cnv", key_added="cnv_posterior", inplace=True, *, amplitude=None, sigma=None,
@@ -73,83 +59,31 @@ def cnv_posteriors(adata, use_rep="cnv", key_added="cnv_posterior", inplace=True
     ``(|x| + amplitude)^2 / (2 sigma^2)`` must be finite for the stored value of the largest magnitude (read back with
     the flag); the posteriors of its chromosome would be 0 / 0 otherwise.
     """
-    key = f"X_{use_rep}"
-    if key not in adata.obsm:
-        raise KeyError(f"tl.cnv_posteriors: {key} not found in adata.obsm. Did you run `tl.infercnv`?")
-    if use_rep not in adata.uns or "chr_pos" not in adata.uns[use_rep]:
-        raise KeyError(f"tl.cnv_posteriors: chr_pos not found in adata.uns['{use_rep}']. Did you run `tl.infercnv`?")
-    x = adata.obsm[key]
-    if len(x.shape) != 2:
-        raise ValueError("tl.cnv_posteriors: X must be 2-D")
-    n, w = int(x.shape[0]), int(x.shape[1])
-    if n < 1 or w < 1:
-        raise ValueError(f"tl.cnv_posteriors: empty matrix of shape {(n, w)}")
-    if w > _lib.ICV_POSTERIOR_MAX_WINDOWS:
-        raise ValueError(f"tl.cnv_posteriors: {w} windows; the kernel keeps a cell's windows and forward variables in "
-                         f"LDS and takes at most {_lib.ICV_POSTERIOR_MAX_WINDOWS}")
-    bounds = chromosome_bounds(adata.uns[use_rep]["chr_pos"], w)
     from_states = False
     if amplitude is None and sigma is None and switch_prob is None and states_key in adata.uns:
         stored = adata.uns[states_key]
         if isinstance(stored, dict) and "params" in stored:
             amplitude, sigma, switch_prob = (stored["params"][k] for k in ("amplitude", "sigma", "switch_prob"))
             from_states = True
-    if from_states and sigma == 0:  # what tl.cnv_states leaves for an all-zero matrix
-        amp, sig = 0.0, 0.0
-    else:
-        amp = None if amplitude is None else _positive("amplitude", amplitude)
-        sig = None if sigma is None else _positive("sigma", sigma)
-    if switch_prob is None:
-        switch_prob = 1e-3
-    try:
-        p = float(switch_prob)
-    except (TypeError, ValueError):
-        raise ValueError(f"tl.cnv_posteriors: switch_prob={switch_prob!r} must be a number") from None
-    if isinstance(switch_prob, bool) or not 0.0 < p < 1.0:
-        raise ValueError(f"tl.cnv_posteriors: switch_prob={switch_prob!r} must lie in (0, 1)")
-    ps, pw = 1.0 - p, p / 2.0
-    if not (pw >= sys.float_info.min and 0.0 < ps < 1.0):
-        raise ValueError(f"tl.cnv_posteriors: switch_prob={switch_prob!r} is too close to 0 or 1 for float64")
-
+    mo = resolve(adata, use_rep, "tl.cnv_posteriors", max_windows=_lib.ICV_POSTERIOR_MAX_WINDOWS,
+                 keeps="a cell's windows and forward variables", amplitude=amplitude, sigma=sigma,
+                 switch_prob=1e-3 if switch_prob is None else switch_prob, log_switch=False, sum_of_squares=False,
+                 zero_model=from_states and sigma == 0)  # (what tl.cnv_states leaves for an all-zero matrix)
+    n, w, bounds, amp, sig, p, on_device = mo.n, mo.w, mo.bounds, mo.amp, mo.sig, mo.p, mo.on_device
     torch = _engine._torch()
-    on_device = isinstance(x, (_engine.PackedCsr, torch.Tensor))
-    dm = _engine.states_input(x)
-    t0 = time.perf_counter()
-    q, flag = _engine.states_rowsq(dm)
-    absmax = _engine.states_absmax(_engine.states_stored_values(dm))
-    if sig is None:
-        q_host = q.cpu().numpy()
-    nonfinite, m = _engine.states_flag_and_absmax(flag, absmax)
-    if nonfinite:
-        raise ValueError(f"tl.cnv_posteriors: {key} has non-finite values")
-    if sig is None:
-        try:
-            sig = math.sqrt(math.fsum(q_host.tolist()) / (float(n) * float(w)))
-        except OverflowError:
-            sig = math.inf
-        if not math.isfinite(sig):
-            raise ValueError(f"tl.cnv_posteriors: the default sigma of {key} overflows float64; pass sigma")
-    if amp is None:
-        amp = 2.0 * sig
-    t1 = time.perf_counter()
-    with torch.cuda.device(dm.device):
-        if sig == 0.0:  # an all-zero matrix: every window is neutral
+    with torch.cuda.device(mo.dm.device):
+        if mo.h is None:  # an all-zero matrix: every window is neutral
             neutral = torch.ones((n, w), dtype=torch.float64, device="cuda")
             loss = torch.zeros((n, w), dtype=torch.float64, device="cuda") if all_states else None
             gain = torch.zeros((n, w), dtype=torch.float64, device="cuda") if all_states else None
         else:
-            h = 1.0 / (2.0 * sig * sig)
-            if not (math.isfinite(h) and h > 0.0 and math.isfinite(amp) and amp > 0.0):
-                raise ValueError(f"tl.cnv_posteriors: sigma={sig!r} / amplitude={amp!r} leave float64's range "
-                                 "(1 / (2 sigma^2) must be finite and > 0)")
-            check_emissions("tl.cnv_posteriors", key, x, m, amp, h, sig)
-            neutral, loss, gain = _engine.posterior_chains(dm, bounds, amplitude=amp, h=h, ps=ps, pw=pw,
+            neutral, loss, gain = _engine.posterior_chains(mo.dm, bounds, amplitude=amp, h=mo.h, ps=1.0 - p, pw=p / 2.0,
                                                            all_states=all_states)
         info = None
         if return_info:
             torch.cuda.current_stream().synchronize()
             info = {"amplitude": amp, "sigma": sig, "switch_prob": p, "n_chromosomes": int(bounds.shape[0]) - 1,
-                    "stage_ms": {"rowsq": (t1 - t0) * 1e3, "chains": (time.perf_counter() - t1) * 1e3}}
+                    "stage_ms": {"rowsq": (mo.t1 - mo.t0) * 1e3, "chains": (time.perf_counter() - mo.t1) * 1e3}}
         if not on_device:
             neutral = neutral.cpu().numpy()
             if all_states:

@@ -222,3 +222,29 @@ def test_errors():
     del ad.uns["cnv"]["chr_pos"]
     with pytest.raises(KeyError, match=r"chr_pos not found in adata.uns\['cnv'\]. Did you run `tl.infercnv`"):
         cnv.tl.cnv_states_fit(ad)
+
+
+@pytest.mark.parametrize("sigma", [None, 0.2], ids=["all_none", "sigma_given"])
+def test_the_three_functions_resolve_one_model_from_one_matrix(sigma):
+    """Why tl/_hmm.py exists: tl.cnv_states, tl.cnv_posteriors (on an adata without stored calls) and the start of
+    tl.cnv_states_fit derive the same (amplitude, sigma, switch_prob), the oracle's, bit for bit."""
+    import torch
+
+    import infercnvpy_amd as cnv
+
+    c = so.planted(40, [20, 9], 5)
+    pos = c["chr_pos"]
+    dense32 = c["x"].toarray().astype(np.float32)
+    for name, xin, host in (("csr_float64", c["x"], c["x"]), ("cuda_float32", torch.from_numpy(dense32).cuda(), dense32)):
+        sig = so.default_sigma(host) if sigma is None else sigma
+        want = {"amplitude": 2.0 * sig, "sigma": sig, "switch_prob": 1e-3}
+        called, fresh = _adata(xin, pos), _adata(xin, pos)
+        cnv.tl.cnv_states(called, sigma=sigma)
+        cnv.tl.cnv_posteriors(fresh, sigma=sigma)
+        assert "cnv_states" not in fresh.uns
+        _, info = _fit(xin, pos, sigma=sigma, max_iter=1)
+        models = [called.uns["cnv_states"]["params"], fresh.uns["cnv_posterior"]["params"], info["history"][0], want]
+        assert all(type(m[k]) is float for m in models for k in fo.NAMES), name
+        bits = [np.array([m[k] for k in fo.NAMES], dtype=np.float64).tobytes() for m in models]
+        print(f"{name}: {models[0]}")
+        assert bits[0] == bits[1] == bits[2] == bits[3], (name, models)
