@@ -1563,27 +1563,34 @@ def knn_fuzzy(knn_dist, n_neighbors):
     return rho, sigma, w
 
 
-def knn_symmetrize(knn_idx, weights, n_neighbors):
-    """C = A + A^T - A o A^T of the membership strengths as canonical CSR, float32, no stored zeros: device tensors
-    (indptr int64, indices int32, data float32)."""
+def _symmetrize(count_fn, fill_fn, knn_idx, values, k_arg):
+    """The canonical CSR (indptr int64, indices int32, data float32; device tensors) that ``count_fn`` / ``fill_fn``
+    build from the n x m neighbour table and its float64 values: row lengths, icv_row_offsets, fill."""
     torch = _torch()
     lib = _lib.load()
-    n, km1 = knn_idx.shape
-    k = int(n_neighbors)
-    assert knn_idx.is_cuda and knn_idx.dtype == torch.int32 and knn_idx.is_contiguous() and km1 == k - 1
-    assert weights.dtype == torch.float64 and weights.is_contiguous() and tuple(weights.shape) == (n, km1)
+    n = knn_idx.shape[0]
+    assert knn_idx.is_cuda and knn_idx.dtype == torch.int32 and knn_idx.is_contiguous()
+    assert values.dtype == torch.float64 and values.is_contiguous() and values.shape == knn_idx.shape
     with torch.cuda.device(knn_idx.device):
         st = _stream_ptr(torch)
         counts = torch.empty(n, dtype=torch.int64, device="cuda")
-        _lib.check(lib.icv_knn_symmetrize_count(_ptr(knn_idx), _ptr(weights), n, k, _ptr(counts), st))
+        _lib.check(count_fn(_ptr(knn_idx), _ptr(values), n, k_arg, _ptr(counts), st))
         indptr = torch.empty(n + 1, dtype=torch.int64, device="cuda")
         _lib.check(lib.icv_row_offsets(_ptr(counts), n, _ptr(indptr), st))
         nnz = int(indptr[-1].item())
         indices = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
         data = torch.empty(max(nnz, 1), dtype=torch.float32, device="cuda")
-        _lib.check(lib.icv_knn_symmetrize_fill(_ptr(knn_idx), _ptr(weights), n, k, _ptr(indptr), nnz, _ptr(indices),
-                                               _ptr(data), st))
+        _lib.check(fill_fn(_ptr(knn_idx), _ptr(values), n, k_arg, _ptr(indptr), nnz, _ptr(indices), _ptr(data), st))
     return indptr, indices[:nnz], data[:nnz]
+
+
+def knn_symmetrize(knn_idx, weights, n_neighbors):
+    """C = A + A^T - A o A^T of the membership strengths as canonical CSR, float32, no stored zeros: device tensors
+    (indptr int64, indices int32, data float32)."""
+    lib = _lib.load()
+    k = int(n_neighbors)
+    assert knn_idx.shape[1] == k - 1
+    return _symmetrize(lib.icv_knn_symmetrize_count, lib.icv_knn_symmetrize_fill, knn_idx, weights, k)
 
 
 def knn_sorted_rows(knn_idx, knn_dist):
@@ -1598,6 +1605,38 @@ def knn_sorted_rows(knn_idx, knn_dist):
         _lib.check(lib.icv_knn_sort_rows(_ptr(indptr), n, _ptr(knn_idx), _ptr(knn_dist), _ptr(cols), _ptr(vals),
                                          _stream_ptr(torch)))
     return indptr, cols.reshape(-1), vals.reshape(-1)
+
+
+# ---- what tl.leiden, tl.umap and tl.tsne share ---------------------------------------------------------------------------
+def _graph_csr(who, indptr, indices, data, dtypes):
+    """(indptr, indices, data, n, nnz) of the device CSR graph (indptr int64 n + 1, indices int32, data of one of the
+    torch ``dtypes``), contiguous; ValueError for row pointers the kernels could not trust and for 2^31 entries."""
+    torch = _torch()
+    n = indptr.numel() - 1
+    nnz = indices.numel()
+    assert indptr.is_cuda and indptr.dtype == torch.int64 and indices.dtype == torch.int32 and data.numel() == nnz
+    assert data.dtype in dtypes and n >= 1
+    # the kernels trust the row pointers: check them here (two scalars and one comparison on the device)
+    if int(indptr[0].item()) != 0 or int(indptr[-1].item()) != nnz or bool((indptr[1:] < indptr[:-1]).any().item()):
+        raise ValueError(f"{who}: indptr must start at 0, be non-decreasing and end at the number of stored entries")
+    if nnz >= 1 << 31:
+        raise ValueError(f"{who}: at most 2^31 - 1 stored entries are supported")
+    with torch.cuda.device(indptr.device):
+        return indptr.contiguous(), indices.contiguous(), data.contiguous(), n, nnz
+
+
+def _workspace(fn, *args):
+    """The uint8 device tensor (current device) of the size the library's ``fn(*args, &bytes)`` asks for."""
+    need = C.c_int64(0)
+    _lib.check(fn(*args, C.byref(need)))
+    return _torch().empty(need.value, dtype=_torch().uint8, device="cuda")
+
+
+def _add_stage_ms(stage_ms, names, ms):
+    """Add the milliseconds ``ms`` of the stages ``names`` to what the dict ``stage_ms`` holds (None: nothing)."""
+    if stage_ms is not None:
+        for name, v in zip(names, ms):
+            stage_ms[name] = stage_ms.get(name, 0.0) + float(v)
 
 
 # ---- tl.leiden: Leiden on the device (icv_leiden*, DESIGN.md 4.10) --------------------------------------------------------
@@ -1619,17 +1658,8 @@ def leiden_quantise(indptr, indices, data, use_weights=True):
     and total = the sum of the integer weights; ValueError for every violation of rule 1 or 2."""
     torch = _torch()
     lib = _lib.load()
-    n = indptr.numel() - 1
-    nnz = indices.numel()
-    assert indptr.is_cuda and indptr.dtype == torch.int64 and indices.dtype == torch.int32 and data.numel() == nnz
-    assert data.dtype in (torch.float32, torch.float64) and n >= 1
-    # the kernels trust the row pointers: check them here (two scalars and one comparison on the device)
-    if int(indptr[0].item()) != 0 or int(indptr[-1].item()) != nnz or bool((indptr[1:] < indptr[:-1]).any().item()):
-        raise ValueError("tl.leiden: indptr must start at 0, be non-decreasing and end at the number of stored entries")
-    if nnz >= 1 << 31:
-        raise ValueError("tl.leiden: at most 2^31 - 1 stored entries are supported")
+    indptr, indices, data, n, nnz = _graph_csr("tl.leiden", indptr, indices, data, (torch.float32, torch.float64))
     with torch.cuda.device(indptr.device):
-        indptr, indices, data = indptr.contiguous(), indices.contiguous(), data.contiguous()
         q_indptr = torch.empty(n + 1, dtype=torch.int64, device="cuda")
         q_indices = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
         q_w = torch.empty(max(nnz, 1), dtype=torch.int64, device="cuda")
@@ -1644,9 +1674,7 @@ def leiden_quantise(indptr, indices, data, use_weights=True):
 
 def leiden_workspace(n, nnz):
     """The uint8 device tensor leiden_iteration needs for a graph of n vertices and nnz integer entries."""
-    need = C.c_int64(0)
-    _lib.check(_lib.load().icv_leiden_workspace(n, nnz, C.byref(need)))
-    return _torch().empty(need.value, dtype=_torch().uint8, device="cuda")
+    return _workspace(_lib.load().icv_leiden_workspace, n, nnz)
 
 
 def leiden_iteration(q_indptr, q_indices, q_w, gom, seed, it, labels, workspace, stage_ms=None):
@@ -1734,32 +1762,20 @@ def umap_epochs(indptr, indices, data, y, *, a, b, gamma=1.0, negative_sample_ra
     of the validation and of the epochs (added to what it holds)."""
     torch = _torch()
     lib = _lib.load()
-    n = indptr.numel() - 1
-    nnz = indices.numel()
-    assert indptr.is_cuda and indptr.dtype == torch.int64 and indices.dtype == torch.int32 and data.numel() == nnz
-    assert data.dtype == torch.float32 and n >= 1
-    assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.dim() == 2 and y.shape[0] == n
-    # the kernels trust the row pointers: check them here (two scalars and one comparison on the device)
-    if int(indptr[0].item()) != 0 or int(indptr[-1].item()) != nnz or bool((indptr[1:] < indptr[:-1]).any().item()):
-        raise ValueError("tl.umap: indptr must start at 0, be non-decreasing and end at the number of stored entries")
-    if nnz >= 1 << 31:
-        raise ValueError("tl.umap: at most 2^31 - 1 stored entries are supported")
+    assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.dim() == 2
+    assert y.shape[0] == indptr.numel() - 1
+    indptr, indices, data, n, nnz = _graph_csr("tl.umap", indptr, indices, data, (torch.float32,))
     c = int(y.shape[1])
     epoch_end = n_epochs if epoch_end is None else epoch_end
     seed = int(random_state) & ((1 << 64) - 1)
     with torch.cuda.device(indptr.device):
         st = _stream_ptr(torch)
-        indptr, indices, data = indptr.contiguous(), indices.contiguous(), data.contiguous()
-        need = C.c_int64(0)
-        _lib.check(lib.icv_umap_workspace(n, nnz, c, C.byref(need)))
-        ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+        ws = _workspace(lib.icv_umap_workspace, n, nnz, c)
         ms = (C.c_float * 2)() if stage_ms is not None else None
         _lib.check(lib.icv_umap_epochs(_ptr(indptr), _ptr(indices), _ptr(data), n, nnz, c, float(a), float(b),
                                        float(gamma), int(negative_sample_rate), float(initial_alpha), int(n_epochs),
                                        int(epoch_begin), int(epoch_end), seed, _ptr(y), _ptr(ws), ms, st))
-        if stage_ms is not None:
-            stage_ms["validation_ms"] = stage_ms.get("validation_ms", 0.0) + float(ms[0])
-            stage_ms["epochs_ms"] = stage_ms.get("epochs_ms", 0.0) + float(ms[1])
+        _add_stage_ms(stage_ms, ("validation_ms", "epochs_ms"), ms)
     return y
 
 
@@ -1782,23 +1798,8 @@ def tsne_affinities(knn_dist, perplexity):
 def tsne_symmetrize(knn_idx, cond):
     """W = A + A^T of the conditional affinities as canonical CSR, float32, no stored zeros: device tensors (indptr int64,
     indices int32, data float32)."""
-    torch = _torch()
     lib = _lib.load()
-    n, kk = knn_idx.shape
-    assert knn_idx.is_cuda and knn_idx.dtype == torch.int32 and knn_idx.is_contiguous()
-    assert cond.dtype == torch.float64 and cond.is_contiguous() and tuple(cond.shape) == (n, kk)
-    with torch.cuda.device(knn_idx.device):
-        st = _stream_ptr(torch)
-        counts = torch.empty(n, dtype=torch.int64, device="cuda")
-        _lib.check(lib.icv_tsne_symmetrize_count(_ptr(knn_idx), _ptr(cond), n, kk, _ptr(counts), st))
-        indptr = torch.empty(n + 1, dtype=torch.int64, device="cuda")
-        _lib.check(lib.icv_row_offsets(_ptr(counts), n, _ptr(indptr), st))
-        nnz = int(indptr[-1].item())
-        indices = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
-        data = torch.empty(max(nnz, 1), dtype=torch.float32, device="cuda")
-        _lib.check(lib.icv_tsne_symmetrize_fill(_ptr(knn_idx), _ptr(cond), n, kk, _ptr(indptr), nnz, _ptr(indices),
-                                                _ptr(data), st))
-    return indptr, indices[:nnz], data[:nnz]
+    return _symmetrize(lib.icv_tsne_symmetrize_count, lib.icv_tsne_symmetrize_fill, knn_idx, cond, int(knn_idx.shape[1]))
 
 
 def tsne_iterations(indptr, indices, data, y, update, gains, *, early_exaggeration=12.0, exaggeration_iters=250,
@@ -1809,32 +1810,19 @@ def tsne_iterations(indptr, indices, data, y, update, gains, *, early_exaggerati
     of the validation and of the iterations (added to what it holds)."""
     torch = _torch()
     lib = _lib.load()
-    n = indptr.numel() - 1
-    nnz = indices.numel()
-    assert indptr.is_cuda and indptr.dtype == torch.int64 and indices.dtype == torch.int32 and data.numel() == nnz
-    assert data.dtype == torch.float32 and n >= 1
     for s in (y, update, gains):
         assert s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and s.dim() == 2 and s.shape == y.shape
-    assert y.shape[0] == n
-    # the kernels trust the row pointers: check them here (two scalars and one comparison on the device)
-    if int(indptr[0].item()) != 0 or int(indptr[-1].item()) != nnz or bool((indptr[1:] < indptr[:-1]).any().item()):
-        raise ValueError("tl.tsne: indptr must start at 0, be non-decreasing and end at the number of stored entries")
-    if nnz >= 1 << 31:
-        raise ValueError("tl.tsne: at most 2^31 - 1 stored entries are supported")
+    assert y.shape[0] == indptr.numel() - 1
+    indptr, indices, data, n, nnz = _graph_csr("tl.tsne", indptr, indices, data, (torch.float32,))
     c = int(y.shape[1])
     with torch.cuda.device(indptr.device):
         st = _stream_ptr(torch)
-        indptr, indices, data = indptr.contiguous(), indices.contiguous(), data.contiguous()
-        need = C.c_int64(0)
-        _lib.check(lib.icv_tsne_workspace(n, nnz, c, C.byref(need)))
-        ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+        ws = _workspace(lib.icv_tsne_workspace, n, nnz, c)
         ms = (C.c_float * 2)() if stage_ms is not None else None
         _lib.check(lib.icv_tsne_iterations(_ptr(indptr), _ptr(indices), _ptr(data), n, nnz, c, float(early_exaggeration),
                                            int(exaggeration_iters), float(learning_rate), int(iter_begin), int(iter_end),
                                            _ptr(y), _ptr(update), _ptr(gains), _ptr(ws), ms, st))
-        if stage_ms is not None:
-            stage_ms["validation_ms"] = stage_ms.get("validation_ms", 0.0) + float(ms[0])
-            stage_ms["iterations_ms"] = stage_ms.get("iterations_ms", 0.0) + float(ms[1])
+        _add_stage_ms(stage_ms, ("validation_ms", "iterations_ms"), ms)
     return y, update, gains
 
 

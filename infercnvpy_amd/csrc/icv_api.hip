@@ -38,6 +38,7 @@
 #include "icv_corr.hpp"
 #include "icv_pca.hpp"
 #include "icv_knn.hpp"
+#include "icv_graph.hpp"
 #include "icv_leiden.hpp"
 #include "icv_umap.hpp"
 #include "icv_tsne.hpp"
@@ -3194,6 +3195,117 @@ int icv_group_sums(const double* values, const int32_t* group, int64_t n, int32_
 
 }  // extern "C"
 
+// ---- what pp.neighbors, tl.leiden, tl.umap and tl.tsne share ---------------------------------------------------------
+namespace {
+#define ICV_TRY(expr)              \
+    do {                           \
+        const int rc_ = (expr);    \
+        if (rc_ != ICV_OK) return rc_; \
+    } while (0)
+
+inline dim3 ld_grid(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
+
+// a workspace laid out as segments of whole 256-byte units: seg(b) is the offset of the next one, seg.o the total
+struct Seg {
+    size_t o = 0;
+    size_t operator()(size_t b) {
+        const size_t at = o;
+        o += (b + 255) / 256 * 256;
+        return at;
+    }
+};
+
+// The event pair behind stage_ms (nothing is created or recorded without it): toc(slot) waits for the stage and adds
+// its milliseconds to ms[slot], which for a slot that is timed once is the stage's time itself.
+struct StageTimer {
+    hipStream_t st;
+    bool on;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float ms[4] = {0, 0, 0, 0};
+    StageTimer(hipStream_t s, const float* stage_ms) : st(s), on(stage_ms != nullptr) {}
+    ~StageTimer() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+    hipError_t create() {
+        if (!on) return hipSuccess;
+        const hipError_t e = hipEventCreate(&ev0);
+        return e != hipSuccess ? e : hipEventCreate(&ev1);
+    }
+    hipError_t tic() { return on ? hipEventRecord(ev0, st) : hipSuccess; }
+    hipError_t toc(int slot) {
+        if (!on) return hipSuccess;
+        hipError_t e = hipEventRecord(ev1, st);
+        if (e != hipSuccess) return e;
+        e = hipEventSynchronize(ev1);
+        if (e != hipSuccess) return e;
+        float t = 0;
+        e = hipEventElapsedTime(&t, ev0, ev1);
+        ms[slot] += t;
+        return e;
+    }
+};
+
+bool graph_sizes_ok(int64_t n, int64_t nnz) { return n >= 1 && n <= (int64_t)1 << 30 && nnz >= 0 && nnz < (int64_t)1 << 31; }
+bool components_ok(int32_t c) { return c == 2 || c == 3; }
+
+// the report of the flags of icv::graph_entry_flags, in the order they are tested; ICV_OK without one
+int graph_flags_error(const char* who, unsigned f) {
+    const char* what = f & 8    ? "the adjacency matrix has a column index out of range"
+                       : f & 16 ? "the rows of the adjacency matrix must be sorted, without duplicates"
+                       : f & 1  ? "the adjacency matrix has non-finite values"
+                       : f & 2  ? "the adjacency matrix has negative values"
+                       : f & 4  ? "the adjacency matrix has stored diagonal entries"
+                       : f & 32 ? "the adjacency matrix is not symmetric"
+                                : nullptr;
+    return what ? fail(ICV_ERR_INVALID, std::string(who) + ": " + what) : ICV_OK;
+}
+
+// k_graph_check on the float32 graph and its four words, read back (head: 16 bytes of the workspace or more)
+struct GraphCheck {
+    unsigned flags, n_long;
+    float w_max;      // largest finite non-negative weight
+    int64_t longest;  // entries of the longest row
+};
+int run_graph_check(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, unsigned* head,
+                    int32_t* long_list, hipStream_t st, GraphCheck* out) {
+    HIP_TRY(hipMemsetAsync(head, 0, 16, st));
+    hipLaunchKernelGGL(icv::k_graph_check, ld_grid(n, 4), dim3(256), 0, st, indptr, indices, data, n, head, long_list);
+    HIP_TRY(hipGetLastError());
+    unsigned h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, head, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->flags = h[0], out->n_long = h[1], out->longest = (int64_t)h[3];
+    std::memcpy(&out->w_max, &h[2], 4);
+    return ICV_OK;
+}
+
+// A + A^T (SUM) or A + A^T - A o A^T of `per_row` neighbours per row: the row lengths, then the canonical CSR
+template <bool SUM>
+int symmetrize_count(const int32_t* knn_idx, const double* w, int64_t n, int per_row, int64_t* row_nnz, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(row_nnz, 0, (size_t)n * sizeof(int64_t), st));
+    hipLaunchKernelGGL(icv::k_knn_sym_count<SUM>, ld_grid(n * per_row), dim3(256), 0, st, knn_idx, w, n, per_row,
+                       reinterpret_cast<unsigned long long*>(row_nnz));
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+template <bool SUM>
+int symmetrize_fill(const int32_t* knn_idx, const double* w, int64_t n, int per_row, const int64_t* indptr, int64_t nnz,
+                    int32_t* indices, float* data, hipStream_t st) {
+    AsyncBuf cur, tc, tv;
+    HIP_TRY(cur.alloc((size_t)n * sizeof(unsigned), st));
+    HIP_TRY(tc.alloc((size_t)nnz * sizeof(int32_t), st));
+    HIP_TRY(tv.alloc((size_t)nnz * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(cur.p, 0, (size_t)n * sizeof(unsigned), st));
+    hipLaunchKernelGGL(icv::k_knn_sym_fill<SUM>, ld_grid(n * per_row), dim3(256), 0, st, knn_idx, w, n, per_row, indptr,
+                       cur.as<unsigned>(), tc.as<int32_t>(), tv.as<float>());
+    hipLaunchKernelGGL(icv::k_knn_sort_rows, ld_grid(n, 4), dim3(256), 0, st, indptr, n, tc.as<int32_t>(), tv.as<float>(),
+                       indices, data);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+}  // namespace
+
 // ---- pp.neighbors (csrc/icv_knn.hpp) ---------------------------------------------------------------------------------
 namespace {
 struct KnnGeom {
@@ -3213,12 +3325,7 @@ struct KnnGeom {
         rows_per = (n + 1023) / 1024;
         if (rows_per < 64) rows_per = 64;
         n_slabs = (int)((n + rows_per - 1) / rows_per);
-        size_t o = 0;
-        auto seg = [&](size_t b) {
-            const size_t at = o;
-            o += (b + 255) / 256 * 256;
-            return at;
-        };
+        Seg seg;
         off_partial = seg((size_t)n_slabs * d * 8);
         off_mu = seg(256 * 4);
         off_flags = seg(16);
@@ -3227,7 +3334,7 @@ struct KnnGeom {
         off_cand = seg((size_t)n * parts * 2 * L * 4);
         off_bound = seg((size_t)n * parts * 2 * 4);
         off_redo = seg((size_t)n * 4);
-        bytes = o;
+        bytes = seg.o;
     }
 };
 int knn_args_ok(int64_t n, int32_t d, int32_t k) {
@@ -3337,12 +3444,7 @@ int icv_knn_symmetrize_count(const int32_t* knn_idx, const double* weights, int6
                              void* stream) {
     if (!knn_idx || !weights || !row_nnz || n < 1 || k < 2 || k > 64)
         return fail(ICV_ERR_INVALID, "bad knn_symmetrize_count arguments");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(row_nnz, 0, (size_t)n * sizeof(int64_t), st));
-    hipLaunchKernelGGL(icv::k_knn_sym_count<false>, dim3((unsigned)((n * (k - 1) + 255) / 256)), dim3(256), 0, st, knn_idx, weights,
-                       n, k - 1, reinterpret_cast<unsigned long long*>(row_nnz));
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return symmetrize_count<false>(knn_idx, weights, n, k - 1, row_nnz, static_cast<hipStream_t>(stream));
 }
 
 int icv_knn_symmetrize_fill(const int32_t* knn_idx, const double* weights, int64_t n, int32_t k, const int64_t* indptr,
@@ -3350,18 +3452,7 @@ int icv_knn_symmetrize_fill(const int32_t* knn_idx, const double* weights, int64
     if (!knn_idx || !weights || !indptr || !indices || !data || n < 1 || k < 2 || k > 64 || nnz < 0 ||
         nnz > 2 * n * (int64_t)(k - 1))
         return fail(ICV_ERR_INVALID, "bad knn_symmetrize_fill arguments");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    AsyncBuf cur, tc, tv;
-    HIP_TRY(cur.alloc((size_t)n * sizeof(unsigned), st));
-    HIP_TRY(tc.alloc((size_t)nnz * sizeof(int32_t), st));
-    HIP_TRY(tv.alloc((size_t)nnz * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(cur.p, 0, (size_t)n * sizeof(unsigned), st));
-    hipLaunchKernelGGL(icv::k_knn_sym_fill<false>, dim3((unsigned)((n * (k - 1) + 255) / 256)), dim3(256), 0, st, knn_idx, weights,
-                       n, k - 1, indptr, cur.as<unsigned>(), tc.as<int32_t>(), tv.as<float>());
-    hipLaunchKernelGGL(icv::k_knn_sort_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, indptr, n, tc.as<int32_t>(),
-                       tv.as<float>(), indices, data);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return symmetrize_fill<false>(knn_idx, weights, n, k - 1, indptr, nnz, indices, data, static_cast<hipStream_t>(stream));
 }
 
 int icv_knn_sort_rows(const int64_t* indptr, int64_t n, const int32_t* cols_in, const float* vals_in, int32_t* cols,
@@ -3383,12 +3474,7 @@ struct LdGeom {
     size_t rp[2], col[2], w[2], loop[2], k, comm[2], K, cnt, sub, Ks, cs, ext, want, wantw, sel, o2c, fa, fb, ra, rb, fl, ll,
         hk, hv, keys[2], vals[2], counters, bytes;
     LdGeom(int64_t n, int64_t nnz) {
-        size_t o = 0;
-        auto seg = [&](size_t b) {
-            const size_t at = o;
-            o += (b + 255) / 256 * 256;
-            return at;
-        };
+        Seg seg;
         const size_t N = (size_t)n + 1, Z = (size_t)nnz + 1;
         for (int i = 0; i < 2; ++i) {
             rp[i] = seg(N * 8), col[i] = seg(Z * 4), w[i] = seg(Z * 8), loop[i] = seg(N * 8), comm[i] = seg(N * 4);
@@ -3399,11 +3485,9 @@ struct LdGeom {
         fa = seg(N * 4), fb = seg(N * 4), ra = seg(N * 4), rb = seg(N * 4), fl = seg(N * 4), ll = seg(N * 4);
         hk = seg(2 * Z * 4), hv = seg(2 * Z * 8);  // k_ld_decide_long's tables: 2 slots per stored entry
         counters = seg(64);
-        bytes = o;
+        bytes = seg.o;
     }
 };
-inline dim3 ld_grid(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
-
 // exclusive prefix sums of m int32 flags (rocprim; its temporary comes from the stream's pool)
 int ld_scan(const int32_t* in, int32_t* out, size_t m, hipStream_t st) {
     size_t tb = 0;
@@ -3413,12 +3497,6 @@ int ld_scan(const int32_t* in, int32_t* out, size_t m, hipStream_t st) {
     HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, in, out, (int32_t)0, m, rocprim::plus<int32_t>(), st));
     return ICV_OK;
 }
-#define ICV_TRY(expr)              \
-    do {                           \
-        const int rc_ = (expr);    \
-        if (rc_ != ICV_OK) return rc_; \
-    } while (0)
-
 struct LdLevel {
     int n;
     int64_t nnz;
@@ -3433,8 +3511,7 @@ struct LdLevel {
 extern "C" {
 
 int icv_leiden_workspace(int64_t n, int64_t nnz, int64_t* bytes) {
-    if (!bytes || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31)
-        return fail(ICV_ERR_INVALID, "bad leiden_workspace arguments");
+    if (!bytes || !graph_sizes_ok(n, nnz)) return fail(ICV_ERR_INVALID, "bad leiden_workspace arguments");
     *bytes = (int64_t)LdGeom(n, nnz).bytes;
     return ICV_OK;
 }
@@ -3442,7 +3519,7 @@ int icv_leiden_workspace(int64_t n, int64_t nnz, int64_t* bytes) {
 int icv_leiden_quantise(const int64_t* indptr, const int32_t* indices, const void* data, int32_t dtype, int64_t n,
                         int64_t nnz, int32_t use_weights, int64_t* q_indptr, int32_t* q_indices, int64_t* q_weights,
                         int64_t* result, void* stream) {
-    if (!indptr || !q_indptr || !result || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 ||
+    if (!indptr || !q_indptr || !result || !graph_sizes_ok(n, nnz) ||
         (nnz > 0 && (!indices || !data || !q_indices || !q_weights)) || (dtype != ICV_F32 && dtype != ICV_F64))
         return fail(ICV_ERR_INVALID, "bad leiden_quantise arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -3465,12 +3542,7 @@ int icv_leiden_quantise(const int64_t* indptr, const int32_t* indices, const voi
     HIP_TRY(hipMemcpyAsync(h, flg.p, 24, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const unsigned f = (unsigned)(h[0] & 0xFFFFFFFFu);
-    if (f & 8) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix has a column index out of range");
-    if (f & 16) return fail(ICV_ERR_INVALID, "tl.leiden: the rows of the adjacency matrix must be sorted, without duplicates");
-    if (f & 1) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix has non-finite values");
-    if (f & 2) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix has negative values");
-    if (f & 4) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix has stored diagonal entries");
-    if (f & 32) return fail(ICV_ERR_INVALID, "tl.leiden: the adjacency matrix is not symmetric");
+    ICV_TRY(graph_flags_error("tl.leiden", f));
     const unsigned __int128 total = ((unsigned __int128)h[2] << 32) + h[1];
     if ((f & 64) || total >= ((unsigned __int128)1 << 62))
         return fail(ICV_ERR_INVALID,
@@ -3491,9 +3563,8 @@ int icv_leiden_quantise(const int64_t* indptr, const int32_t* indices, const voi
 int icv_leiden_iteration(const int64_t* indptr, const int32_t* indices, const int64_t* weights, int64_t n, int64_t nnz,
                          double gom, uint64_t seed, int32_t iteration, int32_t* labels, void* workspace, int32_t* trace,
                          int32_t* n_levels, int64_t* n_moves, int32_t* bound_reached, float* stage_ms, void* stream) {
-    if (!indptr || !labels || !workspace || !trace || !n_levels || !n_moves || !bound_reached || n < 1 ||
-        n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 || (nnz > 0 && (!indices || !weights)) ||
-        !(gom >= 0.0) || !(gom <= 1.7976931348623157e308) || iteration < 0)
+    if (!indptr || !labels || !workspace || !trace || !n_levels || !n_moves || !bound_reached || !graph_sizes_ok(n, nnz) ||
+        (nnz > 0 && (!indices || !weights)) || !(gom >= 0.0) || !(gom <= 1.7976931348623157e308) || iteration < 0)
         return fail(ICV_ERR_INVALID, "bad leiden_iteration arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const LdGeom G(n, nnz);
@@ -3507,31 +3578,8 @@ int icv_leiden_iteration(const int64_t* indptr, const int32_t* indices, const in
     long long* hv = LD(long long, hv);
     unsigned* counters = LD(unsigned, counters);  // [0] wanting [1] selected [2] selected to empty [3] long rows
     unsigned long long* moves = reinterpret_cast<unsigned long long*>(counters + 4);
-    float ms[4] = {0, 0, 0, 0};  // local moving, refinement, aggregation, rest
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct EvGuard {
-        hipEvent_t *a, *b;
-        ~EvGuard() {
-            if (*a) (void)hipEventDestroy(*a);
-            if (*b) (void)hipEventDestroy(*b);
-        }
-    } guard{&ev0, &ev1};
-    if (stage_ms) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-    }
-    auto tic = [&]() -> hipError_t { return stage_ms ? hipEventRecord(ev0, st) : hipSuccess; };
-    auto toc = [&](int slot) -> hipError_t {
-        if (!stage_ms) return hipSuccess;
-        hipError_t e = hipEventRecord(ev1, st);
-        if (e != hipSuccess) return e;
-        e = hipEventSynchronize(ev1);
-        if (e != hipSuccess) return e;
-        float t = 0;
-        e = hipEventElapsedTime(&t, ev0, ev1);
-        ms[slot] += t;
-        return e;
-    };
+    StageTimer T(st, stage_ms);  // local moving, refinement, aggregation, rest
+    HIP_TRY(T.create());
 
     LdLevel L{(int)n, nnz, indptr, indices, reinterpret_cast<const long long*>(weights), nullptr, LD(int32_t, comm[0])};
     HIP_TRY(hipMemcpyAsync(L.comm, labels, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
@@ -3545,7 +3593,7 @@ int icv_leiden_iteration(const int64_t* indptr, const int32_t* indices, const in
         const int ln = L.n;
         const int max_rounds = 64 + (ln < 4096 ? ln : 4096);
         // strengths and the starting partition's sums
-        HIP_TRY(tic());
+        HIP_TRY(T.tic());
         HIP_TRY(hipMemsetAsync(K, 0, (size_t)ln * 8, st));
         HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)ln * 4, st));
         HIP_TRY(hipMemsetAsync(counters + 3, 0, 4, st));
@@ -3585,8 +3633,8 @@ int icv_leiden_iteration(const int64_t* indptr, const int32_t* indices, const in
             hipLaunchKernelGGL(icv::k_ld_apply_move, ld_grid(ln), dim3(256), 0, st, ln, sel, k, L.comm, K, cnt, moves);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(toc(0));
-        HIP_TRY(tic());
+        HIP_TRY(T.toc(0));
+        HIP_TRY(T.tic());
         // ---- refinement (K is now the communities' K_C)
         hipLaunchKernelGGL(icv::k_ld_refine_init, ld_grid(ln, 4), dim3(256), 0, st, ln, L.rp, L.col, L.w, k, L.comm, sub, Ks,
                            cs, ext);
@@ -3612,8 +3660,8 @@ int icv_leiden_iteration(const int64_t* indptr, const int32_t* indices, const in
                                sub, Ks, cs, ext);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(toc(1));
-        HIP_TRY(tic());
+        HIP_TRY(T.toc(1));
+        HIP_TRY(T.tic());
         trace[3 * level] = ln;
         trace[3 * level + 1] = r_move;
         trace[3 * level + 2] = r_ref;
@@ -3627,7 +3675,7 @@ int icv_leiden_iteration(const int64_t* indptr, const int32_t* indices, const in
         HIP_TRY(hipStreamSynchronize(st));
         if (n2 == ln) {
             done = true;
-            HIP_TRY(toc(2));
+            HIP_TRY(T.toc(2));
             break;
         }
         const int nx = (level & 1) ? 0 : 1;  // level 0 reads the caller's graph; buffers alternate above it
@@ -3675,19 +3723,19 @@ int icv_leiden_iteration(const int64_t* indptr, const int32_t* indices, const in
         hipLaunchKernelGGL(icv::k_ld_agg_rowptr, ld_grid(n2 + 1), dim3(256), 0, st, n2, nnz2, keys_in, rp2);
         HIP_TRY(hipGetLastError());
         L = LdLevel{n2, nnz2, rp2, col2, w2, loop2, comm2};
-        HIP_TRY(toc(2));
+        HIP_TRY(T.toc(2));
     }
     if (!done) *bound_reached = 1;
-    HIP_TRY(tic());
+    HIP_TRY(T.tic());
     hipLaunchKernelGGL(icv::k_ld_gather, ld_grid(n), dim3(256), 0, st, n, L.comm, o2c, labels);
     HIP_TRY(hipGetLastError());
     unsigned long long hm = 0;
     HIP_TRY(hipMemcpyAsync(&hm, moves, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(toc(3));
+    HIP_TRY(T.toc(3));
     *n_moves = (int64_t)hm;
     if (stage_ms)
-        for (int i = 0; i < 4; ++i) stage_ms[i] = ms[i];
+        for (int i = 0; i < 4; ++i) stage_ms[i] = T.ms[i];
 #undef LD
     return ICV_OK;
 }
@@ -3747,14 +3795,9 @@ namespace {
 struct UmGeom {
     size_t y2, long_list, head, bytes;  // the second position buffer, the long rows, flags / count / largest weight
     UmGeom(int64_t n, int32_t c) {
-        size_t o = 0;
-        auto seg = [&](size_t b) {
-            const size_t at = o;
-            o += (b + 255) / 256 * 256;
-            return at;
-        };
+        Seg seg;
         y2 = seg((size_t)n * c * 4), long_list = seg(((size_t)n + 1) * 4), head = seg(64);
-        bytes = o;
+        bytes = seg.o;
     }
 };
 inline bool um_finite(double x) { return x >= -1.7976931348623157e308 && x <= 1.7976931348623157e308; }
@@ -3763,8 +3806,7 @@ inline bool um_finite(double x) { return x >= -1.7976931348623157e308 && x <= 1.
 extern "C" {
 
 int icv_umap_workspace(int64_t n, int64_t nnz, int32_t n_components, int64_t* bytes) {
-    if (!bytes || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 ||
-        (n_components != 2 && n_components != 3))
+    if (!bytes || !graph_sizes_ok(n, nnz) || !components_ok(n_components))
         return fail(ICV_ERR_INVALID, "bad umap_workspace arguments");
     *bytes = (int64_t)UmGeom(n, n_components).bytes;
     return ICV_OK;
@@ -3774,8 +3816,8 @@ int icv_umap_epochs(const int64_t* indptr, const int32_t* indices, const float* 
                     int32_t n_components, double a, double b, double gamma, int32_t negative_sample_rate,
                     double initial_alpha, int32_t n_epochs, int32_t epoch_begin, int32_t epoch_end, uint64_t seed, float* y,
                     void* workspace, float* stage_ms, void* stream) {
-    if (!indptr || !y || !workspace || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 ||
-        (nnz > 0 && (!indices || !data)) || (n_components != 2 && n_components != 3) || !um_finite(a) || !(a > 0.0) ||
+    if (!indptr || !y || !workspace || !graph_sizes_ok(n, nnz) || (nnz > 0 && (!indices || !data)) ||
+        !components_ok(n_components) || !um_finite(a) || !(a > 0.0) ||
         !um_finite(b) || !(b > 0.0) || !um_finite(gamma) || !(gamma >= 0.0) || negative_sample_rate < 0 ||
         negative_sample_rate > icv::kUmMaxNegatives || !um_finite(initial_alpha) || !(initial_alpha >= 0.0) ||
         n_epochs < 1 || epoch_begin < 0 || epoch_end < epoch_begin || epoch_end > n_epochs)
@@ -3786,46 +3828,16 @@ int icv_umap_epochs(const int64_t* indptr, const int32_t* indices, const float* 
     float* y2 = reinterpret_cast<float*>(ws + G.y2);
     int32_t* long_list = reinterpret_cast<int32_t*>(ws + G.long_list);
     unsigned* head = reinterpret_cast<unsigned*>(ws + G.head);
-    float ms[2] = {0, 0};  // validation, epochs
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct EvGuard {
-        hipEvent_t *a, *b;
-        ~EvGuard() {
-            if (*a) (void)hipEventDestroy(*a);
-            if (*b) (void)hipEventDestroy(*b);
-        }
-    } guard{&ev0, &ev1};
-    if (stage_ms) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-    }
-    auto tic = [&]() -> hipError_t { return stage_ms ? hipEventRecord(ev0, st) : hipSuccess; };
-    auto toc = [&](int slot) -> hipError_t {
-        if (!stage_ms) return hipSuccess;
-        hipError_t e = hipEventRecord(ev1, st);
-        if (e != hipSuccess) return e;
-        e = hipEventSynchronize(ev1);
-        if (e != hipSuccess) return e;
-        return hipEventElapsedTime(&ms[slot], ev0, ev1);
-    };
+    StageTimer T(st, stage_ms);  // validation, epochs
+    HIP_TRY(T.create());
 
-    HIP_TRY(tic());
-    HIP_TRY(hipMemsetAsync(head, 0, 64, st));
-    hipLaunchKernelGGL(icv::k_um_check, ld_grid(n, 4), dim3(256), 0, st, indptr, indices, data, n, head, long_list);
-    HIP_TRY(hipGetLastError());
-    unsigned h[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, head, 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(toc(0));
-    const unsigned f = h[0], n_long = h[1];
-    if (f & 8) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix has a column index out of range");
-    if (f & 16) return fail(ICV_ERR_INVALID, "tl.umap: the rows of the adjacency matrix must be sorted, without duplicates");
-    if (f & 1) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix has non-finite values");
-    if (f & 2) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix has negative values");
-    if (f & 4) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix has stored diagonal entries");
-    if (f & 32) return fail(ICV_ERR_INVALID, "tl.umap: the adjacency matrix is not symmetric");
-    float w_max = 0.f;
-    std::memcpy(&w_max, &h[2], 4);
+    GraphCheck chk;
+    HIP_TRY(T.tic());
+    ICV_TRY(run_graph_check(indptr, indices, data, n, head, long_list, st, &chk));
+    HIP_TRY(T.toc(0));
+    ICV_TRY(graph_flags_error("tl.umap", chk.flags));
+    const unsigned n_long = chk.n_long;
+    const float w_max = chk.w_max;
 
     icv::UmEpoch P;
     P.a = a, P.b = b, P.c_att = (-2.0 * a) * b, P.c_rep = (2.0 * gamma) * b;
@@ -3834,7 +3846,7 @@ int icv_umap_epochs(const int64_t* indptr, const int32_t* indices, const float* 
     const unsigned short_blocks = (unsigned)((n + 3) / 4);
     const dim3 grid(short_blocks + n_long);
     float *src = y, *dst = y2;
-    HIP_TRY(tic());
+    HIP_TRY(T.tic());
     for (int32_t t = epoch_begin < 1 ? 1 : epoch_begin; t < epoch_end; ++t) {  // nothing is active in epoch 0
         P.alpha = initial_alpha * (1.0 - (double)t / (double)n_epochs);
         P.t = (double)t, P.tm1 = (double)(t - 1);
@@ -3849,8 +3861,8 @@ int icv_umap_epochs(const int64_t* indptr, const int32_t* indices, const float* 
     }
     HIP_TRY(hipGetLastError());
     if (src != y) HIP_TRY(hipMemcpyAsync(y, src, (size_t)n * n_components * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(toc(1));
-    if (stage_ms) stage_ms[0] = ms[0], stage_ms[1] = ms[1];
+    HIP_TRY(T.toc(1));
+    if (stage_ms) stage_ms[0] = T.ms[0], stage_ms[1] = T.ms[1];
     return ICV_OK;
 }
 
@@ -3863,19 +3875,14 @@ struct TsGeom {
     // tickets of k_ts_repulse, the long rows, flags / count / longest row
     size_t y2, u2, g2, zr[2], rr[2], hl[2], ticket, long_list, head, bytes, zero_begin, zero_end;
     TsGeom(int64_t n, int32_t c) {
-        size_t o = 0;
-        auto seg = [&](size_t b) {
-            const size_t at = o;
-            o += (b + 255) / 256 * 256;
-            return at;
-        };
+        Seg seg;
         y2 = seg((size_t)n * c * 4), u2 = seg((size_t)n * c * 4), g2 = seg((size_t)n * c * 4);
-        zero_begin = o;
+        zero_begin = seg.o;
         for (int s = 0; s < 2; ++s) zr[s] = seg((size_t)n * 8), rr[s] = seg((size_t)n * c * 8), hl[s] = seg(256);
         ticket = seg(((size_t)n + 255) / 256 * 4);
-        zero_end = o;
+        zero_end = seg.o;
         long_list = seg(((size_t)n + 1) * 4), head = seg(256);
-        bytes = o;
+        bytes = seg.o;
     }
 };
 }  // namespace
@@ -3896,35 +3903,18 @@ int icv_tsne_symmetrize_count(const int32_t* knn_idx, const double* cond, int64_
                               void* stream) {
     if (!knn_idx || !cond || !row_nnz || n < 1 || k < 1 || k > 63)
         return fail(ICV_ERR_INVALID, "bad tsne_symmetrize_count arguments");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(row_nnz, 0, (size_t)n * sizeof(int64_t), st));
-    hipLaunchKernelGGL(icv::k_knn_sym_count<true>, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, knn_idx, cond, n,
-                       k, reinterpret_cast<unsigned long long*>(row_nnz));
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return symmetrize_count<true>(knn_idx, cond, n, k, row_nnz, static_cast<hipStream_t>(stream));
 }
 
 int icv_tsne_symmetrize_fill(const int32_t* knn_idx, const double* cond, int64_t n, int32_t k, const int64_t* indptr,
                              int64_t nnz, int32_t* indices, float* data, void* stream) {
     if (!knn_idx || !cond || !indptr || !indices || !data || n < 1 || k < 1 || k > 63 || nnz < 0 || nnz > 2 * n * (int64_t)k)
         return fail(ICV_ERR_INVALID, "bad tsne_symmetrize_fill arguments");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    AsyncBuf cur, tc, tv;
-    HIP_TRY(cur.alloc((size_t)n * sizeof(unsigned), st));
-    HIP_TRY(tc.alloc((size_t)nnz * sizeof(int32_t), st));
-    HIP_TRY(tv.alloc((size_t)nnz * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(cur.p, 0, (size_t)n * sizeof(unsigned), st));
-    hipLaunchKernelGGL(icv::k_knn_sym_fill<true>, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, knn_idx, cond, n,
-                       k, indptr, cur.as<unsigned>(), tc.as<int32_t>(), tv.as<float>());
-    hipLaunchKernelGGL(icv::k_knn_sort_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, indptr, n, tc.as<int32_t>(),
-                       tv.as<float>(), indices, data);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return symmetrize_fill<true>(knn_idx, cond, n, k, indptr, nnz, indices, data, static_cast<hipStream_t>(stream));
 }
 
 int icv_tsne_workspace(int64_t n, int64_t nnz, int32_t n_components, int64_t* bytes) {
-    if (!bytes || n < 1 || n > (int64_t)1 << 30 || nnz < 0 || nnz >= (int64_t)1 << 31 ||
-        (n_components != 2 && n_components != 3))
+    if (!bytes || !graph_sizes_ok(n, nnz) || !components_ok(n_components))
         return fail(ICV_ERR_INVALID, "bad tsne_workspace arguments");
     *bytes = (int64_t)TsGeom(n, n_components).bytes;
     return ICV_OK;
@@ -3934,8 +3924,8 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
                         int32_t n_components, double early_exaggeration, int32_t exaggeration_iters, double learning_rate,
                         int32_t iter_begin, int32_t iter_end, float* y, float* update, float* gains, void* workspace,
                         float* stage_ms, void* stream) {
-    if (!indptr || !y || !update || !gains || !workspace || n < 1 || n > (int64_t)1 << 30 || nnz < 0 ||
-        nnz >= (int64_t)1 << 31 || (nnz > 0 && (!indices || !data)) || (n_components != 2 && n_components != 3) ||
+    if (!indptr || !y || !update || !gains || !workspace || !graph_sizes_ok(n, nnz) ||
+        (nnz > 0 && (!indices || !data)) || !components_ok(n_components) ||
         !um_finite(early_exaggeration) || !(early_exaggeration > 0.0) || !um_finite(learning_rate) ||
         !(learning_rate > 0.0) || exaggeration_iters < 0 || iter_begin < 0 || iter_end < iter_begin)
         return fail(ICV_ERR_INVALID, "bad tsne_iterations arguments");
@@ -3947,46 +3937,18 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
     unsigned* head = reinterpret_cast<unsigned*>(ws + G.head);
     unsigned* ticket = reinterpret_cast<unsigned*>(ws + G.ticket);
     auto u64 = [&](size_t at) { return reinterpret_cast<unsigned long long*>(ws + at); };
-    float ms[2] = {0, 0};  // validation, iterations
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct EvGuard {
-        hipEvent_t *a, *b;
-        ~EvGuard() {
-            if (*a) (void)hipEventDestroy(*a);
-            if (*b) (void)hipEventDestroy(*b);
-        }
-    } guard{&ev0, &ev1};
-    if (stage_ms) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-    }
-    auto tic = [&]() -> hipError_t { return stage_ms ? hipEventRecord(ev0, st) : hipSuccess; };
-    auto toc = [&](int slot) -> hipError_t {
-        if (!stage_ms) return hipSuccess;
-        hipError_t e = hipEventRecord(ev1, st);
-        if (e != hipSuccess) return e;
-        e = hipEventSynchronize(ev1);
-        if (e != hipSuccess) return e;
-        return hipEventElapsedTime(&ms[slot], ev0, ev1);
-    };
+    StageTimer T(st, stage_ms);  // validation, iterations
+    HIP_TRY(T.create());
 
-    HIP_TRY(tic());
-    HIP_TRY(hipMemsetAsync(head, 0, 64, st));
-    hipLaunchKernelGGL(icv::k_ts_check, ld_grid(n, 4), dim3(256), 0, st, indptr, indices, data, n, head, long_list);
-    HIP_TRY(hipGetLastError());
-    unsigned h[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, head, 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(toc(0));
-    const unsigned f = h[0], n_long = h[1];
-    if (f & 8) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has a column index out of range");
-    if (f & 16) return fail(ICV_ERR_INVALID, "tl.tsne: the rows of the adjacency matrix must be sorted, without duplicates");
-    if (f & 1) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has non-finite values");
-    if (f & 2) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has negative values");
-    if (f & 4) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has stored diagonal entries");
-    if (f & 32) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix is not symmetric");
-    if (f & 64) return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has values above 2 (affinities are at most 2)");
-    if ((int64_t)h[2] > icv::kTsMaxRow) return fail(ICV_ERR_UNSUPPORTED, "tl.tsne: a row has more than 2^22 stored entries");
+    GraphCheck chk;
+    HIP_TRY(T.tic());
+    ICV_TRY(run_graph_check(indptr, indices, data, n, head, long_list, st, &chk));
+    HIP_TRY(T.toc(0));
+    ICV_TRY(graph_flags_error("tl.tsne", chk.flags));
+    if (chk.w_max > 2.0f)
+        return fail(ICV_ERR_INVALID, "tl.tsne: the adjacency matrix has values above 2 (affinities are at most 2)");
+    if (chk.longest > icv::kTsMaxRow) return fail(ICV_ERR_UNSUPPORTED, "tl.tsne: a row has more than 2^22 stored entries");
+    const unsigned n_long = chk.n_long;
 
     // the j range is split so that the grid has about 2048 workgroups (8 per CU), in whole tiles
     const int64_t i_blocks = (n + 255) / 256;
@@ -4003,7 +3965,7 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
     float *sy = y, *su = update, *sg = gains;
     float *dy = reinterpret_cast<float*>(ws + G.y2), *du = reinterpret_cast<float*>(ws + G.u2),
           *dg = reinterpret_cast<float*>(ws + G.g2);
-    HIP_TRY(tic());
+    HIP_TRY(T.tic());
     HIP_TRY(hipMemsetAsync(ws + G.zero_begin, 0, G.zero_end - G.zero_begin, st));
     int cur = 0;
     for (int32_t t = iter_begin; t < iter_end; ++t, cur ^= 1) {
@@ -4030,8 +3992,8 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
         HIP_TRY(hipMemcpyAsync(update, su, bytes, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(gains, sg, bytes, hipMemcpyDeviceToDevice, st));
     }
-    HIP_TRY(toc(1));
-    if (stage_ms) stage_ms[0] = ms[0], stage_ms[1] = ms[1];
+    HIP_TRY(T.toc(1));
+    if (stage_ms) stage_ms[0] = T.ms[0], stage_ms[1] = T.ms[1];
     return ICV_OK;
 }
 

@@ -6,17 +6,14 @@
 
 #include <cstdint>
 
+#include "icv_graph.hpp"  // ld_mix, ld_wave_sum, kGraphLongRow, graph_entry_flags
+
 namespace icv {
 
 constexpr int kLdEmpty = -2;            // want[v]: an empty community (its id is assigned by rank, rule 4d)
 constexpr int kLdMaxLevels = 64;        // levels per iteration (rule 5)
-constexpr int kLdLdsRow = 512;          // longest row k_ld_decide combines in LDS; longer rows: k_ld_decide_long
+constexpr int kLdLdsRow = kGraphLongRow;  // longest row k_ld_decide combines in LDS; longer rows: k_ld_decide_long
 
-__host__ __device__ __forceinline__ uint64_t ld_mix(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 __host__ __device__ __forceinline__ uint64_t ld_prio(uint64_t s, int v) {
     return ld_mix(s + 0x9E3779B97F4A7C15ull * (uint64_t)(v + 1));
 }
@@ -35,14 +32,13 @@ __device__ __forceinline__ bool ld_wellconn(double gom, long long E, long long K
 __device__ __forceinline__ void ld_add(long long* p, long long v) {
     atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
 }
-__device__ __forceinline__ long long ld_wave_sum(long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ---- rule 1 / 2: validation and the integer weights (a wavefront per row) ---------------------------------------------
-// flags: 1 non-finite, 2 negative, 4 diagonal, 8 column out of range, 16 row not strictly ascending, 32 not symmetric,
-// 64 value >= 2^30.  sums[0] / sums[1]: the low / high 32-bit halves of the weights, summed.
+// flags: those of graph_entry_flags, and 64 value >= 2^30.  sums[0] / sums[1]: the low / high 32-bit halves of the
+// weights, summed.  The lane's accumulated f gates q, as before the per-entry test was shared; the one difference,
+// checked against the host's order of reports, is that -inf now sets flag 1 alone (it used to set 1 and 2, and 1 is
+// reported first).  A graph that passes has f = 0 in both forms, so wq, row_keep and sums are the same; the outputs
+// of one that fails are discarded.
 template <typename T>
 __global__ __launch_bounds__(256) void k_ld_quantise(const int64_t* __restrict__ indptr, const int32_t* __restrict__ col,
                                                      const T* __restrict__ val, int64_t n, int use_weights,
@@ -56,22 +52,7 @@ __global__ __launch_bounds__(256) void k_ld_quantise(const int64_t* __restrict__
     long long keep = 0, lo = 0, hi = 0;
     for (int64_t i = b + lane; i < e; i += 64) {
         const float x = (float)val[i];
-        const int64_t c = col[i];
-        if (!(fabsf(x) <= 3.4028234663852886e38f)) f |= 1;
-        if (x < 0.f) f |= 2;
-        if (c == v) f |= 4;
-        if (i > b && col[i - 1] >= c) f |= 16;
-        if (c < 0 || c >= n) {
-            f |= 8;
-        } else {
-            int64_t l = indptr[c], r = indptr[c + 1];  // row c is searched for column v
-            while (l < r) {
-                const int64_t m = (l + r) >> 1;
-                if (col[m] < v) l = m + 1;
-                else r = m;
-            }
-            if (!(l < indptr[c + 1] && col[l] == v && (float)val[l] == x)) f |= 32;
-        }
+        f |= graph_entry_flags(indptr, col, val, n, v, b, i, x);
         long long q = 0;
         if (f == 0) {
             const float y = use_weights ? x : 1.f;

@@ -8,11 +8,11 @@
 
 #include <cstdint>
 
-#include "icv_leiden.hpp"  // ld_wave_sum, kLdLdsRow
+#include "icv_graph.hpp"  // ld_wave_sum, kGraphLongRow, k_graph_check (the validation)
 
 namespace icv {
 
-constexpr int kTsLongRow = kLdLdsRow;          // rows above this many entries take a workgroup in k_ts_step
+constexpr int kTsLongRow = kGraphLongRow;      // rows above this many entries take a workgroup in k_ts_step
 constexpr int kTsTile = 256;                   // positions per LDS tile of k_ts_repulse (= its block size)
 constexpr int64_t kTsMaxRow = (int64_t)1 << 22;  // |attraction term| 2^40 <= 2^40: 2^22 of them fit an int64
 
@@ -94,46 +94,6 @@ __global__ void __launch_bounds__(256) k_ts_affinity(const float* __restrict__ d
     for (int r = 0; r < kk; ++r) {
         const double d = (double)dr[r];
         p_out[i * kk + r] = ts_exp(-(beta * (d * d - d0))) / S;
-    }
-}
-
-// ---- validation (a wavefront per row), as k_um_check -----------------------------------------------------------------------
-// flags: 1 non-finite, 2 negative, 4 diagonal, 8 column out of range, 16 row not strictly ascending, 32 not symmetric,
-// 64 value above 2.  head[0] flags, head[1] number of long rows, head[2] longest row (saturated at 2^31 - 1)
-__global__ __launch_bounds__(256) void k_ts_check(const int64_t* __restrict__ indptr, const int32_t* __restrict__ col,
-                                                  const float* __restrict__ val, int64_t n, unsigned* __restrict__ head,
-                                                  int32_t* __restrict__ long_list) {
-    const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (v >= n) return;
-    const int64_t b = indptr[v], e = indptr[v + 1];
-    unsigned f = 0;
-    for (int64_t i = b + lane; i < e; i += 64) {
-        const float x = val[i];
-        const int64_t c = col[i];
-        if (!(fabsf(x) <= 3.4028234663852886e38f)) f |= 1;
-        else if (x < 0.f) f |= 2;
-        else if (x > 2.f) f |= 64;
-        if (c == v) f |= 4;
-        if (i > b && col[i - 1] >= c) f |= 16;
-        if (c < 0 || c >= n) {
-            f |= 8;
-        } else {
-            int64_t l = indptr[c], r = indptr[c + 1];  // row c is searched for column v
-            while (l < r) {
-                const int64_t m = (l + r) >> 1;
-                if (col[m] < v) l = m + 1;
-                else r = m;
-            }
-            if (!(l < indptr[c + 1] && col[l] == v && val[l] == x)) f |= 32;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) f |= __shfl_xor(f, off, 64);
-    if (lane == 0) {
-        if (f) atomicOr(&head[0], f);
-        const int64_t len = e - b;
-        atomicMax(&head[2], (unsigned)(len > 0x7fffffff ? 0x7fffffff : len));
-        if (len > kTsLongRow) long_list[atomicAdd(&head[1], 1u)] = (int32_t)v;
     }
 }
 

@@ -8,11 +8,11 @@
 
 #include <cstdint>
 
-#include "icv_leiden.hpp"  // ld_mix (splitmix64's finaliser), ld_wave_sum, kLdLdsRow
+#include "icv_graph.hpp"  // ld_mix, ld_wave_sum, kGraphLongRow, k_graph_check (rule 1)
 
 namespace icv {
 
-constexpr int kUmLdsRow = kLdLdsRow;  // longest row a wavefront stages; longer rows take a workgroup
+constexpr int kUmLdsRow = kGraphLongRow; // longest row a wavefront stages; longer rows take a workgroup
 constexpr int kUmMaxNegatives = 64;   // negative_sample_rate <= this
 
 struct UmEpoch {
@@ -27,48 +27,6 @@ struct UmEpoch {
     int64_t n;
     int r;          // negative_sample_rate
 };
-
-// ---- rule 1: validation, the largest weight, the list of the long rows (a wavefront per row) ---------------------------
-// flags: 1 non-finite, 2 negative, 4 diagonal, 8 column out of range, 16 row not strictly ascending, 32 not symmetric.
-// head[0] flags, head[1] number of long rows, head[2] bits of the largest weight (non-negative floats order as unsigned)
-__global__ __launch_bounds__(256) void k_um_check(const int64_t* __restrict__ indptr, const int32_t* __restrict__ col,
-                                                  const float* __restrict__ val, int64_t n, unsigned* __restrict__ head,
-                                                  int32_t* __restrict__ long_list) {
-    const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (v >= n) return;
-    const int64_t b = indptr[v], e = indptr[v + 1];
-    unsigned f = 0, top = 0;
-    for (int64_t i = b + lane; i < e; i += 64) {
-        const float x = val[i];
-        const int64_t c = col[i];
-        if (!(fabsf(x) <= 3.4028234663852886e38f)) f |= 1;
-        else if (x < 0.f) f |= 2;
-        else top = max(top, __float_as_uint(x == 0.f ? 0.f : x));
-        if (c == v) f |= 4;
-        if (i > b && col[i - 1] >= c) f |= 16;
-        if (c < 0 || c >= n) {
-            f |= 8;
-        } else {
-            int64_t l = indptr[c], r = indptr[c + 1];  // row c is searched for column v
-            while (l < r) {
-                const int64_t m = (l + r) >> 1;
-                if (col[m] < v) l = m + 1;
-                else r = m;
-            }
-            if (!(l < indptr[c + 1] && col[l] == v && val[l] == x)) f |= 32;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        f |= __shfl_xor(f, off, 64);
-        top = max(top, (unsigned)__shfl_xor(top, off, 64));
-    }
-    if (lane == 0) {
-        if (f) atomicOr(&head[0], f);
-        if (top) atomicMax(&head[2], top);
-        if (e - b > kUmLdsRow) long_list[atomicAdd(&head[1], 1u)] = (int32_t)v;
-    }
-}
 
 // ---- rule 2: is the entry of weight w active in epoch t (t >= 1)? ------------------------------------------------------
 __device__ __forceinline__ bool um_active(float wf, const UmEpoch& P) {

@@ -9,44 +9,9 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
-import scipy.sparse as sp
-
 from .. import _engine
-
-
-def _is_tensor(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
-def _graph(adata, neighbors_key, adjacency, obsp):
-    if adjacency is not None:
-        return adjacency
-    if obsp is not None:
-        if obsp not in adata.obsp:
-            raise KeyError(f"{obsp!r} is not in adata.obsp. Did you run `pp.neighbors`?")
-        return adata.obsp[obsp]
-    if neighbors_key not in adata.uns:
-        raise KeyError(f"{neighbors_key!r} is not in adata.uns. Did you run `pp.neighbors`?")
-    key = adata.uns[neighbors_key]["connectivities_key"]
-    if key not in adata.obsp:
-        raise KeyError(f"{key!r} is not in adata.obsp. Did you run `pp.neighbors`?")
-    return adata.obsp[key]
-
-
-def _host_csr(g, who="tl.leiden"):
-    """Canonical CSR arrays (int64, int32, float32 / float64) of a scipy matrix; shape errors before the GPU."""
-    if g.ndim != 2 or g.shape[0] != g.shape[1]:
-        raise ValueError(f"{who}: the adjacency matrix must be square")
-    if g.shape[0] < 1:
-        raise ValueError(f"{who}: the adjacency matrix is empty")
-    a = sp.csr_matrix(g)
-    if a is g:
-        a = a.copy()
-    a.sum_duplicates()
-    a.sort_indices()
-    data = a.data if a.data.dtype in (np.float32, np.float64) else a.data.astype(np.float64)
-    return a.indptr.astype(np.int64), a.indices.astype(np.int32), np.ascontiguousarray(data)
+from ._graph import _graph, _host_csr, _is_tensor  # noqa: F401 (their first home: still importable from here)
+from ._graph import check_seed, finish, resolve_graph
 
 
 def leiden(adata, neighbors_key="cnv_neighbors", key_added="cnv_leiden", inplace=True, *, resolution=1.0, random_state=0,
@@ -104,22 +69,8 @@ def leiden(adata, neighbors_key="cnv_neighbors", key_added="cnv_leiden", inplace
         raise ValueError("tl.leiden: n_iterations and random_state must be integers") from None
     if n_it != n_iterations or (n_it < 1 and n_it != -1):
         raise ValueError(f"tl.leiden: n_iterations={n_iterations!r} must be -1 or a positive integer")
-    if seed != random_state:
-        raise ValueError(f"tl.leiden: random_state={random_state!r} is not an integer")
-    g = _graph(adata, neighbors_key, adjacency, obsp)
-    if isinstance(g, (tuple, list)) and len(g) == 3 and all(_is_tensor(t) for t in g):
-        dev = g
-        n = int(g[0].numel()) - 1
-        if n < 1:
-            raise ValueError("tl.leiden: the adjacency matrix is empty")
-    elif sp.issparse(g):
-        dev = None
-        host = _host_csr(g)
-        n = len(host[0]) - 1
-    else:
-        raise ValueError("tl.leiden: the graph must be a scipy sparse matrix or (indptr, indices, data) CUDA tensors")
-    if adata is not None and hasattr(adata, "n_obs") and adata.n_obs != n:
-        raise ValueError(f"tl.leiden: the graph has {n} vertices, adata has {adata.n_obs} cells")
+    check_seed("tl.leiden", random_state)
+    host, dev, _n = resolve_graph("tl.leiden", adata, neighbors_key, adjacency, obsp)
     import pandas as pd
 
     torch = _engine._torch()
@@ -131,9 +82,5 @@ def leiden(adata, neighbors_key="cnv_neighbors", key_added="cnv_leiden", inplace
     codes = labels.cpu().numpy()
     cats = [str(i) for i in range(info["n_communities"])]
     result = pd.Categorical.from_codes(codes, categories=cats)
-    if inplace:
-        adata.obs[key_added] = result
-        adata.uns[key_added] = {"params": {"resolution": resolution, "random_state": random_state,
-                                           "n_iterations": n_iterations}}
-        return (result, info) if return_info else None
-    return (result, info) if return_info else result
+    params = {"resolution": resolution, "random_state": random_state, "n_iterations": n_iterations}
+    return finish(adata, "obs", key_added, result, params, info, inplace, return_info)

@@ -17,8 +17,8 @@ import numpy as np
 
 from .. import _engine
 from ..pp._neighbors import MAX_DIMS, _points
-from ._leiden import _is_tensor
-from ._umap import _MASK, _uniform24
+from ._graph import (_MASK, _is_tensor, _uniform24, check_components, check_seed, finish, init_to_device,
+                     resolve_init)
 
 _TAG_TSNE = _MASK - 2  # the "epoch" of the counter hash behind the random initial positions
 MAX_NEIGHBORS = 63
@@ -92,17 +92,14 @@ def tsne(adata, use_rep="cnv_pca", key_added="cnv_tsne", inplace=True, *, n_pcs=
     """
     if kwargs:
         raise ValueError(f"tl.tsne: unsupported keyword argument(s): {', '.join(sorted(kwargs))}")
-    if n_components not in (2, 3) or isinstance(n_components, bool):
-        raise ValueError(f"tl.tsne: n_components={n_components!r} must be 2 or 3")
-    c = int(n_components)
+    c = check_components("tl.tsne", n_components)
     try:
         seed = int(random_state)
         perp, ex, eta = float(perplexity), float(early_exaggeration), float(learning_rate)
     except (TypeError, ValueError):
         raise ValueError("tl.tsne: random_state, perplexity, early_exaggeration and learning_rate must be "
                          "numbers") from None
-    if seed != random_state:
-        raise ValueError(f"tl.tsne: random_state={random_state!r} is not an integer")
+    check_seed("tl.tsne", random_state)
     if not (math.isfinite(perp) and perp > 0 and math.isfinite(ex) and ex > 0 and math.isfinite(eta) and eta > 0):
         raise ValueError("tl.tsne: perplexity, early_exaggeration and learning_rate must be finite numbers > 0")
     n_iter = int(max_iter)
@@ -135,30 +132,14 @@ def tsne(adata, use_rep="cnv_pca", key_added="cnv_tsne", inplace=True, *, n_pcs=
         raise ValueError(f"tl.tsne: perplexity={perplexity!r} must be less than the number of neighbours used, "
                          f"min(floor(3 perplexity), {MAX_NEIGHBORS}, n_obs - 1) = {kk}")
 
-    init = init_pos
-    if isinstance(init, str) and init not in ("pca", "random"):
-        if adata is None or init not in adata.obsm:
-            raise KeyError(f"tl.tsne: init_pos={init!r} is neither 'pca', 'random' nor a key of adata.obsm")
-        init = adata.obsm[init]
-    if not isinstance(init, str):
-        if tuple(init.shape) != (n, c):
-            raise ValueError(f"tl.tsne: init_pos has shape {tuple(init.shape)}, expected {(n, c)}")
-        if not _is_tensor(init):
-            init = np.ascontiguousarray(init, dtype=np.float32)
-            if not np.isfinite(init).all():
-                raise ValueError("tl.tsne: init_pos has non-finite values")
+    init = resolve_init("tl.tsne", adata, init_pos, ("pca", "random"), n, c)
     used = init if isinstance(init, str) else "given"
     if isinstance(init, str):
         init = pca_init(x.cpu().numpy() if _is_tensor(x) else x, c) if init == "pca" else random_init(n, c, seed)
 
     torch = _engine._torch()
     xd = (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).cuda().contiguous()
-    if _is_tensor(init):
-        y = init.detach().to(device=xd.device, dtype=torch.float32).contiguous().clone()
-        if not bool(torch.isfinite(y).all().item()):
-            raise ValueError("tl.tsne: init_pos has non-finite values")
-    else:
-        y = torch.from_numpy(init).to(xd.device)
+    y = init_to_device("tl.tsne", init, xd.device)
     stage_ms = {}
 
     def timed(name, fn, *args):
@@ -181,10 +162,6 @@ def tsne(adata, use_rep="cnv_pca", key_added="cnv_tsne", inplace=True, *, n_pcs=
                             stage_ms=stage_ms if return_info else None)
     result = y.cpu().numpy()
     info = {"n_neighbors_used": kk, "n_iter": n_iter, "init_pos": used, "stage_ms": stage_ms} if return_info else None
-    if inplace:
-        adata.obsm[f"X_{key_added}"] = result
-        adata.uns[key_added] = {"params": {"perplexity": perplexity, "early_exaggeration": early_exaggeration,
-                                           "learning_rate": learning_rate, "random_state": random_state,
-                                           "use_rep": rep_name}}
-        return (result, info) if return_info else None
-    return (result, info) if return_info else result
+    params = {"perplexity": perplexity, "early_exaggeration": early_exaggeration, "learning_rate": learning_rate,
+              "random_state": random_state, "use_rep": rep_name}
+    return finish(adata, "obsm", key_added, result, params, info, inplace, return_info)

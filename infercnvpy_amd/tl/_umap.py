@@ -15,27 +15,10 @@ import numpy as np
 import scipy.sparse as sp
 
 from .. import _engine
-from ._leiden import _graph, _host_csr, _is_tensor
+from ._graph import (_MASK, _uniform24, check_components, check_seed, finish, init_to_device, resolve_graph,
+                     resolve_init)
 
-_MASK = (1 << 64) - 1
 _TAG_RANDOM, _TAG_NOISE = _MASK, _MASK - 1  # the "epochs" of the counter hash behind the initial positions
-
-
-def _mix_int(z):
-    z &= _MASK
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK
-    return z ^ (z >> 31)
-
-
-def _uniform24(seed, tag, n, c):
-    """n x c float64 numbers in [0, 1): the top 24 bits of mix(mix(seed ^ mix(tag)) ^ (i c + j))."""
-    z = np.uint64(_mix_int((seed & _MASK) ^ _mix_int(tag))) ^ np.arange(n * c, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    return ((z >> np.uint64(40)).astype(np.float64) * 2.0 ** -24).reshape(n, c)
 
 
 def random_init(n, n_components, random_state):
@@ -134,9 +117,7 @@ def umap(adata, neighbors_key="cnv_neighbors", key_added="cnv_umap", inplace=Tru
     """
     if kwargs:
         raise ValueError(f"tl.umap: unsupported keyword argument(s): {', '.join(sorted(kwargs))}")
-    if n_components not in (2, 3) or isinstance(n_components, bool):
-        raise ValueError(f"tl.umap: n_components={n_components!r} must be 2 or 3")
-    c = int(n_components)
+    c = check_components("tl.umap", n_components)
     try:
         seed = int(random_state)
         rate = int(negative_sample_rate)
@@ -144,8 +125,7 @@ def umap(adata, neighbors_key="cnv_neighbors", key_added="cnv_umap", inplace=Tru
     except (TypeError, ValueError):
         raise ValueError("tl.umap: random_state, negative_sample_rate, alpha, gamma, min_dist and spread must be "
                          "numbers") from None
-    if seed != random_state:
-        raise ValueError(f"tl.umap: random_state={random_state!r} is not an integer")
+    check_seed("tl.umap", random_state)
     if rate != negative_sample_rate or not 0 <= rate <= 64:
         raise ValueError(f"tl.umap: negative_sample_rate={negative_sample_rate!r} must be an integer in [0, 64]")
     if not (math.isfinite(alpha_f) and alpha_f >= 0 and math.isfinite(gamma_f) and gamma_f >= 0):
@@ -157,20 +137,7 @@ def umap(adata, neighbors_key="cnv_neighbors", key_added="cnv_umap", inplace=Tru
     if a is not None and not (math.isfinite(float(a)) and float(a) > 0 and math.isfinite(float(b)) and float(b) > 0):
         raise ValueError("tl.umap: a and b must be finite numbers > 0")
 
-    g = _graph(adata, neighbors_key, adjacency, obsp)
-    host = dev = None
-    if isinstance(g, (tuple, list)) and len(g) == 3 and all(_is_tensor(t) for t in g):
-        dev = g
-        n = int(g[0].numel()) - 1
-        if n < 1:
-            raise ValueError("tl.umap: the adjacency matrix is empty")
-    elif sp.issparse(g):
-        host = _host_csr(g, "tl.umap")
-        n = len(host[0]) - 1
-    else:
-        raise ValueError("tl.umap: the graph must be a scipy sparse matrix or (indptr, indices, data) CUDA tensors")
-    if adata is not None and hasattr(adata, "n_obs") and adata.n_obs != n:
-        raise ValueError(f"tl.umap: the graph has {n} vertices, adata has {adata.n_obs} cells")
+    host, dev, n = resolve_graph("tl.umap", adata, neighbors_key, adjacency, obsp)
     if maxiter is None:
         n_epochs = 500 if n <= 10_000 else 200
     else:
@@ -178,18 +145,7 @@ def umap(adata, neighbors_key="cnv_neighbors", key_added="cnv_umap", inplace=Tru
         if n_epochs != maxiter or n_epochs < 1:
             raise ValueError(f"tl.umap: maxiter={maxiter!r} must be None or a positive integer")
 
-    init = init_pos
-    if isinstance(init, str) and init not in ("spectral", "random"):
-        if adata is None or init not in adata.obsm:
-            raise KeyError(f"tl.umap: init_pos={init!r} is neither 'spectral', 'random' nor a key of adata.obsm")
-        init = adata.obsm[init]
-    if not isinstance(init, str):
-        if tuple(init.shape) != (n, c):
-            raise ValueError(f"tl.umap: init_pos has shape {tuple(init.shape)}, expected {(n, c)}")
-        if not _is_tensor(init):
-            init = np.ascontiguousarray(init, dtype=np.float32)
-            if not np.isfinite(init).all():
-                raise ValueError("tl.umap: init_pos has non-finite values")
+    init = resolve_init("tl.umap", adata, init_pos, ("spectral", "random"), n, c)
     if a is None:
         a, b = find_ab_params(spread_f, min_dist_f)
     a, b = float(a), float(b)
@@ -211,12 +167,7 @@ def umap(adata, neighbors_key="cnv_neighbors", key_added="cnv_umap", inplace=Tru
             init = y0
     if isinstance(init, str):
         init = random_init(n, c, seed)
-    if _is_tensor(init):
-        y = init.detach().to(device=indptr.device, dtype=torch.float32).contiguous().clone()
-        if not bool(torch.isfinite(y).all().item()):
-            raise ValueError("tl.umap: init_pos has non-finite values")
-    else:
-        y = torch.from_numpy(init).to(indptr.device)
+    y = init_to_device("tl.umap", init, indptr.device)
     stage_ms = {}
     _engine.umap_epochs(indptr, indices, data, y, a=a, b=b, gamma=gamma_f, negative_sample_rate=rate,
                         initial_alpha=alpha_f, n_epochs=n_epochs, random_state=seed,
@@ -227,8 +178,5 @@ def umap(adata, neighbors_key="cnv_neighbors", key_added="cnv_umap", inplace=Tru
         w = data.to(torch.float64)
         n_fire = int(((w > 0) & (w >= w.max() / n_epochs)).sum().item()) if w.numel() else 0
         info = {"a": a, "b": b, "n_epochs": n_epochs, "n_fire": n_fire, "init_pos": used, "stage_ms": stage_ms}
-    if inplace:
-        adata.obsm[f"X_{key_added}"] = result
-        adata.uns[key_added] = {"params": {"a": a, "b": b, "random_state": random_state}}
-        return (result, info) if return_info else None
-    return (result, info) if return_info else result
+    params = {"a": a, "b": b, "random_state": random_state}
+    return finish(adata, "obsm", key_added, result, params, info, inplace, return_info)
