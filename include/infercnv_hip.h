@@ -701,6 +701,25 @@ int icv_states_filter(const int8_t *states, const double *p_neutral, int64_t n_r
 int icv_posterior_stats(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, double amplitude, double h, double ps,
                         double pw, double *stats, void *stream);
 
+/* ---- tl.cnv_pseudobulk: the exact mean profile of every group of rows ---------------------------------------
+ * icv_group_profiles: rows (device int64, n_listed row numbers, sorted by group) and group_ptr (device int64, n_groups + 1
+ * ascending positions from 0 to n_listed) list the rows of every group, as for icv_state_votes; a row may stand in
+ * several lists.  Stored values are used as float64; q = rint(v 2^shift), ties to even, as int64 (0 <= shift <= 40,
+ * ICV_ERR_INVALID beyond; the caller keeps every stored magnitude below 2^10 and (rows of the largest group) 2^shift at
+ * or below 2^52, so no sum leaves int64).  sum (device int64, n_groups x n_cols) and stored (device int32, the same
+ * shape) are zeroed and receive the sum of q and the number of stored values != 0 of the group's listed rows at every
+ * window: integer atomic adds, a pure function of the arguments.  -0.0 and a stored 0.0 add to neither.  CSR columns need
+ * be neither sorted nor unique; a column outside [0, n_cols) is passed over.  *flags (device int32) is set to 0; bit 0 is
+ * then set where a value that was read is not finite (it adds to neither table), bit 1 where a row number lies outside
+ * [0, n_rows) (that row is skipped).  n_cols and n_groups have no limit.  No synchronisation.
+ * icv_group_profiles_finish: with L = group_ptr[g + 1] - group_ptr[g], mean[g,w] = (double(sum) / double(L)) 2^-shift --
+ * the conversion rounds to nearest even, the division is correctly rounded, the scaling exact -- and fraction[g,w] =
+ * double(stored) / double(L) (device float64, n_groups x n_cols each); a group of no rows gets 0 in both. */
+int icv_group_profiles(const icv_matrix *m, const int64_t *rows, int64_t n_listed, const int64_t *group_ptr,
+                       int64_t n_groups, int32_t shift, int64_t *sum, int32_t *stored, int32_t *flags, void *stream);
+int icv_group_profiles_finish(const int64_t *sum, const int32_t *stored, const int64_t *group_ptr, int64_t n_groups,
+                              int32_t n_cols, int32_t shift, double *mean, double *fraction, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

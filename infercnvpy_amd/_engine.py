@@ -2059,3 +2059,48 @@ def segments_support(row, start, end, state, loss, gain):
         _lib.check(lib.icv_segments_support(_ptr(row), _ptr(start), _ptr(end), _ptr(state), n_seg, _ptr(loss), _ptr(gain), g,
                                             w, _ptr(cells_min), _ptr(cells_sum), _stream_ptr(torch)))
     return cells_min, cells_sum
+
+
+# ---- tl.cnv_pseudobulk: exact per-group mean profiles on the device (icv_group_profiles*) ------------------
+def group_profiles(dm: DeviceMatrix, rows, group_ptr, shift):
+    """(sum, stored, flags): device int64 / int32 ``G x W`` tables of rule 4 over the listed rows of every group and the
+    device int32 flags (bit 0: a non-finite value, bit 1: a row number outside the matrix).  ``rows``: int64 row numbers
+    sorted by group, ``group_ptr``: int64 G + 1 positions; host arrays are uploaded, CUDA tensors are used as they are.
+    Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    with torch.cuda.device(dm.device):
+        d_rows, d_ptr = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64)).cuda()
+                         for v in (rows, group_ptr))
+        assert d_rows.dtype == torch.int64 and d_ptr.dtype == torch.int64 and d_rows.is_cuda and d_ptr.is_cuda
+        g, w = int(d_ptr.shape[0]) - 1, int(dm.shape[1])
+        assert g >= 0
+        total = torch.empty((g, w), dtype=torch.int64, device="cuda")
+        stored = torch.empty((g, w), dtype=torch.int32, device="cuda")
+        flags = torch.empty(1, dtype=torch.int32, device="cuda")
+        m = dm.c_struct()
+        _lib.check(lib.icv_group_profiles(C.byref(m), _ptr(d_rows), int(d_rows.shape[0]), _ptr(d_ptr), g, int(shift),
+                                          _ptr(total), _ptr(stored), _ptr(flags), _stream_ptr(torch)))
+    return total, stored, flags, d_ptr
+
+
+def group_profiles_finish(total, stored, d_ptr, shift):
+    """(mean, fraction): device float64 ``G x W`` of rule 5 from the tables of :func:`group_profiles`; ``d_ptr`` is the
+    device copy of ``group_ptr`` it returned.  Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    g, w = int(total.shape[0]), int(total.shape[1])
+    with torch.cuda.device(total.device):
+        mean = torch.empty((g, w), dtype=torch.float64, device="cuda")
+        fraction = torch.empty((g, w), dtype=torch.float64, device="cuda")
+        _lib.check(lib.icv_group_profiles_finish(_ptr(total), _ptr(stored), _ptr(d_ptr), g, w, int(shift), _ptr(mean),
+                                                 _ptr(fraction), _stream_ptr(torch)))
+    return mean, fraction
+
+
+def group_profiles_flags_and_absmax(flags, absmax):
+    """(flags as an int, largest |v| as a float) of :func:`group_profiles` and :func:`states_absmax`: the two device
+    scalars in one copy to the host."""
+    torch = _torch()
+    both = torch.cat([flags.to(torch.float64).reshape(1), absmax]).cpu().tolist()
+    return int(both[0]), float(both[1])

@@ -50,6 +50,7 @@ EXPORTS = (
     "icv_segments_count", "icv_segments_fill", "icv_state_votes", "icv_state_consensus", "icv_segments_support",
     "icv_posterior_chains", "icv_states_filter",
     "icv_posterior_stats",
+    "icv_group_profiles", "icv_group_profiles_finish",
 )
 
 
@@ -199,6 +200,8 @@ def load():
     lib.icv_posterior_chains.argtypes = [P(Matrix), vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp, vp]
     lib.icv_states_filter.argtypes = [vp, vp, i64, i32, vp, i32, dbl, vp, vp, vp, vp, vp]
     lib.icv_posterior_stats.argtypes = [P(Matrix), vp, i32, dbl, dbl, dbl, dbl, vp, vp]
+    lib.icv_group_profiles.argtypes = [P(Matrix), vp, i64, vp, i64, i32, vp, vp, vp, vp]
+    lib.icv_group_profiles_finish.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -46,6 +46,7 @@
 #include "icv_segments.hpp"
 #include "icv_hmmfit.hpp"
 #include "icv_posterior.hpp"
+#include "icv_pseudobulk.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -4258,5 +4259,68 @@ int icv_posterior_stats(const icv_matrix* m, const int32_t* chr_start, int32_t n
     return ICV_HMM_LAUNCH(k_posterior_stats, icv::po_lds_bytes(m->n_cols), icv::PoParams{amplitude, h, ps, pw}, stats);
 }
 #undef ICV_HMM_LAUNCH
+
+// ---- tl.cnv_pseudobulk: exact per-group mean profiles -------------------------------------------------------
+static_assert((size_t)icv::kPbTile * 12 <= 48 * 1024, "a tile's accumulators take 48 KB of LDS: three workgroups per CU");
+
+int icv_group_profiles(const icv_matrix* m, const int64_t* rows, int64_t n_listed, const int64_t* group_ptr,
+                       int64_t n_groups, int32_t shift, int64_t* sum, int32_t* stored, int32_t* flags, void* stream) {
+    if (!m || n_listed < 0 || (n_listed > 0 && !rows) || !group_ptr || n_groups < 0 || (n_groups > 0 && (!sum || !stored)) ||
+        !flags || shift < 0 || shift > icv::kPbMaxShift || m->n_rows < 0 || m->n_cols < 1 ||
+        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR) ||
+        (m->format == ICV_DENSE && m->ld < m->n_cols))
+        return fail(ICV_ERR_INVALID, "bad group_profiles arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int32_t), st));
+    if (n_groups == 0) return ICV_OK;
+    const size_t cells = (size_t)n_groups * (size_t)m->n_cols;
+    HIP_TRY(hipMemsetAsync(sum, 0, cells * sizeof(int64_t), st));
+    HIP_TRY(hipMemsetAsync(stored, 0, cells * sizeof(int32_t), st));
+    if (n_listed == 0) return ICV_OK;
+    // (a CSR without stored entries may come with null indices / values: they are never read then)
+    if (m->format == ICV_DENSE ? (!m->values && m->n_rows > 0) : !m->indptr)
+        return fail(ICV_ERR_INVALID, "group_profiles: incomplete matrix");
+    // every group of L rows has ceil(L / slab) <= L / slab + 1 slabs, and a group of no rows has none
+    const int64_t n_tiles = ((int64_t)m->n_cols + icv::kPbTile - 1) / icv::kPbTile;
+    const int64_t max_slabs = n_listed / icv::kPbSlab + std::min(n_groups, n_listed);
+    if (max_slabs > kSegMaxBlocks / n_tiles)
+        return fail(ICV_ERR_UNSUPPORTED, "group_profiles: too many rows x windows for one call");
+    AsyncBuf slabs, slab_off;
+    HIP_TRY(slabs.alloc((size_t)n_groups * sizeof(int64_t), st));
+    HIP_TRY(slab_off.alloc((size_t)(n_groups + 1) * sizeof(int64_t), st));
+    hipLaunchKernelGGL(icv::k_pb_slab_counts, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, st, group_ptr, n_groups,
+                       n_listed, slabs.as<int64_t>());
+    HIP_TRY(hipGetLastError());
+    ICV_TRY(icv_row_offsets(slabs.as<int64_t>(), n_groups, slab_off.as<int64_t>(), stream));
+    const dim3 grid((unsigned)(max_slabs * n_tiles)), block(icv::kPbThreads);
+#define ICV_PB(T, CSR)                                                                                                    \
+    hipLaunchKernelGGL((icv::k_group_profiles<T, CSR>), grid, block, 0, st, (const T*)m->values, m->indptr, m->indices,   \
+                       m->ld, m->n_rows, m->n_cols, rows, n_listed, group_ptr, n_groups, slab_off.as<int64_t>(),          \
+                       (uint32_t)n_tiles, (int)shift, reinterpret_cast<unsigned long long*>(sum), stored, flags)
+    if (m->format == ICV_CSR) {
+        if (m->dtype == ICV_F32) ICV_PB(float, true);
+        else ICV_PB(double, true);
+    } else {
+        if (m->dtype == ICV_F32) ICV_PB(float, false);
+        else ICV_PB(double, false);
+    }
+#undef ICV_PB
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_group_profiles_finish(const int64_t* sum, const int32_t* stored, const int64_t* group_ptr, int64_t n_groups,
+                              int32_t n_cols, int32_t shift, double* mean, double* fraction, void* stream) {
+    if (n_groups < 0 || n_cols < 1 || shift < 0 || shift > icv::kPbMaxShift || !group_ptr ||
+        (n_groups > 0 && (!sum || !stored || !mean || !fraction)))
+        return fail(ICV_ERR_INVALID, "bad group_profiles_finish arguments");
+    if (n_groups == 0) return ICV_OK;
+    if (n_groups > kSegMaxBlocks || (n_groups * (int64_t)n_cols + 255) / 256 > kSegMaxBlocks)
+        return fail(ICV_ERR_UNSUPPORTED, "group_profiles_finish: too many groups x windows for one call");
+    hipLaunchKernelGGL(icv::k_group_profiles_finish, dim3((unsigned)((n_groups * (int64_t)n_cols + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), sum, stored, group_ptr, n_groups, n_cols, (int)shift, mean, fraction);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
 
 }  // extern "C"

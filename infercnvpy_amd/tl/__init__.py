@@ -6,8 +6,9 @@ from ._tsne import tsne
 from ._umap import umap
 from ._linkage import cell_linkage, leaves_list, ward_linkage
 from ._posteriors import cnv_posteriors, cnv_states_filter
+from ._pseudobulk import cnv_pseudobulk
 from ._scores import cnv_score, ithcna, ithgex
 from ._segments import cnv_segments
 from ._states import cnv_states
 
-__all__ = ["infercnv", "infercnv_device", "pca", "leiden", "umap", "tsne", "cnv_score", "cnv_states", "cnv_states_fit", "cnv_segments", "cnv_posteriors", "cnv_states_filter", "ithcna", "ithgex", "cell_linkage", "ward_linkage", "leaves_list"]
+__all__ = ["infercnv", "infercnv_device", "pca", "leiden", "umap", "tsne", "cnv_score", "cnv_states", "cnv_states_fit", "cnv_segments", "cnv_pseudobulk", "cnv_posteriors", "cnv_states_filter", "ithcna", "ithgex", "cell_linkage", "ward_linkage", "leaves_list"]
