@@ -1423,34 +1423,11 @@ class _PcaInput:
     ``f32_exact``: the stored values are float32 numbers (a float32 Gram panel holds them without rounding)."""
 
     def __init__(self, x):
-        torch = _torch()
-        self.host_dense = None
-        if isinstance(x, PackedCsr):
-            ip = x.indptr.cpu().numpy()
-            self.dm = DeviceMatrix(indptr=x.indptr, indices=x.indices, data=x.data, shape=x.shape, indptr_host=ip,
-                                   validate=False)
-            self.f32_exact = True  # X_cnv's values are float32 numbers widened to float64
-        elif isinstance(x, torch.Tensor):
-            if x.dim() != 2:
-                raise ValueError("tl.pca: X must be 2-D")
-            t = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float64)
-            self.dm = DeviceMatrix(dense=t.cuda().contiguous())
-            self.f32_exact = t.dtype == torch.float32
-        elif sp.issparse(x):
-            x = x.tocsr()
-            if x.data.dtype not in (np.float32, np.float64):
-                x = x.astype(np.float64)
-            self.dm = to_device_matrix(x)
-            self.f32_exact = x.data.dtype == np.float32
-        else:
-            a = np.asarray(x)
-            if a.ndim != 2:
-                raise ValueError("tl.pca: X must be 2-D")
-            if a.dtype not in (np.float32, np.float64):
-                a = a.astype(np.float64)
-            self.host_dense, self.dm = np.ascontiguousarray(a), None
-            self.f32_exact = a.dtype == np.float32
-        self.shape = tuple(self.host_dense.shape if self.dm is None else self.dm.shape)
+        m = matrix_input(x, "tl.pca", slabs=True)
+        self.host_dense, self.dm = (m, None) if isinstance(m, np.ndarray) else (None, m)
+        # (X_cnv's values are float32 numbers widened to float64)
+        self.f32_exact = isinstance(x, PackedCsr) or "float32" in str(m.dtype)
+        self.shape = tuple(m.shape)
 
     def slabs(self, rows):
         """(row0, c_struct) of consecutive slabs of at most `rows` rows."""
@@ -1827,17 +1804,26 @@ def tsne_iterations(indptr, indices, data, y, update, gains, *, early_exaggerati
 
 
 # ---- tl.cnv_states: sums of squares and the per-chromosome Viterbi chains on the device (icv_states_*) -------------------
-def states_input(x):
-    """The matrix tl.cnv_states reads, as one DeviceMatrix: a PackedCsr is read where it lies, a host CSR / CSC sends
+def _empty(torch, n, dtype):
+    """An uninitialised CUDA vector of n elements (n may be 0: no allocation of no bytes)."""
+    return torch.empty(max(n, 1), dtype=dtype, device="cuda")[:n]
+
+
+def matrix_input(x, who, slabs=False):
+    """The matrix of ``obsm["X_cnv"]`` as one DeviceMatrix: a PackedCsr is read where it lies, a host CSR / CSC sends
     indptr / indices / stored values once (canonical CSR: ascending unique columns), a CUDA tensor is used as it is, a
-    host dense array is uploaded.  Values stay float32 or float64; any other dtype becomes float64."""
+    host dense array is uploaded.  Values stay float32 or float64; any other dtype becomes float64.  ``who`` prefixes the
+    messages.  ``slabs``: the caller slices rows (tl.pca): a host dense array comes back as a contiguous host array, to
+    be uploaded slab by slab, and the row pointers of a PackedCsr are copied to the host; without it nothing is read
+    back."""
     torch = _torch()
     if isinstance(x, PackedCsr):
-        return DeviceMatrix(indptr=x.indptr, indices=x.indices, data=x.data, shape=x.shape,
-                            indptr_host=np.zeros(x.n_rows + 1, dtype=np.int64), validate=False)
+        ip = x.indptr.cpu().numpy() if slabs else np.zeros(x.n_rows + 1, dtype=np.int64)
+        return DeviceMatrix(indptr=x.indptr, indices=x.indices, data=x.data, shape=x.shape, indptr_host=ip,
+                            validate=False)
     if isinstance(x, torch.Tensor):
         if x.dim() != 2:
-            raise ValueError("tl.cnv_states: X must be 2-D")
+            raise ValueError(f"{who}: X must be 2-D")
         t = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float64)
         return DeviceMatrix(dense=t.cuda().contiguous())
     if sp.issparse(x):
@@ -1847,10 +1833,27 @@ def states_input(x):
         return to_device_matrix(x)
     a = np.asarray(x)
     if a.ndim != 2:
-        raise ValueError("tl.cnv_states: X must be 2-D")
+        raise ValueError(f"{who}: X must be 2-D")
     if a.dtype not in (np.float32, np.float64):
         a = a.astype(np.float64)
-    return to_device_matrix(a)
+    return np.ascontiguousarray(a) if slabs else to_device_matrix(a)
+
+
+def _chr_start_upload(torch, chr_start):
+    """(CUDA int32 copy, C) of ``chr_start``, the host array of C + 1 ascending window numbers from 0 to W; on the
+    current device."""
+    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
+    return torch.from_numpy(chr_start).cuda(), int(chr_start.shape[0]) - 1
+
+
+def _group_lists_upload(torch, rows, group_ptr):
+    """(rows, group_ptr, G) as CUDA int64 tensors: host arrays are uploaded to the current device, CUDA tensors are used
+    as they are."""
+    d_rows, d_ptr = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64)).cuda()
+                     for v in (rows, group_ptr))
+    assert d_rows.dtype == torch.int64 and d_ptr.dtype == torch.int64 and d_rows.is_cuda and d_ptr.is_cuda
+    assert d_ptr.shape[0] >= 1
+    return d_rows, d_ptr, int(d_ptr.shape[0]) - 1
 
 
 def states_rowsq(dm: DeviceMatrix):
@@ -1859,7 +1862,7 @@ def states_rowsq(dm: DeviceMatrix):
     torch = _torch()
     lib = _lib.load()
     with torch.cuda.device(dm.device):
-        q = torch.empty(max(dm.shape[0], 1), dtype=torch.float64, device="cuda")[:dm.shape[0]]
+        q = _empty(torch, dm.shape[0], torch.float64)
         flag = torch.empty(1, dtype=torch.int32, device="cuda")
         m = dm.c_struct()
         _lib.check(lib.icv_states_rowsq(C.byref(m), _ptr(q), _ptr(flag), _stream_ptr(torch)))
@@ -1883,12 +1886,12 @@ def states_stored_values(dm: DeviceMatrix):
     return dm.dense if dm.format == _lib.ICV_DENSE else dm.data
 
 
-def states_flag_and_absmax(flag, absmax):
-    """(non-finite flag as a bool, largest |v| as a float) of :func:`states_rowsq` and :func:`states_absmax`: the two
-    device scalars in one copy to the host (the one synchronisation the flag needs anyway)."""
+def flag_and_absmax(flag, absmax):
+    """(flag word as an int, largest |v| as a float) of :func:`states_rowsq` or :func:`group_profiles` and
+    :func:`states_absmax`: the two device scalars in one copy to the host (the one synchronisation the flag needs anyway)."""
     torch = _torch()
     both = torch.cat([flag.to(torch.float64).reshape(1), absmax]).cpu().tolist()
-    return bool(both[0]), float(both[1])
+    return int(both[0]), float(both[1])
 
 
 def _hmm_call(entry, dm: DeviceMatrix, chr_start, scalars, outputs):
@@ -1897,12 +1900,11 @@ def _hmm_call(entry, dm: DeviceMatrix, chr_start, scalars, outputs):
     ``dm``'s device, and ``entry(matrix, chr_start, C, *scalars, *outputs, stream)`` is enqueued on the current stream.
     Returns the outputs; nothing is read back."""
     torch = _torch()
-    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
     with torch.cuda.device(dm.device):
-        cs = torch.from_numpy(chr_start).cuda()
+        cs, n_chr = _chr_start_upload(torch, chr_start)
         out = outputs(torch)
         m = dm.c_struct()
-        _lib.check(entry(C.byref(m), _ptr(cs), int(chr_start.shape[0]) - 1, *(float(v) for v in scalars),
+        _lib.check(entry(C.byref(m), _ptr(cs), n_chr, *(float(v) for v in scalars),
                          *(_ptr(t) for t in out), _stream_ptr(torch)))
     return out
 
@@ -1955,23 +1957,21 @@ def states_filter(states, p_neutral, chr_start, max_p_normal):
     assert p_neutral.is_cuda and p_neutral.dtype == torch.float64 and p_neutral.is_contiguous()
     assert p_neutral.shape == states.shape and p_neutral.device == states.device
     n, w = int(states.shape[0]), int(states.shape[1])
-    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
     with torch.cuda.device(states.device):
-        cs = torch.from_numpy(chr_start).cuda()
+        cs, n_chr = _chr_start_upload(torch, chr_start)
         filtered = torch.empty((n, w), dtype=torch.int8, device="cuda")
-        count = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-        removed = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        count, removed = _empty(torch, n, torch.int32), _empty(torch, n, torch.int32)
         bad = torch.empty(1, dtype=torch.int32, device="cuda")
-        _lib.check(lib.icv_states_filter(_ptr(states), _ptr(p_neutral), n, w, _ptr(cs), int(chr_start.shape[0]) - 1,
+        _lib.check(lib.icv_states_filter(_ptr(states), _ptr(p_neutral), n, w, _ptr(cs), n_chr,
                                          float(max_p_normal), _ptr(filtered), _ptr(count), _ptr(removed), _ptr(bad),
                                          _stream_ptr(torch)))
     return filtered, count, removed, bad
 
 
 # ---- tl.cnv_segments: runs of the int8 call matrix, group votes and consensus on the device (icv_segments_*, icv_state_*) --
-def segments_input(x):
-    """The int8 call matrix tl.cnv_segments reads, as a contiguous CUDA tensor: a CUDA tensor is read where it lies, a
-    host array is uploaded once.  (The caller checked shape and dtype.)"""
+def dense_input(x):
+    """A dense array (the int8 calls, the float64 posteriors) as a contiguous CUDA tensor: a CUDA tensor is read where it
+    lies, a host array is uploaded once.  (The caller checked shape and dtype.)"""
     torch = _torch()
     if isinstance(x, torch.Tensor):
         return x.cuda().contiguous()
@@ -1990,21 +1990,16 @@ def segments_tables(states, chr_start):
     lib = _lib.load()
     assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
     n, w = int(states.shape[0]), int(states.shape[1])
-    chr_start = np.ascontiguousarray(chr_start, dtype=np.int32)
-    n_chr = int(chr_start.shape[0]) - 1
     with torch.cuda.device(states.device):
         st = _stream_ptr(torch)
-        cs = torch.from_numpy(chr_start).cuda()
-        counts = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")[:n]
+        cs, n_chr = _chr_start_upload(torch, chr_start)
+        counts = _empty(torch, n, torch.int64)
         bad = torch.empty(1, dtype=torch.int32, device="cuda")
         _lib.check(lib.icv_segments_count(_ptr(states), n, w, _ptr(cs), n_chr, _ptr(counts), _ptr(bad), st))
         offsets = torch.empty(n + 1, dtype=torch.int64, device="cuda")
         _lib.check(lib.icv_row_offsets(_ptr(counts), n, _ptr(offsets), st))
         n_seg = int(offsets[-1].item())
-        row = torch.empty(max(n_seg, 1), dtype=torch.int64, device="cuda")[:n_seg]
-        start = torch.empty(max(n_seg, 1), dtype=torch.int32, device="cuda")[:n_seg]
-        end = torch.empty(max(n_seg, 1), dtype=torch.int32, device="cuda")[:n_seg]
-        state = torch.empty(max(n_seg, 1), dtype=torch.int8, device="cuda")[:n_seg]
+        row, start, end, state = (_empty(torch, n_seg, t) for t in (torch.int64, torch.int32, torch.int32, torch.int8))
         _lib.check(lib.icv_segments_fill(_ptr(states), n, w, _ptr(cs), n_chr, _ptr(offsets), n_seg, _ptr(row), _ptr(start),
                                          _ptr(end), _ptr(state), st))
     return counts, offsets, row, start, end, state, bad
@@ -2018,17 +2013,13 @@ def state_votes(states, rows, group_ptr):
     lib = _lib.load()
     assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
     n, w = int(states.shape[0]), int(states.shape[1])
-    rows = np.ascontiguousarray(rows, dtype=np.int64)
-    group_ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
-    g = int(group_ptr.shape[0]) - 1
-    assert g >= 0 and int(group_ptr[0]) == 0 and int(group_ptr[-1]) == rows.shape[0]
+    assert int(group_ptr[0]) == 0 and int(group_ptr[-1]) == len(rows)
     with torch.cuda.device(states.device):
-        d_rows = torch.from_numpy(rows).cuda()
-        d_ptr = torch.from_numpy(group_ptr).cuda()
+        d_rows, d_ptr, g = _group_lists_upload(torch, rows, group_ptr)
         loss = torch.empty((g, w), dtype=torch.int32, device="cuda")
         gain = torch.empty((g, w), dtype=torch.int32, device="cuda")
         bad = torch.empty(1, dtype=torch.int32, device="cuda")
-        _lib.check(lib.icv_state_votes(_ptr(states), n, w, _ptr(d_rows), int(rows.shape[0]), _ptr(d_ptr), g, _ptr(loss),
+        _lib.check(lib.icv_state_votes(_ptr(states), n, w, _ptr(d_rows), int(d_rows.shape[0]), _ptr(d_ptr), g, _ptr(loss),
                                        _ptr(gain), _ptr(bad), _stream_ptr(torch)))
     return loss, gain, bad
 
@@ -2054,8 +2045,7 @@ def segments_support(row, start, end, state, loss, gain):
     n_seg = int(row.shape[0])
     g, w = int(loss.shape[0]), int(loss.shape[1])
     with torch.cuda.device(loss.device):
-        cells_min = torch.empty(max(n_seg, 1), dtype=torch.int32, device="cuda")[:n_seg]
-        cells_sum = torch.empty(max(n_seg, 1), dtype=torch.int64, device="cuda")[:n_seg]
+        cells_min, cells_sum = _empty(torch, n_seg, torch.int32), _empty(torch, n_seg, torch.int64)
         _lib.check(lib.icv_segments_support(_ptr(row), _ptr(start), _ptr(end), _ptr(state), n_seg, _ptr(loss), _ptr(gain), g,
                                             w, _ptr(cells_min), _ptr(cells_sum), _stream_ptr(torch)))
     return cells_min, cells_sum
@@ -2070,11 +2060,8 @@ def group_profiles(dm: DeviceMatrix, rows, group_ptr, shift):
     torch = _torch()
     lib = _lib.load()
     with torch.cuda.device(dm.device):
-        d_rows, d_ptr = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64)).cuda()
-                         for v in (rows, group_ptr))
-        assert d_rows.dtype == torch.int64 and d_ptr.dtype == torch.int64 and d_rows.is_cuda and d_ptr.is_cuda
-        g, w = int(d_ptr.shape[0]) - 1, int(dm.shape[1])
-        assert g >= 0
+        d_rows, d_ptr, g = _group_lists_upload(torch, rows, group_ptr)
+        w = int(dm.shape[1])
         total = torch.empty((g, w), dtype=torch.int64, device="cuda")
         stored = torch.empty((g, w), dtype=torch.int32, device="cuda")
         flags = torch.empty(1, dtype=torch.int32, device="cuda")
@@ -2096,11 +2083,3 @@ def group_profiles_finish(total, stored, d_ptr, shift):
         _lib.check(lib.icv_group_profiles_finish(_ptr(total), _ptr(stored), _ptr(d_ptr), g, w, int(shift), _ptr(mean),
                                                  _ptr(fraction), _stream_ptr(torch)))
     return mean, fraction
-
-
-def group_profiles_flags_and_absmax(flags, absmax):
-    """(flags as an int, largest |v| as a float) of :func:`group_profiles` and :func:`states_absmax`: the two device
-    scalars in one copy to the host."""
-    torch = _torch()
-    both = torch.cat([flags.to(torch.float64).reshape(1), absmax]).cpu().tolist()
-    return int(both[0]), float(both[1])

@@ -15,6 +15,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -67,6 +68,27 @@ int fail(int code, const std::string& msg) {
             return fail(ICV_ERR_HIP, std::string(#expr) + ": " + hipGetErrorName(e_) + " (" + \
                                          hipGetErrorString(e_) + ")");                         \
     } while (0)
+
+// One instantiation by an element-type code (ICV_F32 / ICV_F64, checked by the caller): f, a generic lambda, gets a value
+// of the element type.  by_matrix adds std::true_type for a CSR matrix and std::false_type for a dense one.
+template <typename F>
+auto by_dtype(int32_t dtype, F&& f) {
+    return dtype == ICV_F32 ? f(float{}) : f(double{});
+}
+template <typename F>
+auto by_matrix(const icv_matrix* m, F&& f) {
+    return by_dtype(m->dtype,
+                    [&](auto t) { return m->format == ICV_CSR ? f(t, std::true_type{}) : f(t, std::false_type{}); });
+}
+
+// what every entry point that takes a matrix checks first: a row count, an element type and a format that exist
+bool matrix_header_ok(const icv_matrix* m) {
+    return m && m->n_rows >= 0 && (m->dtype == ICV_F32 || m->dtype == ICV_F64) &&
+           (m->format == ICV_DENSE || m->format == ICV_CSR);
+}
+// the pointer its format cannot do without: the values of a dense matrix, the row offsets of a CSR one (a CSR without
+// stored entries may come with null indices / values: they are never read then)
+bool matrix_complete(const icv_matrix* m) { return m->format == ICV_DENSE ? m->values != nullptr : m->indptr != nullptr; }
 
 // Developer knobs (environment variables that force a kernel route / geometry for A/B timing and for the tests that
 // compare the kernels with each other).  They are read ONCE, at the first dispatch, not on every call (a
@@ -2607,12 +2629,10 @@ int icv_csr_row_abs_sum(const void* data, int32_t dtype, const int64_t* indptr, 
     if (n_rows < 1) return ICV_OK;
     dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == ICV_F32)
-        hipLaunchKernelGGL(icv::k_csr_row_abs_sum<float>, grid, block, 0, st, static_cast<const float*>(data), indptr,
-                           n_rows, row_sum);
-    else
-        hipLaunchKernelGGL(icv::k_csr_row_abs_sum<double>, grid, block, 0, st, static_cast<const double*>(data), indptr,
-                           n_rows, row_sum);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_csr_row_abs_sum<T>, grid, block, 0, st, static_cast<const T*>(data), indptr, n_rows, row_sum);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -2649,12 +2669,11 @@ int icv_csr_densify(const void* data, int32_t dtype, const int64_t* indptr, cons
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(out, 0, (size_t)((n_sel - 1) * ldo + n_cols) * sizeof(float), st));
     dim3 grid((unsigned)((n_sel + 3) / 4)), block(256);
-    if (dtype == ICV_F32)
-        hipLaunchKernelGGL(icv::k_csr_densify<float>, grid, block, 0, st, static_cast<const float*>(data), indptr, indices,
-                           rows, n_sel, out, ldo);
-    else
-        hipLaunchKernelGGL(icv::k_csr_densify<double>, grid, block, 0, st, static_cast<const double*>(data), indptr,
-                           indices, rows, n_sel, out, ldo);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_csr_densify<T>, grid, block, 0, st, static_cast<const T*>(data), indptr, indices, rows,
+                           n_sel, out, ldo);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -2663,8 +2682,7 @@ static_assert(icv::kPcaKB == ICV_GRAM_BLOCK, "the header's block size is the ker
 
 int icv_gram_f64(const icv_matrix* m, int32_t panel_dtype, void* panel, int64_t panel_ld, double* g, int64_t ldg,
                  int32_t accumulate, void* stream) {
-    if (!m || !g || m->n_rows < 0 || m->n_cols < 1 || ldg < m->n_cols || (panel_dtype != ICV_F32 && panel_dtype != ICV_F64) ||
-        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR))
+    if (!matrix_header_ok(m) || !g || m->n_cols < 1 || ldg < m->n_cols || (panel_dtype != ICV_F32 && panel_dtype != ICV_F64))
         return fail(ICV_ERR_INVALID, "bad gram_f64 arguments");
     const int n = m->n_cols, n_t = (n + icv::kPcaT - 1) / icv::kPcaT, n_tri = n_t * (n_t + 1) / 2;
     if (m->n_rows > 0 && (!panel || panel_ld < (int64_t)n_t * icv::kPcaT))
@@ -2680,18 +2698,18 @@ int icv_gram_f64(const icv_matrix* m, int32_t panel_dtype, void* panel, int64_t 
     const size_t esz = panel_dtype == ICV_F32 ? 4 : 8;
     HIP_TRY(hipMemsetAsync(panel, 0, (size_t)n_pad * panel_ld * esz, st));
     const dim3 rgrid((unsigned)((rows + 3) / 4)), rblock(256);
-#define ICV_PANEL(T, P)                                                                                                \
-    if (m->format == ICV_CSR)                                                                                          \
-        hipLaunchKernelGGL((icv::k_pca_panel_csr<T, P>), rgrid, rblock, 0, st, (const T*)m->values, m->indptr,       \
-                           m->indices, rows, (P*)panel, panel_ld);                                                     \
-    else                                                                                                               \
-        hipLaunchKernelGGL((icv::k_pca_panel_dense<T, P>), rgrid, rblock, 0, st, (const T*)m->values, m->ld, rows, n, \
-                           (P*)panel, panel_ld);
-    if (m->dtype == ICV_F32 && panel_dtype == ICV_F32) { ICV_PANEL(float, float) }
-    else if (m->dtype == ICV_F32) { ICV_PANEL(float, double) }
-    else if (panel_dtype == ICV_F32) { ICV_PANEL(double, float) }
-    else { ICV_PANEL(double, double) }
-#undef ICV_PANEL
+    by_matrix(m, [&](auto t, auto csr) {
+        by_dtype(panel_dtype, [&](auto p) {
+            using T = decltype(t);
+            using P = decltype(p);
+            if constexpr (decltype(csr)::value)
+                hipLaunchKernelGGL((icv::k_pca_panel_csr<T, P>), rgrid, rblock, 0, st, (const T*)m->values, m->indptr,
+                                   m->indices, rows, (P*)panel, panel_ld);
+            else
+                hipLaunchKernelGGL((icv::k_pca_panel_dense<T, P>), rgrid, rblock, 0, st, (const T*)m->values, m->ld, rows, n,
+                                   (P*)panel, panel_ld);
+        });
+    });
     HIP_TRY(hipGetLastError());
     // partial tiles of up to 256 MB per launch pair; the reduction adds them to G in block order either way
     const int64_t n_blocks = (n_pad + icv::kPcaKB - 1) / icv::kPcaKB;
@@ -2705,12 +2723,11 @@ int icv_gram_f64(const icv_matrix* m, int32_t panel_dtype, void* panel, int64_t 
         const int64_t c0 = b0 * icv::kPcaKB;
         const int64_t np = n_pad - c0 < nb * icv::kPcaKB ? n_pad - c0 : nb * icv::kPcaKB;
         const dim3 grid((unsigned)n_tri, (unsigned)nb);
-        if (panel_dtype == ICV_F32)
-            hipLaunchKernelGGL(icv::k_gram_f64<float>, grid, dim3(256), 0, st, (const float*)panel + c0 * panel_ld,
-                               panel_ld, np, n_t, part_b.as<double>());
-        else
-            hipLaunchKernelGGL(icv::k_gram_f64<double>, grid, dim3(256), 0, st, (const double*)panel + c0 * panel_ld,
-                               panel_ld, np, n_t, part_b.as<double>());
+        by_dtype(panel_dtype, [&](auto p) {
+            using P = decltype(p);
+            hipLaunchKernelGGL(icv::k_gram_f64<P>, grid, dim3(256), 0, st, (const P*)panel + c0 * panel_ld, panel_ld, np,
+                               n_t, part_b.as<double>());
+        });
         hipLaunchKernelGGL(icv::k_gram_reduce, dim3((unsigned)n_tri), dim3(256), 0, st, part_b.as<double>(), (int)nb,
                            n_t, n, g, ldg, (accumulate || b0 > 0) ? 1 : 0);
     }
@@ -2720,24 +2737,23 @@ int icv_gram_f64(const icv_matrix* m, int32_t panel_dtype, void* panel, int64_t 
 
 int icv_project(const icv_matrix* m, const double* v, int32_t k, const double* shift, int32_t out_dtype, void* out,
                 int64_t ldo, void* stream) {
-    if (!m || !v || !out || k < 1 || ldo < k || m->n_rows < 0 || (out_dtype != ICV_F32 && out_dtype != ICV_F64) ||
-        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR))
+    if (!matrix_header_ok(m) || !v || !out || k < 1 || ldo < k || (out_dtype != ICV_F32 && out_dtype != ICV_F64))
         return fail(ICV_ERR_INVALID, "bad project arguments");
     if (m->n_rows == 0) return ICV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((m->n_rows + 3) / 4)), block(256);
-#define ICV_PROJ(T, O)                                                                                                 \
-    if (m->format == ICV_CSR)                                                                                          \
-        hipLaunchKernelGGL((icv::k_csr_project<T, O>), grid, block, 0, st, (const T*)m->values, m->indptr, m->indices, \
-                           m->n_rows, v, k, shift, (O*)out, ldo);                                                      \
-    else                                                                                                               \
-        hipLaunchKernelGGL((icv::k_dense_project<T, O>), grid, block, 0, st, (const T*)m->values, m->ld, m->n_rows,   \
-                           m->n_cols, v, k, shift, (O*)out, ldo);
-    if (m->dtype == ICV_F32 && out_dtype == ICV_F32) { ICV_PROJ(float, float) }
-    else if (m->dtype == ICV_F32) { ICV_PROJ(float, double) }
-    else if (out_dtype == ICV_F32) { ICV_PROJ(double, float) }
-    else { ICV_PROJ(double, double) }
-#undef ICV_PROJ
+    by_matrix(m, [&](auto t, auto csr) {
+        by_dtype(out_dtype, [&](auto o) {
+            using T = decltype(t);
+            using O = decltype(o);
+            if constexpr (decltype(csr)::value)
+                hipLaunchKernelGGL((icv::k_csr_project<T, O>), grid, block, 0, st, (const T*)m->values, m->indptr, m->indices,
+                                   m->n_rows, v, k, shift, (O*)out, ldo);
+            else
+                hipLaunchKernelGGL((icv::k_dense_project<T, O>), grid, block, 0, st, (const T*)m->values, m->ld, m->n_rows,
+                                   m->n_cols, v, k, shift, (O*)out, ldo);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -4008,8 +4024,7 @@ namespace {
 // window takes; params_ok, params_rule: its verdict on the model's scalars and the words for it.
 int hmm_check(const std::string& who, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, bool outputs_ok, int cap,
               int lds_per_window, bool params_ok, const char* params_rule) {
-    if (!m || !chr_start || !outputs_ok || n_chr < 1 || m->n_rows < 0 || (m->dtype != ICV_F32 && m->dtype != ICV_F64) ||
-        (m->format != ICV_DENSE && m->format != ICV_CSR))
+    if (!matrix_header_ok(m) || !chr_start || !outputs_ok || n_chr < 1)
         return fail(ICV_ERR_INVALID, "bad " + who + " arguments");
     if (m->n_cols < 1 || m->n_cols > cap)
         return fail(ICV_ERR_INVALID, who + ": n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
@@ -4017,7 +4032,7 @@ int hmm_check(const std::string& who, const icv_matrix* m, const int32_t* chr_st
                                          " bytes of LDS per window)");
     if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, who + ": more chromosomes than windows");
     if (!params_ok) return fail(ICV_ERR_INVALID, who + ": " + params_rule);
-    if (m->format == ICV_DENSE ? (m->ld < m->n_cols || !m->values) : !m->indptr)
+    if (!matrix_complete(m) || (m->format == ICV_DENSE && m->ld < m->n_cols))
         return fail(ICV_ERR_INVALID, who + ": incomplete matrix");
     if (m->n_rows > 0x7fffffffLL) return fail(ICV_ERR_UNSUPPORTED, who + ": more than 2^31 - 1 rows in one call");
     return ICV_OK;
@@ -4031,28 +4046,21 @@ bool po_params_ok(double amplitude, double h, double ps, double pw) {
 constexpr const char* kPoParamsRule =
     "amplitude and h must be finite and > 0, ps = 1 - p and pw = p / 2 for a p in (0, 1) with pw a normal float64";
 
-// one instantiation of a chain kernel over the rows of m, one wavefront per row, with lds bytes of dynamic LDS; args: what
-// the kernel takes after (val, indptr, indices, ld, W, chr_start, C)
-template <typename T, typename Kernel, typename... Args>
-int hmm_launch(Kernel kern, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, size_t lds, void* stream,
-               Args... args) {
+// A chain kernel over the rows of m, one wavefront per row, with lds bytes of dynamic LDS.  pick(t, csr) returns the kernel's
+// instantiation for the element type of t and the format (by_matrix); args: what the kernel takes after
+// (val, indptr, indices, ld, W, chr_start, C)
+template <typename Pick, typename... Args>
+int hmm_launch(Pick pick, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, size_t lds, void* stream, Args... args) {
     if (m->n_rows == 0) return ICV_OK;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)m->n_rows), dim3(64), lds, static_cast<hipStream_t>(stream), (const T*)m->values,
-                       m->indptr, m->indices, m->ld, m->n_cols, chr_start, n_chr, args...);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return by_matrix(m, [&](auto t, auto csr) {
+        auto kern = pick(t, csr);
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)m->n_rows), dim3(64), lds, static_cast<hipStream_t>(stream),
+                           (const decltype(t)*)m->values, m->indptr, m->indices, m->ld, m->n_cols, chr_start, n_chr, args...);
+        HIP_TRY(hipGetLastError());
+        return (int)ICV_OK;
+    });
 }
-
-// KERNEL<float | double, CSR | dense> by m's dtype and format
-#define ICV_HMM_LAUNCH(KERNEL, lds, ...)                                                                               \
-    (m->format == ICV_CSR                                                                                              \
-         ? (m->dtype == ICV_F32                                                                                        \
-                ? hmm_launch<float>(icv::KERNEL<float, true>, m, chr_start, n_chr, lds, stream, __VA_ARGS__)           \
-                : hmm_launch<double>(icv::KERNEL<double, true>, m, chr_start, n_chr, lds, stream, __VA_ARGS__))        \
-         : (m->dtype == ICV_F32                                                                                        \
-                ? hmm_launch<float>(icv::KERNEL<float, false>, m, chr_start, n_chr, lds, stream, __VA_ARGS__)          \
-                : hmm_launch<double>(icv::KERNEL<double, false>, m, chr_start, n_chr, lds, stream, __VA_ARGS__)))
 
 }  // namespace
 
@@ -4063,26 +4071,23 @@ static_assert(icv::kStMaxWindows == ICV_STATES_MAX_WINDOWS, "the header's window
 static_assert((size_t)icv::kStMaxWindows * icv::kStLdsPerWindow <= (size_t)icv::kLdsLimit, "one cell fits a CU's LDS");
 
 int icv_states_rowsq(const icv_matrix* m, double* rowsq, int32_t* nonfinite, void* stream) {
-    if (!m || !rowsq || !nonfinite || m->n_rows < 0 || m->n_cols < 0 || (m->dtype != ICV_F32 && m->dtype != ICV_F64) ||
-        (m->format != ICV_DENSE && m->format != ICV_CSR) || (m->format == ICV_DENSE && m->ld < m->n_cols))
+    if (!matrix_header_ok(m) || !rowsq || !nonfinite || m->n_cols < 0 || (m->format == ICV_DENSE && m->ld < m->n_cols))
         return fail(ICV_ERR_INVALID, "bad states_rowsq arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(nonfinite, 0, sizeof(int32_t), st));
     if (m->n_rows == 0) return ICV_OK;
-    // (a CSR without stored entries may come with null indices / values: they are never read then)
-    if (m->format == ICV_DENSE ? (!m->values && m->n_cols > 0) : !m->indptr)
+    if (!matrix_complete(m) && (m->format == ICV_CSR || m->n_cols > 0))  // (a dense matrix of no columns has no values)
         return fail(ICV_ERR_INVALID, "states_rowsq: incomplete matrix");
     const dim3 grid((unsigned)((m->n_rows + 255) / 256)), block(256);
-#define ICV_ROWSQ(T)                                                                                                   \
-    if (m->format == ICV_CSR)                                                                                          \
-        hipLaunchKernelGGL(icv::k_states_rowsq_csr<T>, grid, block, 0, st, (const T*)m->values, m->indptr, m->n_rows,  \
-                           rowsq, nonfinite);                                                                          \
-    else                                                                                                               \
-        hipLaunchKernelGGL(icv::k_states_rowsq_dense<T>, grid, block, 0, st, (const T*)m->values, m->ld, m->n_rows,    \
-                           m->n_cols, rowsq, nonfinite);
-    if (m->dtype == ICV_F32) { ICV_ROWSQ(float) }
-    else { ICV_ROWSQ(double) }
-#undef ICV_ROWSQ
+    by_matrix(m, [&](auto t, auto csr) {
+        using T = decltype(t);
+        if constexpr (decltype(csr)::value)
+            hipLaunchKernelGGL(icv::k_states_rowsq_csr<T>, grid, block, 0, st, (const T*)m->values, m->indptr, m->n_rows, rowsq,
+                               nonfinite);
+        else
+            hipLaunchKernelGGL(icv::k_states_rowsq_dense<T>, grid, block, 0, st, (const T*)m->values, m->ld, m->n_rows,
+                               m->n_cols, rowsq, nonfinite);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -4093,8 +4098,8 @@ int icv_states_viterbi(const icv_matrix* m, const int32_t* chr_start, int32_t n_
                            std::isfinite(stay) && std::isfinite(sw);
     ICV_TRY(hmm_check("states_viterbi", m, chr_start, n_chr, states && nonneutral, ICV_STATES_MAX_WINDOWS,
                       icv::kStLdsPerWindow, params_ok, "amplitude and h must be finite and > 0, stay and sw finite"));
-    return ICV_HMM_LAUNCH(k_states_viterbi, icv::st_lds_bytes(m->n_cols), icv::StParams{amplitude, h, stay, sw}, states,
-                          nonneutral);
+    return hmm_launch([](auto t, auto csr) { return icv::k_states_viterbi<decltype(t), decltype(csr)::value>; }, m, chr_start,
+                      n_chr, icv::st_lds_bytes(m->n_cols), stream, icv::StParams{amplitude, h, stay, sw}, states, nonneutral);
 }
 
 int icv_states_fraction(const int32_t* nonneutral, int64_t n_rows, int32_t n_cols, double* fraction, void* stream) {
@@ -4126,6 +4131,20 @@ bool seg_bad_shape(const void* states, int64_t n_rows, int32_t n_cols, const int
 
 constexpr int64_t kSegMaxBlocks = 0x7fffffffLL;
 
+// k_seg_rows<fill> over all rows with the chromosome mask of the call; who: the entry point without icv_
+int seg_rows_launch(bool fill, const char* who, const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start,
+                    int32_t n_chr, hipStream_t st, int64_t* counts, int32_t* bad, const int64_t* offsets, int64_t n_segments,
+                    int64_t* seg_row, int32_t* seg_start, int32_t* seg_end, int8_t* seg_state) {
+    const int64_t blocks = (n_rows + icv::kSegRowsPerBlock - 1) / icv::kSegRowsPerBlock;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, std::string(who) + ": too many rows for one call");
+    AsyncBuf mask;
+    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
+    hipLaunchKernelGGL(fill ? icv::k_seg_rows<true> : icv::k_seg_rows<false>, dim3((unsigned)blocks), dim3(64 * icv::kSegRowsPerBlock), 0, st, states, n_rows,
+                       n_cols, mask.as<uint32_t>(), counts, bad, offsets, n_segments, seg_row, seg_start, seg_end, seg_state);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
 }  // namespace
 
 int icv_segments_count(const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start, int32_t n_chr,
@@ -4135,15 +4154,8 @@ int icv_segments_count(const int8_t* states, int64_t n_rows, int32_t n_cols, con
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
     if (n_rows == 0) return ICV_OK;
-    const int64_t blocks = (n_rows + icv::kSegRowsPerBlock - 1) / icv::kSegRowsPerBlock;
-    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "segments_count: too many rows for one call");
-    AsyncBuf mask;
-    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
-    hipLaunchKernelGGL(icv::k_seg_rows<false>, dim3((unsigned)blocks), dim3(64 * icv::kSegRowsPerBlock), 0, st, states,
-                       n_rows, n_cols, mask.as<uint32_t>(), counts, bad, (const int64_t*)nullptr, (int64_t)0,
-                       (int64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int8_t*)nullptr);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return seg_rows_launch(false, "segments_count", states, n_rows, n_cols, chr_start, n_chr, st, counts, bad, nullptr, 0,
+                           nullptr, nullptr, nullptr, nullptr);
 }
 
 int icv_segments_fill(const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start, int32_t n_chr,
@@ -4153,16 +4165,8 @@ int icv_segments_fill(const int8_t* states, int64_t n_rows, int32_t n_cols, cons
         (n_segments > 0 && (!seg_row || !seg_start || !seg_end || !seg_state)))
         return fail(ICV_ERR_INVALID, "bad segments_fill arguments");
     if (n_rows == 0 || n_segments == 0) return ICV_OK;
-    const int64_t blocks = (n_rows + icv::kSegRowsPerBlock - 1) / icv::kSegRowsPerBlock;
-    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "segments_fill: too many rows for one call");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    AsyncBuf mask;
-    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
-    hipLaunchKernelGGL(icv::k_seg_rows<true>, dim3((unsigned)blocks), dim3(64 * icv::kSegRowsPerBlock), 0, st, states,
-                       n_rows, n_cols, mask.as<uint32_t>(), (int64_t*)nullptr, (int32_t*)nullptr, offsets, n_segments,
-                       seg_row, seg_start, seg_end, seg_state);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return seg_rows_launch(true, "segments_fill", states, n_rows, n_cols, chr_start, n_chr, static_cast<hipStream_t>(stream),
+                           nullptr, nullptr, offsets, n_segments, seg_row, seg_start, seg_end, seg_state);
 }
 
 int icv_state_votes(const int8_t* states, int64_t n_rows, int32_t n_cols, const int64_t* rows, int64_t n_listed,
@@ -4224,8 +4228,8 @@ int icv_posterior_chains(const icv_matrix* m, const int32_t* chr_start, int32_t 
                          double ps, double pw, double* neutral, double* loss, double* gain, void* stream) {
     ICV_TRY(hmm_check("posterior_chains", m, chr_start, n_chr, neutral && (loss == nullptr) == (gain == nullptr),
                       ICV_POSTERIOR_MAX_WINDOWS, icv::kPoLdsPerWindow, po_params_ok(amplitude, h, ps, pw), kPoParamsRule));
-    return ICV_HMM_LAUNCH(k_posterior_chains, icv::po_lds_bytes(m->n_cols), icv::PoParams{amplitude, h, ps, pw}, neutral,
-                          loss, gain);
+    return hmm_launch([](auto t, auto csr) { return icv::k_posterior_chains<decltype(t), decltype(csr)::value>; }, m, chr_start,
+                      n_chr, icv::po_lds_bytes(m->n_cols), stream, icv::PoParams{amplitude, h, ps, pw}, neutral, loss, gain);
 }
 
 int icv_states_filter(const int8_t* states, const double* p_neutral, int64_t n_rows, int32_t n_cols,
@@ -4256,18 +4260,17 @@ int icv_posterior_stats(const icv_matrix* m, const int32_t* chr_start, int32_t n
                         double pw, double* stats, void* stream) {
     ICV_TRY(hmm_check("posterior_stats", m, chr_start, n_chr, stats != nullptr, ICV_POSTERIOR_MAX_WINDOWS,
                       icv::kPoLdsPerWindow, po_params_ok(amplitude, h, ps, pw), kPoParamsRule));
-    return ICV_HMM_LAUNCH(k_posterior_stats, icv::po_lds_bytes(m->n_cols), icv::PoParams{amplitude, h, ps, pw}, stats);
+    return hmm_launch([](auto t, auto csr) { return icv::k_posterior_stats<decltype(t), decltype(csr)::value>; }, m, chr_start,
+                      n_chr, icv::po_lds_bytes(m->n_cols), stream, icv::PoParams{amplitude, h, ps, pw}, stats);
 }
-#undef ICV_HMM_LAUNCH
 
 // ---- tl.cnv_pseudobulk: exact per-group mean profiles -------------------------------------------------------
 static_assert((size_t)icv::kPbTile * 12 <= 48 * 1024, "a tile's accumulators take 48 KB of LDS: three workgroups per CU");
 
 int icv_group_profiles(const icv_matrix* m, const int64_t* rows, int64_t n_listed, const int64_t* group_ptr,
                        int64_t n_groups, int32_t shift, int64_t* sum, int32_t* stored, int32_t* flags, void* stream) {
-    if (!m || n_listed < 0 || (n_listed > 0 && !rows) || !group_ptr || n_groups < 0 || (n_groups > 0 && (!sum || !stored)) ||
-        !flags || shift < 0 || shift > icv::kPbMaxShift || m->n_rows < 0 || m->n_cols < 1 ||
-        (m->dtype != ICV_F32 && m->dtype != ICV_F64) || (m->format != ICV_DENSE && m->format != ICV_CSR) ||
+    if (!matrix_header_ok(m) || n_listed < 0 || (n_listed > 0 && !rows) || !group_ptr || n_groups < 0 ||
+        (n_groups > 0 && (!sum || !stored)) || !flags || shift < 0 || shift > icv::kPbMaxShift || m->n_cols < 1 ||
         (m->format == ICV_DENSE && m->ld < m->n_cols))
         return fail(ICV_ERR_INVALID, "bad group_profiles arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -4277,8 +4280,7 @@ int icv_group_profiles(const icv_matrix* m, const int64_t* rows, int64_t n_liste
     HIP_TRY(hipMemsetAsync(sum, 0, cells * sizeof(int64_t), st));
     HIP_TRY(hipMemsetAsync(stored, 0, cells * sizeof(int32_t), st));
     if (n_listed == 0) return ICV_OK;
-    // (a CSR without stored entries may come with null indices / values: they are never read then)
-    if (m->format == ICV_DENSE ? (!m->values && m->n_rows > 0) : !m->indptr)
+    if (!matrix_complete(m) && (m->format == ICV_CSR || m->n_rows > 0))  // (a dense matrix of no rows has no values)
         return fail(ICV_ERR_INVALID, "group_profiles: incomplete matrix");
     // every group of L rows has ceil(L / slab) <= L / slab + 1 slabs, and a group of no rows has none
     const int64_t n_tiles = ((int64_t)m->n_cols + icv::kPbTile - 1) / icv::kPbTile;
@@ -4293,18 +4295,12 @@ int icv_group_profiles(const icv_matrix* m, const int64_t* rows, int64_t n_liste
     HIP_TRY(hipGetLastError());
     ICV_TRY(icv_row_offsets(slabs.as<int64_t>(), n_groups, slab_off.as<int64_t>(), stream));
     const dim3 grid((unsigned)(max_slabs * n_tiles)), block(icv::kPbThreads);
-#define ICV_PB(T, CSR)                                                                                                    \
-    hipLaunchKernelGGL((icv::k_group_profiles<T, CSR>), grid, block, 0, st, (const T*)m->values, m->indptr, m->indices,   \
-                       m->ld, m->n_rows, m->n_cols, rows, n_listed, group_ptr, n_groups, slab_off.as<int64_t>(),          \
-                       (uint32_t)n_tiles, (int)shift, reinterpret_cast<unsigned long long*>(sum), stored, flags)
-    if (m->format == ICV_CSR) {
-        if (m->dtype == ICV_F32) ICV_PB(float, true);
-        else ICV_PB(double, true);
-    } else {
-        if (m->dtype == ICV_F32) ICV_PB(float, false);
-        else ICV_PB(double, false);
-    }
-#undef ICV_PB
+    by_matrix(m, [&](auto t, auto csr) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((icv::k_group_profiles<T, decltype(csr)::value>), grid, block, 0, st, (const T*)m->values, m->indptr,
+                           m->indices, m->ld, m->n_rows, m->n_cols, rows, n_listed, group_ptr, n_groups, slab_off.as<int64_t>(),
+                           (uint32_t)n_tiles, (int)shift, reinterpret_cast<unsigned long long*>(sum), stored, flags);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }

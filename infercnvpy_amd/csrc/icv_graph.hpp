@@ -1,5 +1,6 @@
 // What tl.leiden, tl.umap and tl.tsne share on the device: the counter hash, the wavefront sum,
 // the row length above which a row takes a workgroup, and the validation of a stored entry of the symmetric CSR graph.
+// Also the search of a group table that tl.cnv_segments and tl.cnv_pseudobulk share (last_group_at).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,18 @@ __host__ __device__ __forceinline__ uint64_t ld_mix(uint64_t z) {  // splitmix64
 __device__ __forceinline__ long long ld_wave_sum(long long v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+// The last g in [0, G) with ptr[g] <= pos, for an ascending ptr with ptr[0] <= pos: the group that holds position pos of a
+// list sorted by group (groups of no entries before it share its offset and are passed over).  0 when G < 2.
+__device__ __forceinline__ int64_t last_group_at(const int64_t* __restrict__ ptr, int64_t G, int64_t pos) {
+    int64_t glo = 0, ghi = G;
+    while (ghi - glo > 1) {
+        const int64_t mid = glo + (ghi - glo) / 2;
+        if (ptr[mid] <= pos) glo = mid;
+        else ghi = mid;
+    }
+    return glo;
 }
 
 // The flags of stored entry i (value x = (float)val[i]) of row v, whose entries start at b: 1 non-finite, 2 negative,

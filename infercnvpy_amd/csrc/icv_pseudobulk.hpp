@@ -20,6 +20,8 @@
 
 #include <cstdint>
 
+#include "icv_graph.hpp"
+
 namespace icv {
 
 constexpr int kPbTile = 4096;     // windows per workgroup: 12 bytes of LDS each
@@ -74,15 +76,7 @@ __global__ __launch_bounds__(kPbThreads) void k_group_profiles(
     if (slab >= slab_off[G]) return;  // (the grid is an upper bound of the slabs; the whole workgroup leaves)
     const int32_t c0 = (int32_t)(blockIdx.x % n_tiles) * kPbTile;
     const int32_t width = W - c0 < kPbTile ? W - c0 : kPbTile;
-    // the group of this slab: the last g with slab_off[g] <= slab (groups of no rows before it have the same offset and
-    // are passed over)
-    int64_t glo = 0, ghi = G;
-    while (ghi - glo > 1) {
-        const int64_t mid = glo + (ghi - glo) / 2;
-        if (slab_off[mid] <= slab) glo = mid;
-        else ghi = mid;
-    }
-    const int64_t g = glo;
+    const int64_t g = last_group_at(slab_off, G, slab);  // the group of this slab
     int64_t lo, hi;
     pb_group_span(group_ptr, g, M, lo, hi);
     const int64_t pos0 = lo + (slab - slab_off[g]) * kPbSlab;

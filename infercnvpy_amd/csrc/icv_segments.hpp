@@ -23,6 +23,8 @@
 
 #include <cstdint>
 
+#include "icv_graph.hpp"
+
 namespace icv {
 
 constexpr int kSegStrip = 16;              // windows per lane and step (one 16-byte load)
@@ -174,14 +176,7 @@ __global__ __launch_bounds__(256) void k_state_votes(const int8_t* __restrict__ 
     const int64_t c0 = (int64_t)(blockIdx.x % n_tiles) * kVoteTile + (int64_t)threadIdx.x * kVoteCols;
     if (pos0 >= pos1 || c0 >= (int64_t)W) return;
     const bool whole = c0 + kVoteCols <= (int64_t)W;
-    // the group of position pos0: the last g with group_ptr[g] <= pos0 (groups of no rows before it are passed over)
-    int64_t glo = 0, ghi = G;
-    while (ghi - glo > 1) {
-        const int64_t mid = glo + (ghi - glo) / 2;
-        if (group_ptr[mid] <= pos0) glo = mid;
-        else ghi = mid;
-    }
-    int64_t g = glo, pos = pos0;
+    int64_t g = last_group_at(group_ptr, G, pos0), pos = pos0;  // the group of position pos0
     bool invalid = false;
     while (pos < pos1 && g < G) {
         int64_t gend = group_ptr[g + 1];

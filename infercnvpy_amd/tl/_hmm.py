@@ -4,6 +4,8 @@
 The three functions must derive the same ``(amplitude, sigma, switch_prob)`` from the same matrix and the same
 arguments (DESIGN.md 4.13 rules 1 and 6), otherwise the posteriors do not belong to the calls and the fit does not start
 where the calls were made.  :func:`resolve` is that derivation; what differs between the callers is an argument of it.
+The argument checks that the functions downstream of the calls share live here too: :func:`chromosome_bounds`,
+:func:`at_least_one` and :func:`call_matrix`.
 """
 from __future__ import annotations
 
@@ -55,6 +57,46 @@ def _positive(name, value, who="tl.cnv_states"):
     if isinstance(value, bool) or not (math.isfinite(v) and v > 0):
         raise ValueError(f"{who}: {name}={value!r} must be finite and > 0")
     return v
+
+
+def at_least_one(who, name, value):
+    """``value`` as an int; ``ValueError`` unless it is an integer >= 1."""
+    try:
+        k = int(value)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{who}: {name}={value!r} must be an integer >= 1") from None
+    if isinstance(value, bool) or k != value or k < 1:
+        raise ValueError(f"{who}: {name}={value!r} must be an integer >= 1")
+    return k
+
+
+def call_matrix(adata, who, key, cnv_key, chr_pos_hint, pkey=None):
+    """(x, post, n, w): the int8 call matrix ``adata.obsm[key]`` of ``tl.cnv_segments`` and ``tl.cnv_states_filter`` after
+    its checks, in the order they are reported: the keys, 2-D, int8, not empty.  ``chr_pos_hint`` ends the message about a
+    missing ``adata.uns[cnv_key]["chr_pos"]``.  With ``pkey``, ``post = adata.obsm[pkey]`` must be there (looked for after
+    ``key``) and be float64 of the same shape (checked before the empty matrix); otherwise ``post`` is None."""
+    if key not in adata.obsm:
+        raise KeyError(f"{who}: {key} not found in adata.obsm. Did you run `tl.cnv_states`?")
+    if pkey is not None and pkey not in adata.obsm:
+        raise KeyError(f"{who}: {pkey} not found in adata.obsm. Did you run `tl.cnv_posteriors`?")
+    if cnv_key not in adata.uns or "chr_pos" not in adata.uns[cnv_key]:
+        raise KeyError(f"{who}: chr_pos not found in adata.uns['{cnv_key}']. Did you run {chr_pos_hint}")
+    x, post = adata.obsm[key], None if pkey is None else adata.obsm[pkey]
+    shape = getattr(x, "shape", None)
+    if shape is None or len(shape) != 2:
+        raise ValueError(f"{who}: {key} must be 2-D")
+    if str(getattr(x, "dtype", None)) not in ("int8", "torch.int8"):
+        raise ValueError(f"{who}: {key} must be int8 (-1 loss, 0 neutral, +1 gain), not "
+                         f"{getattr(x, 'dtype', type(x).__name__)}")
+    if pkey is not None:
+        if tuple(getattr(post, "shape", ())) != tuple(shape):
+            raise ValueError(f"{who}: {pkey} has shape {tuple(getattr(post, 'shape', ()))}, {key} has {tuple(shape)}")
+        if str(getattr(post, "dtype", None)) not in ("float64", "torch.float64"):
+            raise ValueError(f"{who}: {pkey} must be float64, not {getattr(post, 'dtype', type(post).__name__)}")
+    n, w = int(shape[0]), int(shape[1])
+    if n < 1 or w < 1:
+        raise ValueError(f"{who}: empty matrix of shape {(n, w)}")
+    return x, post, n, w
 
 
 def check_emissions(who, key, x, m, amp, h, sig):
@@ -160,14 +202,14 @@ def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch
 
     torch = _engine._torch()
     on_device = isinstance(x, (_engine.PackedCsr, torch.Tensor))
-    dm = _engine.states_input(x)
+    dm = _engine.matrix_input(x, who)
     t0 = time.perf_counter()
     q, flag = _engine.states_rowsq(dm)
     absmax = _engine.states_absmax(_engine.states_stored_values(dm))
     want_q = sum_of_squares or sig is None
     if want_q:
         q_host = q.cpu().numpy()
-    nonfinite, m = _engine.states_flag_and_absmax(flag, absmax)
+    nonfinite, m = _engine.flag_and_absmax(flag, absmax)
     if nonfinite:
         raise ValueError(f"{who}: {key} has non-finite values")
     qs = None

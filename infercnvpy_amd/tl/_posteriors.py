@@ -12,7 +12,7 @@ from __future__ import annotations
 import time
 
 from .. import _engine, _lib
-from ._hmm import chromosome_bounds, resolve
+from ._hmm import call_matrix, chromosome_bounds, resolve
 
 
 def cnv_posteriors(adata, use_rep="cnv", key_added="cnv_posterior", inplace=True, *, amplitude=None, sigma=None,
@@ -138,27 +138,7 @@ def cnv_states_filter(adata, use_rep="cnv_states", posterior_key="cnv_posterior"
     not a number in [0, 1] or a call other than -1 / 0 / +1 raises ``ValueError`` (one flag read back from the device).
     """
     key, pkey = f"X_{use_rep}", f"X_{posterior_key}_neutral"
-    if key not in adata.obsm:
-        raise KeyError(f"tl.cnv_states_filter: {key} not found in adata.obsm. Did you run `tl.cnv_states`?")
-    if pkey not in adata.obsm:
-        raise KeyError(f"tl.cnv_states_filter: {pkey} not found in adata.obsm. Did you run `tl.cnv_posteriors`?")
-    if cnv_key not in adata.uns or "chr_pos" not in adata.uns[cnv_key]:
-        raise KeyError(f"tl.cnv_states_filter: chr_pos not found in adata.uns['{cnv_key}']. Did you run `tl.infercnv`?")
-    x, post = adata.obsm[key], adata.obsm[pkey]
-    shape = getattr(x, "shape", None)
-    if shape is None or len(shape) != 2:
-        raise ValueError(f"tl.cnv_states_filter: {key} must be 2-D")
-    if str(getattr(x, "dtype", None)) not in ("int8", "torch.int8"):
-        raise ValueError(f"tl.cnv_states_filter: {key} must be int8 (-1 loss, 0 neutral, +1 gain), not "
-                         f"{getattr(x, 'dtype', type(x).__name__)}")
-    if tuple(getattr(post, "shape", ())) != tuple(shape):
-        raise ValueError(f"tl.cnv_states_filter: {pkey} has shape {tuple(getattr(post, 'shape', ()))}, {key} has "
-                         f"{tuple(shape)}")
-    if str(getattr(post, "dtype", None)) not in ("float64", "torch.float64"):
-        raise ValueError(f"tl.cnv_states_filter: {pkey} must be float64, not {getattr(post, 'dtype', type(post).__name__)}")
-    n, w = int(shape[0]), int(shape[1])
-    if n < 1 or w < 1:
-        raise ValueError(f"tl.cnv_states_filter: empty matrix of shape {(n, w)}")
+    x, post, n, w = call_matrix(adata, "tl.cnv_states_filter", key, cnv_key, "`tl.infercnv`?", pkey)
     if w > _lib.ICV_FILTER_MAX_WINDOWS:
         raise ValueError(f"tl.cnv_states_filter: {w} windows; a run's int64 sum takes at most "
                          f"{_lib.ICV_FILTER_MAX_WINDOWS}")
@@ -173,9 +153,9 @@ def cnv_states_filter(adata, use_rep="cnv_states", posterior_key="cnv_posterior"
     torch = _engine._torch()
     on_device = isinstance(x, torch.Tensor) or isinstance(post, torch.Tensor)
     t0 = time.perf_counter()
-    states = _engine.segments_input(x)
+    states = _engine.dense_input(x)
     with torch.cuda.device(states.device):
-        p_dev = _engine.segments_input(post).to(states.device)
+        p_dev = _engine.dense_input(post).to(states.device)
         filtered, count, removed, bad = _engine.states_filter(states, p_dev, bounds, thr)
         fraction = _engine.states_fraction(count, w)
         if int(bad.item()):

@@ -16,8 +16,8 @@ import numpy as np
 
 from .. import _engine
 from .._compat import SimpleAnnData
-from ._hmm import chromosome_bounds
-from ._segments import _group_codes
+from ._groups import group_codes, group_table
+from ._hmm import at_least_one, chromosome_bounds
 
 MAX_MAGNITUDE = 1024.0  # rule 2: every stored magnitude is below 2^10
 MAX_SHIFT = 40
@@ -28,22 +28,12 @@ def profile_shift(largest_group):
     return min(MAX_SHIFT, 52 - int(largest_group).bit_length())
 
 
-def _min_cells(value):
-    try:
-        k = int(value)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"tl.cnv_pseudobulk: min_cells={value!r} must be an integer >= 1") from None
-    if isinstance(value, bool) or k != value or k < 1:
-        raise ValueError(f"tl.cnv_pseudobulk: min_cells={value!r} must be an integer >= 1")
-    return k
-
-
 def group_lists(adata, groupby, n_rows, min_cells, key="X_cnv"):
     """(labels, n_cells, dropped, rows, group_ptr) of the groups of ``adata.obs[groupby]`` with at least ``min_cells``
     cells: the kept labels in group order, their int64 sizes, the labels left out, the int64 row numbers of the kept
     groups' cells sorted by group (ascending inside a group) and the G + 1 positions of the groups in ``rows``.  The
     groups are those of ``tl.cnv_segments``; a missing label belongs to none.  ``ValueError`` when no group is kept."""
-    codes, groups = _group_codes(adata, groupby)
+    codes, groups = group_codes(adata, groupby)
     if codes.shape[0] != n_rows:
         raise ValueError(f"tl.cnv_pseudobulk: `{groupby}` has {codes.shape[0]} labels for the {n_rows} rows of {key}")
     sizes = np.bincount(codes[codes >= 0], minlength=len(groups)).astype(np.int64)
@@ -51,13 +41,8 @@ def group_lists(adata, groupby, n_rows, min_cells, key="X_cnv"):
     dropped = [groups[g] for g in np.flatnonzero(sizes < min_cells)]
     if kept.shape[0] == 0:
         raise ValueError(f"tl.cnv_pseudobulk: no group of `{groupby}` has min_cells={min_cells} cells")
-    new_code = np.full(len(groups) + 1, -1, dtype=np.int64)  # (the last slot takes the code -1)
-    new_code[kept] = np.arange(kept.shape[0])
-    codes = new_code[codes]
-    rows = np.argsort(codes, kind="stable")[int((codes < 0).sum()):].astype(np.int64)  # (the -1 codes sort first)
-    group_ptr = np.zeros(kept.shape[0] + 1, dtype=np.int64)
-    group_ptr[1:] = np.cumsum(sizes[kept])
-    return groups[kept], sizes[kept], dropped, rows, group_ptr
+    rows, group_ptr, n_cells = group_table(codes, len(groups), keep=kept, sizes=sizes)
+    return groups[kept], n_cells, dropped, rows, group_ptr
 
 
 def cnv_pseudobulk(adata, groupby="cnv_leiden", *, use_rep="cnv", min_cells=1, return_info=False):
@@ -122,7 +107,7 @@ def cnv_pseudobulk(adata, groupby="cnv_leiden", *, use_rep="cnv", min_cells=1, r
     n, w = int(shape[0]), int(shape[1])
     if n < 1 or w < 1:
         raise ValueError(f"tl.cnv_pseudobulk: empty matrix of shape {(n, w)}")
-    fewest = _min_cells(min_cells)
+    fewest = at_least_one("tl.cnv_pseudobulk", "min_cells", min_cells)
     chr_pos = adata.uns[use_rep]["chr_pos"]
     chromosome_bounds(chr_pos, w)
 
@@ -134,12 +119,12 @@ def cnv_pseudobulk(adata, groupby="cnv_leiden", *, use_rep="cnv", min_cells=1, r
     torch = _engine._torch()
     on_device = isinstance(x, (_engine.PackedCsr, torch.Tensor))
     t0 = time.perf_counter()
-    dm = _engine.states_input(x)
+    dm = _engine.matrix_input(x, "tl.cnv_pseudobulk")
     with torch.cuda.device(dm.device):
         total, stored, flags, d_ptr = _engine.group_profiles(dm, rows, group_ptr, shift)
         absmax = _engine.states_absmax(_engine.states_stored_values(dm))
         mean, fraction = _engine.group_profiles_finish(total, stored, d_ptr, shift)
-        bits, m = _engine.group_profiles_flags_and_absmax(flags, absmax)
+        bits, m = _engine.flag_and_absmax(flags, absmax)
         if bits & 1:
             raise ValueError(f"tl.cnv_pseudobulk: {key} has non-finite values")
         if not m < MAX_MAGNITUDE and isinstance(x, _engine.PackedCsr):

@@ -7,6 +7,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .. import _engine
+from ._groups import group_codes
 
 
 def cnv_score(adata, groupby: str = "cnv_leiden", *, use_rep: str = "cnv", key_added: str = "cnv_score",
@@ -42,15 +43,9 @@ def cnv_score(adata, groupby: str = "cnv_leiden", *, use_rep: str = "cnv", key_a
     # group sums on the device in a fixed order (icv_group_sums): K sums come back, and a host X_cnv and a
     # device-resident one give the same bits.  Labels -> group codes in one vectorised pass (first-appearance order =
     # the reference's `labels.unique()` loop, :65); the counts are the host's own bincount
-    import pandas as pd
-
+    # (what tl.leiden leaves is categorical: the codes are there already and unused categories are groups without rows)
     labels = adata.obs[groupby]
-    if isinstance(getattr(labels, "dtype", None), pd.CategoricalDtype):
-        # what tl.leiden leaves: the codes are there already (-1: missing); unused categories are groups without rows
-        codes, uniques = labels.cat.codes.to_numpy(), labels.cat.categories
-    else:
-        codes, uniques = pd.factorize(np.asarray(labels.values if hasattr(labels, "values") else labels),
-                                      use_na_sentinel=True)
+    codes, uniques = group_codes(adata, groupby)
     codes = codes.astype(np.int32, copy=False)
     n_groups = len(uniques)
     sums, _ = _engine.group_sums(row_abs, codes, n_groups, want_counts=False)

@@ -14,7 +14,8 @@ from fractions import Fraction
 import numpy as np
 
 from .. import _engine
-from ._states import chromosome_bounds
+from ._groups import group_codes, group_table
+from ._hmm import at_least_one, call_matrix, chromosome_bounds
 
 
 def _min_fraction(value):
@@ -25,29 +26,6 @@ def _min_fraction(value):
     if isinstance(value, bool) or not 0 < f <= 1:
         raise ValueError(f"tl.cnv_segments: min_fraction={value!r} must lie in (0, 1]")
     return f
-
-
-def _min_windows(value):
-    try:
-        k = int(value)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"tl.cnv_segments: min_windows={value!r} must be an integer >= 1") from None
-    if isinstance(value, bool) or k != value or k < 1:
-        raise ValueError(f"tl.cnv_segments: min_windows={value!r} must be an integer >= 1")
-    return k
-
-
-def _group_codes(adata, groupby):
-    """(codes int64 n, labels of the G groups): as tl.cnv_score derives them; -1 is a missing label."""
-    import pandas as pd
-
-    labels = adata.obs[groupby]
-    if isinstance(getattr(labels, "dtype", None), pd.CategoricalDtype):
-        codes, uniques = labels.cat.codes.to_numpy(), labels.cat.categories
-    else:
-        codes, uniques = pd.factorize(np.asarray(labels.values if hasattr(labels, "values") else labels),
-                                      use_na_sentinel=True)
-    return np.asarray(codes, dtype=np.int64), np.asarray(uniques)
 
 
 def _chromosome_names(chr_pos, starts):
@@ -109,43 +87,26 @@ def cnv_segments(adata, groupby=None, *, use_rep="cnv_states", cnv_key="cnv", ke
     import pandas as pd
 
     key = f"X_{use_rep}"
-    if key not in adata.obsm:
-        raise KeyError(f"tl.cnv_segments: {key} not found in adata.obsm. Did you run `tl.cnv_states`?")
-    if cnv_key not in adata.uns or "chr_pos" not in adata.uns[cnv_key]:
-        raise KeyError(f"tl.cnv_segments: chr_pos not found in adata.uns['{cnv_key}']. Did you run `tl.cnv_states`? "
-                       "(it reads what `tl.infercnv` leaves there)")
-    x = adata.obsm[key]
-    shape = getattr(x, "shape", None)
-    if shape is None or len(shape) != 2:
-        raise ValueError(f"tl.cnv_segments: {key} must be 2-D")
-    if str(getattr(x, "dtype", None)) not in ("int8", "torch.int8"):
-        raise ValueError(f"tl.cnv_segments: {key} must be int8 (-1 loss, 0 neutral, +1 gain), not "
-                         f"{getattr(x, 'dtype', type(x).__name__)}")
-    n, w = int(shape[0]), int(shape[1])
-    if n < 1 or w < 1:
-        raise ValueError(f"tl.cnv_segments: empty matrix of shape {(n, w)}")
+    x, _, _, w = call_matrix(adata, "tl.cnv_segments", key, cnv_key,
+                             "`tl.cnv_states`? (it reads what `tl.infercnv` leaves there)")
     chr_pos = adata.uns[cnv_key]["chr_pos"]
     bounds = chromosome_bounds(chr_pos, w)
     fraction = _min_fraction(min_fraction)
-    shortest = _min_windows(min_windows)
+    shortest = at_least_one("tl.cnv_segments", "min_windows", min_windows)
     params = {"groupby": groupby, "use_rep": use_rep, "min_fraction": float(fraction), "min_windows": shortest}
     if groupby is not None:
         if groupby not in adata.obs.columns:
             raise ValueError(f"tl.cnv_segments: `{groupby}` not found in `adata.obs`"
                              + (". Did you run `tl.leiden`?" if groupby == "cnv_leiden" else ""))
-        codes, groups = _group_codes(adata, groupby)
+        codes, groups = group_codes(adata, groupby)
         n_groups = len(groups)
-        listed = codes >= 0
-        rows = np.argsort(codes, kind="stable")[int(n - listed.sum()):].astype(np.int64)  # (the -1 codes sort first)
-        n_cells = np.bincount(codes[listed], minlength=n_groups).astype(np.int64)
-        group_ptr = np.zeros(n_groups + 1, dtype=np.int64)
-        group_ptr[1:] = np.cumsum(n_cells)
+        rows, group_ptr, n_cells = group_table(codes, n_groups)
         need = np.asarray([max(1, math.ceil(fraction * int(c))) for c in n_cells], dtype=np.int32)
 
     torch = _engine._torch()
     stage_ms = {}
     t0 = time.perf_counter()
-    states = _engine.segments_input(x)
+    states = _engine.dense_input(x)
     with torch.cuda.device(states.device):
         if groupby is None:
             _, _, row, start, end, state, bad = _engine.segments_tables(states, bounds)

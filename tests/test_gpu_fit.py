@@ -58,7 +58,7 @@ def test_statistics_of_every_case_equal_the_oracle(name):
     want = fo.stats(c["x"], c["chr_pos"], p["amplitude"], p["sigma"], p["switch_prob"])
     assert np.isfinite(want).all()
     h, ps, pw = po.scalars(p["sigma"], p["switch_prob"])
-    dm = _engine.states_input(c["x"])
+    dm = _engine.matrix_input(c["x"], "test")
     got = _engine.posterior_stats(dm, chromosome_bounds(c["chr_pos"], c["x"].shape[1]), amplitude=p["amplitude"], h=h,
                                   ps=ps, pw=pw)
     assert got.is_cuda and str(got.dtype) == "torch.float64" and tuple(got.shape) == want.shape

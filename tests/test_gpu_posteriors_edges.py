@@ -94,7 +94,7 @@ def test_chr_start_with_an_empty_chromosome_and_uncovered_windows(layout, kind):
     stats = fo.stats(x, None, a, sigma, p, bounds=bounds)
     h, ps, pw = po.scalars(sigma, p)
     kw = dict(amplitude=a, h=h, ps=ps, pw=pw)
-    dm = _engine.states_input(x) if kind == "csr" else _engine.DeviceMatrix(dense=torch.from_numpy(dense).cuda())
+    dm = _engine.matrix_input(x, "test") if kind == "csr" else _engine.DeviceMatrix(dense=torch.from_numpy(dense).cuda())
     cs = np.asarray(bounds, dtype=np.int32)
     only, _, _ = _engine.posterior_chains(dm, cs, **kw)
     _same(only, neutral, "neutral alone")
@@ -134,7 +134,7 @@ def test_exp_cutoff_case_in_float32_equals_the_oracle(kind):
     _same(gain, c["gain"], kind + " gain")
     p = c["params"]
     h, ps, pw = po.scalars(p["sigma"], p["switch_prob"])
-    got = _engine.posterior_stats(_engine.states_input(x), chromosome_bounds(c["chr_pos"], c["x"].shape[1]),
+    got = _engine.posterior_stats(_engine.matrix_input(x, "test"), chromosome_bounds(c["chr_pos"], c["x"].shape[1]),
                                   amplitude=p["amplitude"], h=h, ps=ps, pw=pw)
     _same(got, fo.stats(c["x"], c["chr_pos"], p["amplitude"], p["sigma"], p["switch_prob"]), kind + " statistics")
 

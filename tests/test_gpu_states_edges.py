@@ -117,7 +117,7 @@ def test_chr_start_with_an_empty_chromosome_and_uncovered_windows(layout, kind):
     bounds = [0, 10, 10, 17, w] if layout == "empty_chromosome" else [3, 9, w - 2]
     want, want_fraction, _ = so.cnv_states(x, None, amplitude=a, sigma=sigma, bounds=bounds)
     h, stay, sw = so.scalars(sigma, 1e-3)
-    dm = _engine.states_input(x) if kind == "csr" else _engine.DeviceMatrix(dense=torch.from_numpy(x.toarray()).cuda())
+    dm = _engine.matrix_input(x, "test") if kind == "csr" else _engine.DeviceMatrix(dense=torch.from_numpy(x.toarray()).cuda())
     states, count = _engine.states_viterbi(dm, np.asarray(bounds, dtype=np.int32), amplitude=a, h=h, stay=stay, sw=sw)
     states, count = states.cpu().numpy(), count.cpu().numpy()
     assert states.tobytes() == want.tobytes()

@@ -215,9 +215,9 @@ def test_group_derivation():
     with pytest.raises(ValueError, match="no group of `clone` has min_cells=4 cells"):
         _groups(plain, 4)
     # the same lists as tl.cnv_segments' derivation gives the oracle
-    from infercnvpy_amd.tl._segments import _group_codes
+    from infercnvpy_amd.tl._groups import group_codes
 
-    codes, groups = _group_codes(_adata(n=6, labels=plain), "clone")
+    codes, groups = group_codes(_adata(n=6, labels=plain), "clone")
     rows, group_ptr = pb.lists(codes, len(groups))
     assert (rows.tolist(), group_ptr.tolist()) == _groups(plain)[3:]
     with pytest.raises(ValueError, match="has 6 labels for the 5 rows"):

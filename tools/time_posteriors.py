@@ -37,7 +37,7 @@ def main():
 
     x = synthetic_packed(a.cells, a.windows, a.density)
     nnz = x.nnz()
-    dm = _engine.states_input(x)
+    dm = _engine.matrix_input(x, "time_posteriors")
     bounds = chromosome_bounds(a.windows)
     n_chr = int(bounds.shape[0]) - 1
     q, flag = _engine.states_rowsq(dm)

@@ -86,8 +86,8 @@ def main():
     out = {"cells": n, "windows": w, "stored": nnz, "stored_fraction": nnz / (n * w), "hbm_copy_tb_per_s": hbm_tbs,
            "device": torch.cuda.get_device_name(0), "runs": []}
     rng = np.random.default_rng(1)
-    forms = {"csr_float64": (_engine.states_input(packed), 12 * nnz + 16 * n, packed),
-             "dense_float32": (_engine.states_input(dense32), 4 * n * w + 8 * n, dense32)}
+    forms = {"csr_float64": (_engine.matrix_input(packed, "time_pseudobulk"), 12 * nnz + 16 * n, packed),
+             "dense_float32": (_engine.matrix_input(dense32, "time_pseudobulk"), 4 * n * w + 8 * n, dense32)}
     for G in a.groups:
         codes = rng.integers(0, G, size=n)
         rows = torch.from_numpy(np.argsort(codes, kind="stable").astype(np.int64)).cuda()

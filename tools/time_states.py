@@ -47,7 +47,7 @@ def main():
 
     x = synthetic_packed(a.cells, a.windows, a.density)
     nnz = x.nnz()
-    dm = _engine.states_input(x)
+    dm = _engine.matrix_input(x, "time_states")
     bounds = chromosome_bounds(a.windows)
     q, flag = _engine.states_rowsq(dm)
     assert int(flag.item()) == 0
