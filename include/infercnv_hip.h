@@ -124,6 +124,11 @@ enum {
     ICV_KERNEL_SPLIT = 6    /* chromosome groups (row larger than LDS) + median on float64 windows in HBM */
 };
 int icv_plan_last_kernel(icv_plan_t plan, int32_t *h_kind);
+/* How many cells the last smoothing launch on this plan handed back to k_smooth (more than 64 windows in the bins of
+ * the two middle ranks; k_smooth_se: also cells with a stored NaN): the device-side counter of that launch, copied to
+ * the host.  0 where the last launch was of a kernel that hands nothing back (ICV_KERNEL_GENERIC, _SPLIT) or nothing
+ * was launched.  The caller has synchronised the stream of that call.  Diagnostics and tests. */
+int icv_plan_last_handed_back(icv_plan_t plan, int64_t *h_n);
 /* Host tables of the CSR stored-entries kernel (k_smooth_se), for tests that restate its arithmetic on the CPU:
  * *h_applies = 1 if the plan's geometry admits the kernel (else nothing more is written); per input column the
  * block of its gene (-1: masked) and the gene's offset inside the block; per block the offset of its first gene

@@ -166,6 +166,13 @@ class GenePlan:
         _lib.check(_lib.load().icv_plan_last_kernel(self._handle, C.byref(kind)))
         return int(kind.value)
 
+    def last_handed_back(self) -> int:
+        """How many cells the last smoothing launch on this plan handed back to the generic kernel (0 where that
+        launch was of a kernel that hands nothing back).  Synchronise the stream of that call first."""
+        n = C.c_int64(0)
+        _lib.check(_lib.load().icv_plan_last_handed_back(self._handle, C.byref(n)))
+        return int(n.value)
+
     def close(self):
         if getattr(self, "_handle", None) is not None and self._handle.value:
             _lib.load().icv_plan_destroy(self._handle)

@@ -1177,6 +1177,18 @@ int icv_plan_last_kernel(icv_plan_t pl, int32_t* kind) {
     return ICV_OK;
 }
 
+int icv_plan_last_handed_back(icv_plan_t pl, int64_t* n) {
+    if (!pl || !n) return fail(ICV_ERR_INVALID, "null argument");
+    *n = 0;
+    const int k = pl->last_kernel;
+    const bool hands_back = k == ICV_KERNEL_WS || k == ICV_KERNEL_WS_CSR || k == ICV_KERNEL_X16 || k == ICV_KERNEL_SD;
+    if (!hands_back || !pl->d_row_count) return ICV_OK;  // (k_smooth and the split path rank every cell themselves)
+    int count = 0;
+    HIP_TRY(hipMemcpy(&count, pl->d_row_count, sizeof(int), hipMemcpyDeviceToHost));
+    *n = count;
+    return ICV_OK;
+}
+
 int icv_plan_chr_pos(icv_plan_t pl, int32_t* h_chr_pos) {
     if (!pl || !h_chr_pos) return fail(ICV_ERR_INVALID, "null argument");
     std::memcpy(h_chr_pos, pl->p.chr_pos.data(), pl->p.chr_pos.size() * sizeof(int32_t));
