@@ -725,6 +725,26 @@ int icv_group_profiles(const icv_matrix *m, const int64_t *rows, int64_t n_liste
 int icv_group_profiles_finish(const int64_t *sum, const int32_t *stored, const int64_t *group_ptr, int64_t n_groups,
                               int32_t n_cols, int32_t shift, double *mean, double *fraction, void *stream);
 
+/* ---- tl.cnv_correlation and tl.cnv_signal: the rows of a matrix against centred profiles ------------------
+ * icv_profile_corr: m as for icv_states_viterbi (stored values are used as float64, an entry that is not stored is 0; CSR
+ * columns ascending; a column outside [0, n_cols) is passed over).  profiles_t (device float64, n_cols x n_profiles
+ * row-major: the n_profiles values of one window are contiguous) holds the centred profiles c_g = p_g - mean(p_g), s2
+ * (device float64, n_profiles) their sums of squares; both are the host's doubles.  Per row i, sequentially over the
+ * windows in ascending order and starting from +0.0: A += x, B += x x, D_g += x c_g[w], every product rounded before its
+ * add (float64, no fused multiply-add); a term with x == 0 adds nothing, so a CSR and a dense form of one matrix give the
+ * same bits.  a, b (device float64, n_rows) receive A and B, signal (the same shape) B / n_cols, and r (device float64,
+ * n_rows x n_profiles row-major) r_ig = D_ig / sqrt(vx_i s2_g) with vx_i = B_i - (A_i A_i) / n_cols, clipped to
+ * [-1, 1], NaN where vx_i <= 0 or s2_g == 0: each a correctly rounded operation, a pure function of the arguments.
+ * n_profiles = 0 is allowed (profiles_t, s2 and r may be null) and gives a, b and signal alone.  *flags (device int32)
+ * is set to 0; bit 0 is then set where a stored value is not finite.  n_cols has no limit and n_profiles none below
+ * 64 x 65535 (ICV_ERR_UNSUPPORTED beyond).  No synchronisation.
+ * icv_profile_corr_best: best_g[i] (device int32) = the lowest g with the largest r[i,g] that is no NaN and best_r[i]
+ * (device float64) that value; -1 and NaN when the whole row is NaN or n_profiles = 0. */
+int icv_profile_corr(const icv_matrix *m, const double *profiles_t, const double *s2, int64_t n_profiles, double *a,
+                     double *b, double *signal, double *r, int32_t *flags, void *stream);
+int icv_profile_corr_best(const double *r, int64_t n_rows, int64_t n_profiles, double *best_r, int32_t *best_g,
+                          void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -2083,3 +2083,43 @@ def group_profiles_finish(total, stored, d_ptr, shift):
         _lib.check(lib.icv_group_profiles_finish(_ptr(total), _ptr(stored), _ptr(d_ptr), g, w, int(shift), _ptr(mean),
                                                  _ptr(fraction), _stream_ptr(torch)))
     return mean, fraction
+
+
+# ---- tl.cnv_correlation / tl.cnv_signal: rows against centred profiles on the device (icv_profile_corr*) ------
+def profile_corr(dm: DeviceMatrix, centred=None, s2=None):
+    """(A, B, signal, r, flags): device float64 vectors of rule 2's row sums and of ``B / W``, the device float64 ``n x G``
+    correlations of rule 3 and the device int32 flags (bit 0: a non-finite stored value).  ``centred``: host float64
+    ``G x W`` centred profiles, ``s2``: host float64 ``G`` sums of squares; both None gives G = 0 and an ``n x 0`` r.
+    Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    n, w = int(dm.shape[0]), int(dm.shape[1])
+    with torch.cuda.device(dm.device):
+        if centred is None:
+            g, ct, d_s2 = 0, None, None
+        else:
+            centred = np.asarray(centred, dtype=np.float64)
+            g = int(centred.shape[0])
+            assert centred.shape == (g, w) and np.asarray(s2).shape == (g,)
+            ct = torch.from_numpy(np.ascontiguousarray(centred.T)).cuda()  # (W x G: a window's values are contiguous)
+            d_s2 = torch.from_numpy(np.ascontiguousarray(s2, dtype=np.float64)).cuda()
+        a, b, signal = (_empty(torch, n, torch.float64) for _ in range(3))
+        r = _empty(torch, n * g, torch.float64).reshape(n, g)
+        flags = torch.empty(1, dtype=torch.int32, device="cuda")
+        m = dm.c_struct()
+        _lib.check(lib.icv_profile_corr(C.byref(m), _ptr(ct) if g else None, _ptr(d_s2) if g else None, g, _ptr(a), _ptr(b),
+                                        _ptr(signal), _ptr(r) if g else None, _ptr(flags), _stream_ptr(torch)))
+    return a, b, signal, r, flags
+
+
+def profile_corr_best(r):
+    """(best_r float64 n, best_g int32 n), device tensors: rule 4 for the device ``n x G`` table of :func:`profile_corr`.
+    Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    assert r.is_cuda and r.dtype == torch.float64 and r.dim() == 2 and r.is_contiguous()
+    n, g = int(r.shape[0]), int(r.shape[1])
+    with torch.cuda.device(r.device):
+        best_r, best_g = _empty(torch, n, torch.float64), _empty(torch, n, torch.int32)
+        _lib.check(lib.icv_profile_corr_best(_ptr(r) if g else None, n, g, _ptr(best_r), _ptr(best_g), _stream_ptr(torch)))
+    return best_r, best_g

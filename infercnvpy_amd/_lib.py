@@ -51,6 +51,7 @@ EXPORTS = (
     "icv_posterior_chains", "icv_states_filter",
     "icv_posterior_stats",
     "icv_group_profiles", "icv_group_profiles_finish",
+    "icv_profile_corr", "icv_profile_corr_best",
 )
 
 
@@ -203,6 +204,8 @@ def load():
     lib.icv_posterior_stats.argtypes = [P(Matrix), vp, i32, dbl, dbl, dbl, dbl, vp, vp]
     lib.icv_group_profiles.argtypes = [P(Matrix), vp, i64, vp, i64, i32, vp, vp, vp, vp]
     lib.icv_group_profiles_finish.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
+    lib.icv_profile_corr.argtypes = [P(Matrix), vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.icv_profile_corr_best.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -48,6 +48,7 @@
 #include "icv_hmmfit.hpp"
 #include "icv_posterior.hpp"
 #include "icv_pseudobulk.hpp"
+#include "icv_profile_corr.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -4327,6 +4328,53 @@ int icv_group_profiles_finish(const int64_t* sum, const int32_t* stored, const i
         return fail(ICV_ERR_UNSUPPORTED, "group_profiles_finish: too many groups x windows for one call");
     hipLaunchKernelGGL(icv::k_group_profiles_finish, dim3((unsigned)((n_groups * (int64_t)n_cols + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), sum, stored, group_ptr, n_groups, n_cols, (int)shift, mean, fraction);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_correlation / tl.cnv_signal: the rows of X_cnv against centred profiles -------------------------
+int icv_profile_corr(const icv_matrix* m, const double* profiles_t, const double* s2, int64_t n_profiles, double* a, double* b,
+                     double* signal, double* r, int32_t* flags, void* stream) {
+    if (!matrix_header_ok(m) || n_profiles < 0 || (n_profiles > 0 && (!profiles_t || !s2 || !r)) || !a || !b || !signal ||
+        !flags || m->n_cols < 1 || (m->format == ICV_DENSE && m->ld < m->n_cols))
+        return fail(ICV_ERR_INVALID, "bad profile_corr arguments");
+    if (m->n_rows > 0 && !matrix_complete(m)) return fail(ICV_ERR_INVALID, "profile_corr: incomplete matrix");
+    const int gp = icv::pc_group_lanes(n_profiles);
+    const int64_t blocks = (m->n_rows + icv::kPcThreads / gp - 1) / (icv::kPcThreads / gp);
+    const int64_t tiles = std::max<int64_t>(1, (n_profiles + icv::kPcTileG - 1) / icv::kPcTileG);
+    if (blocks > kSegMaxBlocks || tiles > 65535)
+        return fail(ICV_ERR_UNSUPPORTED, "profile_corr: too many rows or profiles for one call");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int32_t), st));
+    if (m->n_rows == 0) return ICV_OK;
+    const dim3 grid((unsigned)blocks, (unsigned)tiles), block(icv::kPcThreads);
+    by_matrix(m, [&](auto t, auto csr) {
+        using T = decltype(t);
+        auto launch = [&](auto lanes) {
+            hipLaunchKernelGGL((icv::k_profile_corr<T, decltype(csr)::value, decltype(lanes)::value>), grid, block, 0, st,
+                               (const T*)m->values, m->indptr, m->indices, m->ld, m->n_rows, m->n_cols, profiles_t, s2,
+                               n_profiles, a, b, signal, r, flags);
+        };
+        switch (gp) {
+            case 1: launch(std::integral_constant<int, 1>{}); break;
+            case 8: launch(std::integral_constant<int, 8>{}); break;
+            case 16: launch(std::integral_constant<int, 16>{}); break;
+            case 32: launch(std::integral_constant<int, 32>{}); break;
+            default: launch(std::integral_constant<int, 64>{}); break;
+        }
+    });
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_profile_corr_best(const double* r, int64_t n_rows, int64_t n_profiles, double* best_r, int32_t* best_g, void* stream) {
+    if (n_rows < 0 || n_profiles < 0 || n_profiles > 0x7fffffffLL || (n_rows > 0 && (!best_r || !best_g)) ||
+        (n_rows > 0 && n_profiles > 0 && !r))
+        return fail(ICV_ERR_INVALID, "bad profile_corr_best arguments");
+    if (n_rows == 0) return ICV_OK;
+    if ((n_rows + 255) / 256 > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "profile_corr_best: too many rows for one call");
+    hipLaunchKernelGGL(icv::k_profile_corr_best, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), r, n_rows, n_profiles, best_r, best_g);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }

@@ -59,6 +59,20 @@ def _positive(name, value, who="tl.cnv_states"):
     return v
 
 
+def unit_fraction(who, name, value):
+    """``value`` as an exact ``fractions.Fraction`` (a float is taken at its binary value); ``ValueError`` unless it is a
+    number in (0, 1]."""
+    from fractions import Fraction
+
+    try:
+        f = Fraction(value) if isinstance(value, (int, str, Fraction)) else Fraction(float(value))
+    except (TypeError, ValueError, OverflowError, ZeroDivisionError):
+        raise ValueError(f"{who}: {name}={value!r} must be a number in (0, 1]") from None
+    if isinstance(value, bool) or not 0 < f <= 1:
+        raise ValueError(f"{who}: {name}={value!r} must lie in (0, 1]")
+    return f
+
+
 def at_least_one(who, name, value):
     """``value`` as an int; ``ValueError`` unless it is an integer >= 1."""
     try:

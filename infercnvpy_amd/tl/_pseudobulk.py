@@ -45,6 +45,25 @@ def group_lists(adata, groupby, n_rows, min_cells, key="X_cnv"):
     return groups[kept], n_cells, dropped, rows, group_ptr
 
 
+def mean_profiles(dm, x, rows, group_ptr, shift, who, key):
+    """(mean, fraction), device float64 ``G x W``: rules 3-5 for the listed rows of every group of ``dm``, the device form
+    of ``x``, on the current device.  One pair of scalars is read back: ``ValueError`` (prefixed ``who``, naming ``key``)
+    for a non-finite value and for a stored magnitude of 1024 or more."""
+    total, stored, flags, d_ptr = _engine.group_profiles(dm, rows, group_ptr, shift)
+    absmax = _engine.states_absmax(_engine.states_stored_values(dm))
+    mean, fraction = _engine.group_profiles_finish(total, stored, d_ptr, shift)
+    bits, m = _engine.flag_and_absmax(flags, absmax)
+    if bits & 1:
+        raise ValueError(f"{who}: {key} has non-finite values")
+    if not m < MAX_MAGNITUDE and isinstance(x, _engine.PackedCsr):
+        # (the m of a PackedCsr covers the unused tail of its buffers: look at the stored entries alone)
+        m = float(_engine.states_absmax(x.data[:x.nnz()]).item())
+    if not m < MAX_MAGNITUDE:
+        raise ValueError(f"{who}: {key} has a stored value of magnitude {m!r}; the exact sums take "
+                         f"magnitudes below {MAX_MAGNITUDE:g}: rescale the matrix or clip the value")
+    return mean, fraction
+
+
 def cnv_pseudobulk(adata, groupby="cnv_leiden", *, use_rep="cnv", min_cells=1, return_info=False):
     """One mean CNV profile per group of cells, as a new container that the HMM functions run on.
 
@@ -121,18 +140,7 @@ def cnv_pseudobulk(adata, groupby="cnv_leiden", *, use_rep="cnv", min_cells=1, r
     t0 = time.perf_counter()
     dm = _engine.matrix_input(x, "tl.cnv_pseudobulk")
     with torch.cuda.device(dm.device):
-        total, stored, flags, d_ptr = _engine.group_profiles(dm, rows, group_ptr, shift)
-        absmax = _engine.states_absmax(_engine.states_stored_values(dm))
-        mean, fraction = _engine.group_profiles_finish(total, stored, d_ptr, shift)
-        bits, m = _engine.flag_and_absmax(flags, absmax)
-        if bits & 1:
-            raise ValueError(f"tl.cnv_pseudobulk: {key} has non-finite values")
-        if not m < MAX_MAGNITUDE and isinstance(x, _engine.PackedCsr):
-            # (the m of a PackedCsr covers the unused tail of its buffers: look at the stored entries alone)
-            m = float(_engine.states_absmax(x.data[:x.nnz()]).item())
-        if not m < MAX_MAGNITUDE:
-            raise ValueError(f"tl.cnv_pseudobulk: {key} has a stored value of magnitude {m!r}; the exact sums take "
-                             f"magnitudes below {MAX_MAGNITUDE:g}: rescale the matrix or clip the value")
+        mean, fraction = mean_profiles(dm, x, rows, group_ptr, shift, "tl.cnv_pseudobulk", key)
         if not on_device:
             mean, fraction = mean.cpu().numpy(), fraction.cpu().numpy()
     stage_ms = {"profiles": (time.perf_counter() - t0) * 1e3}

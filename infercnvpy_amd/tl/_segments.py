@@ -9,23 +9,12 @@ from __future__ import annotations
 
 import math
 import time
-from fractions import Fraction
 
 import numpy as np
 
 from .. import _engine
 from ._groups import group_codes, group_table
-from ._hmm import at_least_one, call_matrix, chromosome_bounds
-
-
-def _min_fraction(value):
-    try:  # (a float is taken at its exact binary value)
-        f = Fraction(value) if isinstance(value, (int, str, Fraction)) else Fraction(float(value))
-    except (TypeError, ValueError, OverflowError, ZeroDivisionError):
-        raise ValueError(f"tl.cnv_segments: min_fraction={value!r} must be a number in (0, 1]") from None
-    if isinstance(value, bool) or not 0 < f <= 1:
-        raise ValueError(f"tl.cnv_segments: min_fraction={value!r} must lie in (0, 1]")
-    return f
+from ._hmm import at_least_one, call_matrix, chromosome_bounds, unit_fraction
 
 
 def _chromosome_names(chr_pos, starts):
@@ -91,7 +80,7 @@ def cnv_segments(adata, groupby=None, *, use_rep="cnv_states", cnv_key="cnv", ke
                              "`tl.cnv_states`? (it reads what `tl.infercnv` leaves there)")
     chr_pos = adata.uns[cnv_key]["chr_pos"]
     bounds = chromosome_bounds(chr_pos, w)
-    fraction = _min_fraction(min_fraction)
+    fraction = unit_fraction("tl.cnv_segments", "min_fraction", min_fraction)
     shortest = at_least_one("tl.cnv_segments", "min_windows", min_windows)
     params = {"groupby": groupby, "use_rep": use_rep, "min_fraction": float(fraction), "min_windows": shortest}
     if groupby is not None:
