@@ -190,15 +190,28 @@ struct icv_plan_s {
 
 namespace {
 
-// grid of k_smooth_se (workgroups per CU from its LDS map; ICV_WGS_PER_CU: developer knob for occupancy experiments) --
-// ONE definition for the launch and for the count of per-workgroup partial-moment slots the thresholds read (ADVICE r3:
-// the two used to be computed separately and agreed only while kSeLds gave exactly two workgroups per CU)
-int64_t se_grid(const icv_plan_t pl, int64_t n_rows) {
-    int per_cu = icv::kLdsLimit / icv::kSeLds;
-    if (const int v = knobs().wgs_per_cu)
-        if (v >= 1 && v < per_cu) per_cu = v;
-    int64_t grid = (int64_t)pl->n_cu * per_cu;
+// grid of a kernel whose workgroups take the rows in turns: per_cu workgroups on every CU, at most one per row
+int64_t cu_grid(const icv_plan_t pl, int per_cu, int64_t n_rows) {
+    const int64_t grid = (int64_t)pl->n_cu * per_cu;
     return grid > n_rows ? n_rows : grid;
+}
+
+// plan-owned, grow-only device buffer: at least `need` elements of `elem_bytes` behind ptr.  After an allocation that
+// failed the pointer is null and the capacity 0, so the next call allocates again.
+template <typename T>
+int grow(T*& ptr, int64_t& cap, int64_t need, size_t elem_bytes = sizeof(T)) {
+    if (cap >= need) return ICV_OK;
+    (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc((void**)&ptr, (size_t)need * elem_bytes));
+    cap = need;
+    return ICV_OK;
+}
+
+// thr == NULL: no threshold is applied and the chunk arguments are not looked at
+bool chunk_args_ok(const void* thr, int64_t chunksize, int64_t row_phase) {
+    return !thr || (chunksize >= 1 && row_phase >= 0 && row_phase < chunksize);
 }
 
 // one compute call at a time per plan (the plan owns the per-call workspace); released on scope exit
@@ -476,8 +489,24 @@ int fill_params(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const vo
     return ICV_OK;
 }
 
-int run_kernel(void (*kern)(const icv::KParams), int64_t grid, int lds, const icv::KParams& K, hipStream_t st,
-               int block = icv::NT) {
+typedef void (*SmoothKernel)(const icv::KParams);
+
+// Which smoothing kernel a call takes and how it is launched.  pick_route decides it, ONCE per call; run_route carries
+// it out, and the chunk thresholds take the count of partial-moment slots from it.
+struct SmoothRoute {
+    int kind = ICV_KERNEL_NONE;   // ICV_KERNEL_*
+    SmoothKernel kern = nullptr;  // (ICV_KERNEL_SPLIT: none -- the chromosome groups take the generic kernel in turn)
+    int64_t grid = 0;
+    int block = icv::NT, lds = 0;
+    int64_t moment_slots = 0;     // per-chunk partial-moment slots the launch writes (grid x wavefronts); 0: per-cell moments
+    bool writes_windows = false;  // the float64 windows (K.win_out) leave this launch
+    int k0 = 0, k1 = 0;           // k_smooth_se: fraction bits of its bins
+};
+
+int run_kernel(const SmoothRoute& r, const icv::KParams& K, hipStream_t st) {
+    const SmoothKernel kern = r.kern;
+    const int64_t grid = r.grid;
+    const int lds = r.lds, block = r.block;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     if (knobs().phase_profile) {
         // developer diagnostic: shader cycles per phase, summed over workgroups (thread 0 of each)
@@ -490,7 +519,7 @@ int run_kernel(void (*kern)(const icv::KParams), int64_t grid, int lds, const ic
         HIP_TRY(hipStreamSynchronize(st));
         unsigned long long h[32];
         HIP_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-        if (block == icv::XT) {  // k_smooth_x16 (-DICV_X_PROFILE): shader cycles per cell of wavefront 15
+        if (r.kind == ICV_KERNEL_X16) {  // k_smooth_x16 (-DICV_X_PROFILE): shader cycles per cell of wavefront 15
             (void)hipFree(d);
             std::fprintf(stderr, "[icv x16 profile] grid=%lld rows=%lld lds=%d cycles per cell: A: store %.0f, chains %.0f, S "
                                  "%.0f, barrier 1 %.0f, B: output+gather+clear %.0f, W %.0f, L %.0f, barrier 2 %.0f\n", (long long)grid,
@@ -501,7 +530,7 @@ int run_kernel(void (*kern)(const icv::KParams), int64_t grid, int lds, const ic
             return ICV_OK;
         }
         (void)hipFree(d);
-        if (lds == icv::kSeLds) {  // k_smooth_se (-DICV_SE_PROFILE=<thread>): work of phase 0..3, each followed by its barrier wait
+        if (r.kind == ICV_KERNEL_SD) {  // k_smooth_se (-DICV_SE_PROFILE=<thread>): work of phase 0..3, each followed by its barrier wait
             std::fprintf(stderr, "[icv se profile] grid=%lld rows=%lld cycles per cell of the profiled thread:", (long long)grid,
                          (long long)K.n_rows);
             const char* nm[8] = {"ph0", "A", "ph1", "B1", "ph2", "B2", "ph3", "B3"};
@@ -528,33 +557,12 @@ int run_kernel(void (*kern)(const icv::KParams), int64_t grid, int lds, const ic
     return ICV_OK;
 }
 
-// the geometry / input admits k_smooth_x16 (same routing as launch_smooth -> launch_smooth_fast)
-bool x16_applies(const icv_plan_t pl, const icv_matrix* m, const icv::KParams& K, const icv::Layout& lay) {
-    const icv::Plan& p = pl->p;
-    return lay.fits && m->dtype == ICV_F32 && m->format == ICV_DENSE && p.ws_ok && K.vec_ok && std::isfinite(K.cap) &&
-           !knobs().force_generic && p.x16_ok && !K.bounded && !knobs().no_x16 &&
-           p.step == 10 &&
-           ((p.B == 10 && p.window == 100 && p.x16_fine == 4096) || (p.B == 5 && p.window == 250 && p.x16_fine == 1024));
-}
-
 // plan-owned workspace of the kernels that hand cells back to the generic k_smooth: the list of those cells, its
 // counter (zeroed here) and the per-wavefront partial moments
 int hand_back_workspace(icv_plan_t pl, icv::KParams& K, hipStream_t st) {
-    if (pl->row_list_cap < K.n_rows) {
-        (void)hipFree(pl->d_row_list);
-        pl->d_row_list = nullptr;
-        pl->row_list_cap = 0;
-        HIP_TRY(hipMalloc((void**)&pl->d_row_list, (size_t)K.n_rows * sizeof(int64_t)));
-        pl->row_list_cap = K.n_rows;
-    }
-    if (pl->cell_part_cap < K.n_rows) {
-        (void)hipFree(pl->d_cell_part);
-        pl->d_cell_part = nullptr;
-        pl->cell_part_cap = 0;
-        // 16 wavefront partial pairs per cell (k_smooth_x16; k_smooth_ws / k_smooth_se use the first 8)
-        HIP_TRY(hipMalloc((void**)&pl->d_cell_part, (size_t)K.n_rows * 32 * sizeof(double)));
-        pl->cell_part_cap = K.n_rows;
-    }
+    if (int rc = grow(pl->d_row_list, pl->row_list_cap, K.n_rows)) return rc;
+    // 16 wavefront partial pairs per cell (k_smooth_x16; k_smooth_ws / k_smooth_se use the first 8)
+    if (int rc = grow(pl->d_cell_part, pl->cell_part_cap, K.n_rows, 32 * sizeof(double))) return rc;
     K.cell_part = pl->d_cell_part;
     if (!pl->d_row_count) HIP_TRY(hipMalloc((void**)&pl->d_row_count, sizeof(int)));
     HIP_TRY(hipMemsetAsync(pl->d_row_count, 0, sizeof(int), st));
@@ -577,9 +585,7 @@ int launch_hand_back(icv_plan_t pl, const icv::KParams& K, hipStream_t st, bool 
     else gk = need <= 4 ? icv::k_smooth<float, false, 4> : icv::k_smooth<float, false, 8>;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gk), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 p.lay32.total));
-    int64_t g2 = pl->n_cu;
-    if (g2 > K.n_rows) g2 = K.n_rows;
-    hipLaunchKernelGGL(gk, dim3((unsigned)g2), dim3(icv::NT), p.lay32.total, st, G);
+    hipLaunchKernelGGL(gk, dim3((unsigned)cu_grid(pl, 1, K.n_rows)), dim3(icv::NT), p.lay32.total, st, G);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -600,228 +606,264 @@ bool se_fraction_bits(const icv::Plan& p, double cap, int* k0, int* k1) {
     return true;
 }
 
-// the CSR float32 input takes the stored-entries kernel k_smooth_se (same test in launch_smooth and in the chunk-moment
-// set-up of icv_infercnv_run)
-bool stored_entries_kernel(const icv_plan_t pl, const icv_matrix* m, const icv::KParams& K, const icv::Layout& lay) {
-    if (!(lay.fits && m->dtype == ICV_F32 && m->format == ICV_CSR && std::isfinite(K.cap) &&
-          m->csr_end > m->csr_begin && !knobs().force_generic))
-        return false;
-    int k0 = 0, k1 = 0;
-    return se_fraction_bits(pl->p, K.cap, &k0, &k1);
+// ---- the kernel instantiations of a plan's geometry (no decisions here: pick_route asks for them) ---------------------
+// k_smooth_ws: float32 in block form, the row in LDS (dense, or rebuilt from the prepared CSR entries)
+SmoothKernel ws_kernel(const icv::Plan& p, bool csr) {
+    constexpr int U = icv::kFastUMax;
+    const int need_b = (p.NB + icv::kThreads - 1) / icv::kThreads;
+    const bool u10 = (p.B == 10 && p.window == 100);
+    if (csr) {
+        if (need_b <= 4) return u10 ? icv::k_smooth_ws<U, 4, 4, 10, 10, true> : icv::k_smooth_ws<U, 4, 4, 0, 0, true>;
+        return (p.B == 5) ? icv::k_smooth_ws<U, 8, 4, 5, 0, true> : icv::k_smooth_ws<U, 8, 4, 0, 0, true>;
+    }
+    if (need_b <= 4) return u10 ? icv::k_smooth_ws<U, 4, 4, 10, 10, false> : icv::k_smooth_ws<U, 4, 4, 0, 0, false>;
+    if (p.B == 5 && p.window == 250) return icv::k_smooth_ws<U, 8, 4, 5, 50, false>;
+    return (p.B == 5) ? icv::k_smooth_ws<U, 8, 4, 5, 0, false> : icv::k_smooth_ws<U, 8, 4, 0, 0, false>;
 }
 
-// k_smooth_se (icv_kernel_se.hpp): CSR float32 input in block form, stored entries only
-int launch_smooth_se(icv_plan_t pl, icv::KParams K, hipStream_t st, hipEvent_t kernel_done = nullptr,
-                     int64_t csr_entries = 0, int row_len_hint = 0) {
-    const icv::Plan& p = pl->p;
-    int k0 = 0, k1 = 0;
-    if (!se_fraction_bits(p, K.cap, &k0, &k1)) return fail(ICV_ERR_INVALID, "k_smooth_se does not apply");
-    AsyncBuf tab_guard, hi_guard, wt_guard, g_guard;  // per-column, per-window, per-block tables: released on every exit path
-    const int nz = (int)pl->zrow_elems;
-    hipLaunchKernelGGL(icv::k_zero_row<float>, dim3((nz + 255) / 256), dim3(256), 0, st, K,
-                       static_cast<float*>(pl->d_zrow), nz);
-    HIP_TRY(tab_guard.alloc((size_t)K.n_cols * 16, st));
-    HIP_TRY(wt_guard.alloc((size_t)p.W * 16, st));
-    HIP_TRY(g_guard.alloc((size_t)(p.NB + 8) * 8, st));
-    if (K.bounded) HIP_TRY(hi_guard.alloc((size_t)K.n_cols * 4, st));
-    K.sd_tab = tab_guard.p;
-    K.sd_tab_hi = K.bounded ? hi_guard.as<float>() : nullptr;
-    K.sd_wtab = wt_guard.p;
-    K.sd_g16 = g_guard.as<double>();
-    K.sd_scale = std::ldexp(1.0, k0);
-    K.sd_qinv = std::ldexp(1.0, -k0);
-    K.sd_q1inv = std::ldexp(1.0, -k1);
-    K.sd_r = std::ldexp(1.0, k1 - k0);
-    K.sd_window = p.window;
-    hipLaunchKernelGGL(icv::k_se_table, dim3((unsigned)((K.n_cols + 255) / 256)), dim3(256), 0, st, K,
-                       tab_guard.as<icv::u32x4>(), const_cast<float*>(K.sd_tab_hi), (float)std::ldexp(1.0, k1));
-    const int n_wt = p.W > p.NB + 8 ? p.W : p.NB + 8;
-    hipLaunchKernelGGL(icv::k_se_wtab, dim3((unsigned)((n_wt + 255) / 256)), dim3(256), 0, st, K,
-                       static_cast<const float*>(pl->d_zrow), pl->d_se_w0, pl->d_se_w1, wt_guard.as<icv::u32x4>(),
-                       g_guard.as<double>(), K.sd_r);
-    if (int rc = hand_back_workspace(pl, K, st)) return rc;
-    int64_t grid = se_grid(pl, K.n_rows);
-    if (grid < 1) {
-        if (kernel_done) HIP_TRY(hipEventRecord(kernel_done, st));
-        return ICV_OK;
-    }
-    void (*kern)(const icv::KParams);
-    // window registers per thread: 3 where the windows fit (<= 1 536: window 250 / step 10 at 20 000 genes has 1 472), else
-    // 4; entry slots per thread from the mean row length: PF x 512 slots should hold mean + 4 sigma (binomial) entries --
-    // longer rows take the in-phase loop, any PF gives the same bits
+// k_smooth_x16: window 100 / step 10 or window 250 / step 10 (the instantiations assume step 10: blocks between adjacent
+// windows); null for every other geometry.  `win`: the float64 windows leave the kernel as well (chunk-moment mode only)
+SmoothKernel x16_kernel(const icv::Plan& p, bool chunk, bool win) {
+    if (!p.x16_ok || p.step != 10) return nullptr;
+    if (p.B == 10 && p.window == 100 && p.x16_fine == 4096)
+        return win ? icv::k_smooth_x16<10, 10, 1, true, 4096, true, true>
+                   : (chunk ? icv::k_smooth_x16<10, 10, 1, true, 4096, true> : icv::k_smooth_x16<10, 10, 1, false, 4096, true>);
+    if (p.B == 5 && p.window == 250 && p.x16_fine == 1024)
+        return win ? icv::k_smooth_x16<5, 50, 2, true, 1024, false, true>
+                   : (chunk ? icv::k_smooth_x16<5, 50, 2, true, 1024, false> : icv::k_smooth_x16<5, 50, 2, false, 1024, false>);
+    return nullptr;
+}
+
+// k_smooth_se.  Window registers per thread: 3 where the windows fit (<= 1 536: window 250 / step 10 at 20 000 genes has
+// 1 472), else 4; entry slots per thread from the mean row length: PF x 512 slots should hold mean + 4 sigma (binomial)
+// entries -- longer rows take the in-phase loop, any PF gives the same bits
+SmoothKernel se_kernel(const icv::Plan& p, const icv_matrix* m, bool bounded, bool chunk, bool win) {
     const bool w3 = p.W <= 3 * icv::NT && !knobs().se_maxw4;
+    if (win) {
+        // calculate_gene_values: the float64 windows leave the kernel as well (four entry slots per thread whatever
+        // the row length: any slot count gives the same bits, and this path is bound by the cells x genes output)
+        if (w3) return bounded ? icv::k_smooth_se<3, true, true, 4, true> : icv::k_smooth_se<3, true, false, 4, true>;
+        return bounded ? icv::k_smooth_se<4, true, true, 4, true> : icv::k_smooth_se<4, true, false, 4, true>;
+    }
+    if (!chunk) {
+        if (w3) return bounded ? icv::k_smooth_se<3, false, true> : icv::k_smooth_se<3, false, false>;
+        return bounded ? icv::k_smooth_se<4, false, true> : icv::k_smooth_se<4, false, false>;
+    }
     int pf = 4;
-    if (K.chunk_part && !knobs().se_maxw4 && K.n_rows > 0) {
+    if (!knobs().se_maxw4 && m->n_rows > 0) {
         double want = 0.0;
-        if (row_len_hint > 0) {
-            want = (double)row_len_hint;  // the caller's figure: the length most rows stay under (icv_matrix._pad)
-        } else if (csr_entries > 0) {     // none: mean + 3.5 sigma of a binomial row length
-            const double mean = (double)csr_entries / (double)K.n_rows;
-            const double dens = mean / (double)(K.n_cols > 0 ? K.n_cols : 1);
+        if (m->_pad > 0) {
+            want = (double)m->_pad;  // the caller's figure: the length most rows stay under (icv_matrix._pad)
+        } else if (m->csr_end > m->csr_begin) {  // none: mean + 3.5 sigma of a binomial row length
+            const double mean = (double)(m->csr_end - m->csr_begin) / (double)m->n_rows;
+            const double dens = mean / (double)(m->n_cols > 0 ? m->n_cols : 1);
             want = mean + 3.5 * std::sqrt(mean * (dens < 1.0 ? 1.0 - dens : 0.0)) + 8.0;
         }
         if (want > 0.0) pf = want <= icv::NT ? 1 : want <= 2 * icv::NT ? 2 : want <= 3 * icv::NT ? 3 : 4;
     }
-#define ICV_SE_PICK(MW, CH, BD)                                                                              \
-    (pf == 1 ? icv::k_smooth_se<MW, CH, BD, 1> : pf == 2 ? icv::k_smooth_se<MW, CH, BD, 2>                   \
-     : pf == 3 ? icv::k_smooth_se<MW, CH, BD, 3> : icv::k_smooth_se<MW, CH, BD, 4>)
-    if (K.win_out) {
-        // calculate_gene_values: the float64 windows leave the kernel as well (four entry slots per thread whatever
-        // the row length: any slot count gives the same bits, and this path is bound by the cells x genes output)
-        if (!K.chunk_part) return fail(ICV_ERR_INVALID, "k_smooth_se with windows needs the chunk-moment mode");
-        if (w3) kern = K.bounded ? icv::k_smooth_se<3, true, true, 4, true> : icv::k_smooth_se<3, true, false, 4, true>;
-        else kern = K.bounded ? icv::k_smooth_se<4, true, true, 4, true> : icv::k_smooth_se<4, true, false, 4, true>;
-    } else if (K.chunk_part) {
-        if (w3) kern = K.bounded ? ICV_SE_PICK(3, true, true) : ICV_SE_PICK(3, true, false);
-        else kern = K.bounded ? ICV_SE_PICK(4, true, true) : ICV_SE_PICK(4, true, false);
-    } else {
-        if (w3) kern = K.bounded ? icv::k_smooth_se<3, false, true> : icv::k_smooth_se<3, false, false>;
-        else kern = K.bounded ? icv::k_smooth_se<4, false, true> : icv::k_smooth_se<4, false, false>;
-    }
+#define ICV_SE_PICK(MW, BD)                                                                              \
+    (pf == 1 ? icv::k_smooth_se<MW, true, BD, 1> : pf == 2 ? icv::k_smooth_se<MW, true, BD, 2>           \
+     : pf == 3 ? icv::k_smooth_se<MW, true, BD, 3> : icv::k_smooth_se<MW, true, BD, 4>)
+    if (w3) return bounded ? ICV_SE_PICK(3, true) : ICV_SE_PICK(3, false);
+    return bounded ? ICV_SE_PICK(4, true) : ICV_SE_PICK(4, false);
 #undef ICV_SE_PICK
-    int rc = run_kernel(kern, grid, icv::kSeLds, K, st);
-    if (kernel_done && !rc) HIP_TRY(hipEventRecord(kernel_done, st));
-    if (rc) return rc;
-    if (!K.chunk_part)
-        hipLaunchKernelGGL(icv::k_stats_finish, dim3((unsigned)((K.n_rows + 255) / 256)), dim3(256), 0, st, K.cell_part,
-                           K.n_rows, K.cell_stats);
-    pl->last_kernel = ICV_KERNEL_SD;
-    return launch_hand_back(pl, K, st, true);
 }
 
-// float32, blocked form, small enough geometry: register-prefetch kernels (dense or prepared CSR)
-// kernel_done (optional): recorded right after the smoothing kernel itself, before the moment finish / hand-back
-// launches, so that profiling reports the dominant kernel's own duration
-int launch_smooth_fast(icv_plan_t pl, icv::KParams K, hipStream_t st, bool csr, int64_t csr_begin, int64_t csr_end,
-                       hipEvent_t kernel_done = nullptr) {
-    const icv::Plan& p = pl->p;
-    const int need_b = (p.NB + icv::kThreads - 1) / icv::kThreads;
-    void (*kern)(const icv::KParams) = nullptr;
-    constexpr int U = icv::kFastUMax;
-    K.scratch_off = p.fast_scratch_off;
-    AsyncBuf ws_guard;  // prepared CSR entries: released on every exit path
-    void* ws_buf = nullptr;
-    const int lds = p.fast_lds;
-    if (!p.ws_ok) return -1;  // caller falls back to the generic kernel
-    {
-        const bool u10 = (p.B == 10 && p.window == 100);
-        if (!csr) {
-            if (need_b <= 4) kern = u10 ? icv::k_smooth_ws<U, 4, 4, 10, 10, false> : icv::k_smooth_ws<U, 4, 4, 0, 0, false>;
-            else if (p.B == 5 && p.window == 250) kern = icv::k_smooth_ws<U, 8, 4, 5, 50, false>;
-            else kern = (p.B == 5) ? icv::k_smooth_ws<U, 8, 4, 5, 0, false> : icv::k_smooth_ws<U, 8, 4, 0, 0, false>;
-        } else {
-            const int nz = (int)pl->zrow_elems;
-            hipLaunchKernelGGL(icv::k_zero_row<float>, dim3((nz + 255) / 256), dim3(256), 0, st, K,
-                               static_cast<float*>(pl->d_zrow), nz);
-            const int64_t n = csr_end - csr_begin;
-            int64_t g = (n + 255) / 256;
-            if (g > 8192) g = 8192;
-            if (need_b <= 4) kern = u10 ? icv::k_smooth_ws<U, 4, 4, 10, 10, true> : icv::k_smooth_ws<U, 4, 4, 0, 0, true>;
-            else kern = (p.B == 5) ? icv::k_smooth_ws<U, 8, 4, 5, 0, true> : icv::k_smooth_ws<U, 8, 4, 0, 0, true>;
-            // prepared entries {LDS position, centred and clipped value} on top of the zero row
-            HIP_TRY(ws_guard.alloc((size_t)(n > 0 ? n : 1) * 6, st));
-            ws_buf = ws_guard.p;
-            float* cv = static_cast<float*>(ws_buf);
-            uint16_t* ps = reinterpret_cast<uint16_t*>(cv + (n > 0 ? n : 1));
-            K.cvals = cv - csr_begin;  // indexed by the absolute entry number
-            K.pos16 = ps - csr_begin;
-            if (n > 0)
-                hipLaunchKernelGGL(icv::k_csr_prepare, dim3((unsigned)g), dim3(256), 0, st, K, csr_begin, csr_end,
-                                   const_cast<uint16_t*>(K.pos16), const_cast<float*>(K.cvals));
-        }
-        K.hist_off = p.ws_hist_off;
-        if (int rc = hand_back_workspace(pl, K, st)) return rc;
-    }
-    int per_cu = icv::kLdsLimit / lds;
-    if (per_cu > 4) per_cu = 4;
-    if (const int v = knobs().wgs_per_cu)  // developer knob: occupancy experiments
-        if (v >= 1 && v < per_cu) per_cu = v;
-    int64_t grid = (int64_t)pl->n_cu * per_cu;
-    if (grid > K.n_rows) grid = K.n_rows;
-    if (grid < 1) {
-        if (kernel_done) HIP_TRY(hipEventRecord(kernel_done, st));
-        return ICV_OK;
-    }
-    int rc;
-    // dense float32, one reference row, window 100 / step 10 or window 250 / step 10 geometry: the 16-wavefront
-    // kernel, one 1024-thread workgroup per CU (ICV_NO_X16=1: developer knob, previous generation)
-    void (*xk)(const icv::KParams) = nullptr;
-    if (!csr && p.x16_ok && !K.bounded && !knobs().no_x16) {
-        if (p.step != 10)
-            xk = nullptr;  // the instantiations below assume step 10 (blocks between adjacent windows)
-        else if (p.B == 10 && p.window == 100 && p.x16_fine == 4096)
-            xk = K.win_out ? icv::k_smooth_x16<10, 10, 1, true, 4096, true, true>
-                           : (K.chunk_part ? icv::k_smooth_x16<10, 10, 1, true, 4096, true>
-                                           : icv::k_smooth_x16<10, 10, 1, false, 4096, true>);
-        else if (p.B == 5 && p.window == 250 && p.x16_fine == 1024)
-            xk = K.win_out ? icv::k_smooth_x16<5, 50, 2, true, 1024, false, true>
-                           : (K.chunk_part ? icv::k_smooth_x16<5, 50, 2, true, 1024, false>
-                                           : icv::k_smooth_x16<5, 50, 2, false, 1024, false>);
-    }
-    // float64 windows requested (calculate_gene_values): only the x16 instantiations write them, in chunk-moment mode;
-    // every other geometry takes the generic kernel (ONE smoothing pass either way)
-    if (K.win_out && (!xk || !K.chunk_part)) return -1;
-    if (xk) {
-        icv::KParams X = K;
-        X.win_off = p.x16_s01_off;
-        X.hist_off = p.x16_hist_off;
-        X.scratch_off = p.x16_scratch_off;
-        int64_t gx = pl->n_cu;
-        if (gx > K.n_rows) gx = K.n_rows;
-        rc = run_kernel(xk, gx, p.x16_lds, X, st, icv::XT);
-        if (kernel_done && !rc) HIP_TRY(hipEventRecord(kernel_done, st));
-        if (rc) return rc;
-        if (!K.chunk_part)
-            hipLaunchKernelGGL(icv::k_stats_finish_n, dim3((unsigned)((K.n_rows + 255) / 256)), dim3(256), 0, st,
-                               K.cell_part, K.n_rows, icv::XWAVE, K.cell_stats);
-    } else {
-        rc = run_kernel(kern, grid, lds, K, st);
-        if (kernel_done && !rc) HIP_TRY(hipEventRecord(kernel_done, st));
-        if (rc) return rc;
-        // per-wavefront partial moments -> cell_stats (cells handed back are overwritten by k_smooth below)
-        hipLaunchKernelGGL(icv::k_stats_finish, dim3((unsigned)((K.n_rows + 255) / 256)), dim3(256), 0, st,
-                           K.cell_part, K.n_rows, K.cell_stats);
-    }
-    pl->last_kernel = xk ? ICV_KERNEL_X16 : (csr ? ICV_KERNEL_WS_CSR : ICV_KERNEL_WS);
-    return launch_hand_back(pl, K, st, csr);
-}
-
+// the generic k_smooth on `lay` (the plan's own layout, or a chromosome group's): any dtype / format that fits LDS
 template <typename T, bool CSR>
-int launch_smooth_t(icv_plan_t pl, const icv::KParams& K, const icv::Layout& lay, hipStream_t st) {
+SmoothRoute generic_route(const icv_plan_t pl, const icv::Layout& lay, int64_t n_rows) {
     const icv::Plan& p = pl->p;
-    int maxb = 0;
-    if (p.B > 1) {
-        const int need = (p.NB + icv::kThreads - 1) / icv::kThreads;
-        maxb = need <= 4 ? 4 : 8;
-    }
-    void (*kern)(const icv::KParams) = nullptr;
-    if (maxb == 0) kern = icv::k_smooth<T, CSR, 0>;
-    else if (maxb == 4) kern = icv::k_smooth<T, CSR, 4>;
-    else kern = icv::k_smooth<T, CSR, 8>;
+    SmoothRoute r;
+    r.kind = ICV_KERNEL_GENERIC;
+    const int need = (p.NB + icv::kThreads - 1) / icv::kThreads;
+    r.kern = p.B <= 1 ? icv::k_smooth<T, CSR, 0> : (need <= 4 ? icv::k_smooth<T, CSR, 4> : icv::k_smooth<T, CSR, 8>);
     int per_cu = icv::kLdsLimit / lay.total;
-    if (per_cu > 4) per_cu = 4;  // 32 wavefronts per CU / 8 per workgroup
-    if (per_cu < 1) per_cu = 1;
-    int64_t grid = (int64_t)pl->n_cu * per_cu;
-    if (grid > K.n_rows) grid = K.n_rows;
-    if (grid < 1) return ICV_OK;
-    if constexpr (CSR) {
-        const int n = (int)pl->zrow_elems;
-        hipLaunchKernelGGL(icv::k_zero_row<T>, dim3((n + 255) / 256), dim3(256), 0, st, K,
-                           static_cast<T*>(pl->d_zrow), n);
+    per_cu = per_cu > 4 ? 4 : (per_cu < 1 ? 1 : per_cu);  // 32 wavefronts per CU / 8 per workgroup
+    r.grid = cu_grid(pl, per_cu, n_rows);
+    r.lds = lay.total;
+    r.writes_windows = true;
+    return r;
+}
+
+// THE statement of which smoothing kernel a call takes, in the order of preference.  K: the call's parameters
+// (fill_params; K.win_out set where the caller wants the float64 windows); want_chunk_moments: the caller asks for no
+// per-cell moments, so a kernel that can forms them per chunk (moment_slots > 0 then: the caller owes it K.chunk_part).
+//   1. a row that does not fit LDS: chromosome groups (smooth_split)
+//   2. dense float32 in block form, 16-byte aligned: k_smooth_x16 where the geometry has an instantiation and there is
+//      one reference row, else k_smooth_ws
+//   3. CSR float32 with stored entries: k_smooth_se where its bins keep 40 fraction bits, else k_smooth_ws on prepared entries
+//   4. everything else, float32 with an infinite clip value and the developer knob ICV_FORCE_GENERIC: k_smooth
+// The float64 windows are written by k_smooth_x16 and k_smooth_se in chunk-moment mode only and never by k_smooth_ws:
+// a call that wants them and cannot have them there takes k_smooth (ONE smoothing pass either way).
+SmoothRoute pick_route(const icv_plan_t pl, const icv_matrix* m, const icv::KParams& K, const icv::Layout& lay,
+                       bool want_chunk_moments) {
+    const icv::Plan& p = pl->p;
+    const Knobs& kn = knobs();
+    SmoothRoute r;
+    if (!lay.fits) {
+        r.kind = ICV_KERNEL_SPLIT;
+        r.writes_windows = true;
+        return r;
     }
-    if (lay.win_global) {
-        const int64_t need = grid * (int64_t)p.W;
-        if (pl->win_scratch_cap < need) {
-            (void)hipFree(pl->d_win_scratch);
-            pl->d_win_scratch = nullptr;
-            HIP_TRY(hipMalloc((void**)&pl->d_win_scratch, (size_t)need * sizeof(double)));
-            pl->win_scratch_cap = need;
+    const bool want_win = K.win_out != nullptr, csr = m->format == ICV_CSR;
+    const bool fast_allowed = m->dtype == ICV_F32 && std::isfinite(K.cap) && !kn.force_generic;
+    const bool win_ok = !want_win || want_chunk_moments;  // the x16 / se instantiations that write windows form chunk moments
+    // ICV_WGS_PER_CU: developer knob for occupancy experiments
+    auto knob_per_cu = [&](int per_cu) { return kn.wgs_per_cu >= 1 && kn.wgs_per_cu < per_cu ? kn.wgs_per_cu : per_cu; };
+    if (fast_allowed && !csr && p.ws_ok && K.vec_ok) {
+        // ICV_NO_X16=1: developer knob, the previous generation
+        const SmoothKernel xk = (K.bounded || kn.no_x16) ? nullptr : x16_kernel(p, want_chunk_moments, want_win);
+        if (xk && win_ok) {  // 16 wavefronts per cell, one 1024-thread workgroup per CU
+            r.kind = ICV_KERNEL_X16;
+            r.kern = xk;
+            r.grid = cu_grid(pl, 1, K.n_rows);
+            r.block = icv::XT;
+            r.lds = p.x16_lds;
+            r.moment_slots = want_chunk_moments ? r.grid * icv::XWAVE : 0;
+            r.writes_windows = want_win;
+            return r;
         }
-        icv::KParams K2 = K;
-        K2.win_scratch = pl->d_win_scratch;
-        return run_kernel(kern, grid, lay.total, K2, st);
+        if (!want_win) {
+            r.kind = ICV_KERNEL_WS;
+            r.kern = ws_kernel(p, false);
+            r.lds = p.fast_lds;
+            r.grid = cu_grid(pl, knob_per_cu(std::min(icv::kLdsLimit / r.lds, 4)), K.n_rows);
+            return r;
+        }
     }
-    return run_kernel(kern, grid, lay.total, K, st);
+    if (fast_allowed && csr && m->csr_end > m->csr_begin) {
+        if (se_fraction_bits(p, K.cap, &r.k0, &r.k1) && win_ok) {
+            r.kind = ICV_KERNEL_SD;
+            r.kern = se_kernel(p, m, K.bounded != 0, want_chunk_moments, want_win);
+            r.lds = icv::kSeLds;
+            r.grid = cu_grid(pl, knob_per_cu(icv::kLdsLimit / icv::kSeLds), K.n_rows);  // workgroups per CU from its LDS map
+            r.moment_slots = want_chunk_moments ? r.grid * icv::NWAVE : 0;
+            r.writes_windows = want_win;
+            return r;
+        }
+        if (p.ws_ok && aligned16(K.ref_lo) && !want_win) {
+            r.kind = ICV_KERNEL_WS_CSR;
+            r.kern = ws_kernel(p, true);
+            r.lds = p.fast_lds;
+            r.grid = cu_grid(pl, knob_per_cu(std::min(icv::kLdsLimit / r.lds, 4)), K.n_rows);
+            return r;
+        }
+    }
+    return by_matrix(m, [&](auto t, auto is_csr) {
+        return generic_route<decltype(t), decltype(is_csr)::value>(pl, lay, K.n_rows);
+    });
+}
+
+template <typename T>
+void zero_row(icv_plan_t pl, const icv::KParams& K, hipStream_t st) {
+    const int n = (int)pl->zrow_elems;
+    hipLaunchKernelGGL(icv::k_zero_row<T>, dim3((n + 255) / 256), dim3(256), 0, st, K, static_cast<T*>(pl->d_zrow), n);
+}
+
+// ---- what a route's kernel needs before it starts (tmp: stream-ordered tables, released when the route has been issued)
+// k_smooth_se (icv_kernel_se.hpp): the zero row, the per-column, per-window and per-block tables, the hand-back workspace
+int prepare_se(icv_plan_t pl, const SmoothRoute& r, icv::KParams& K, hipStream_t st, AsyncBuf* tmp) {
+    const icv::Plan& p = pl->p;
+    AsyncBuf &tab = tmp[0], &hi = tmp[1], &wt = tmp[2], &g = tmp[3];
+    zero_row<float>(pl, K, st);
+    HIP_TRY(tab.alloc((size_t)K.n_cols * 16, st));
+    HIP_TRY(wt.alloc((size_t)p.W * 16, st));
+    HIP_TRY(g.alloc((size_t)(p.NB + 8) * 8, st));
+    if (K.bounded) HIP_TRY(hi.alloc((size_t)K.n_cols * 4, st));
+    K.sd_tab = tab.p;
+    K.sd_tab_hi = K.bounded ? hi.as<float>() : nullptr;
+    K.sd_wtab = wt.p;
+    K.sd_g16 = g.as<double>();
+    K.sd_scale = std::ldexp(1.0, r.k0);
+    K.sd_qinv = std::ldexp(1.0, -r.k0);
+    K.sd_q1inv = std::ldexp(1.0, -r.k1);
+    K.sd_r = std::ldexp(1.0, r.k1 - r.k0);
+    K.sd_window = p.window;
+    hipLaunchKernelGGL(icv::k_se_table, dim3((unsigned)((K.n_cols + 255) / 256)), dim3(256), 0, st, K,
+                       tab.as<icv::u32x4>(), const_cast<float*>(K.sd_tab_hi), (float)std::ldexp(1.0, r.k1));
+    const int n_wt = p.W > p.NB + 8 ? p.W : p.NB + 8;
+    hipLaunchKernelGGL(icv::k_se_wtab, dim3((unsigned)((n_wt + 255) / 256)), dim3(256), 0, st, K,
+                       static_cast<const float*>(pl->d_zrow), pl->d_se_w0, pl->d_se_w1, wt.as<icv::u32x4>(),
+                       g.as<double>(), K.sd_r);
+    return hand_back_workspace(pl, K, st);
+}
+
+// k_smooth_ws / k_smooth_x16: the hand-back workspace; CSR input: the zero row and, on top of it, the prepared entries
+// {LDS position, centred and clipped value} (k_csr_prepare)
+int prepare_fast(icv_plan_t pl, const icv_matrix* m, icv::KParams& K, hipStream_t st, AsyncBuf* tmp) {
+    const icv::Plan& p = pl->p;
+    K.scratch_off = p.fast_scratch_off;
+    if (m->format == ICV_CSR) {
+        zero_row<float>(pl, K, st);
+        const int64_t n = m->csr_end - m->csr_begin;
+        int64_t g = (n + 255) / 256;
+        if (g > 8192) g = 8192;
+        HIP_TRY(tmp[0].alloc((size_t)(n > 0 ? n : 1) * 6, st));
+        float* cv = tmp[0].as<float>();
+        uint16_t* ps = reinterpret_cast<uint16_t*>(cv + (n > 0 ? n : 1));
+        K.cvals = cv - m->csr_begin;  // indexed by the absolute entry number
+        K.pos16 = ps - m->csr_begin;
+        if (n > 0)
+            hipLaunchKernelGGL(icv::k_csr_prepare, dim3((unsigned)g), dim3(256), 0, st, K, m->csr_begin, m->csr_end,
+                               const_cast<uint16_t*>(K.pos16), const_cast<float*>(K.cvals));
+    }
+    K.hist_off = p.ws_hist_off;
+    return hand_back_workspace(pl, K, st);
+}
+
+// k_smooth: the zero row of a CSR input; Layout::win_global: the per-workgroup window lines in HBM
+int prepare_generic(icv_plan_t pl, const SmoothRoute& r, const icv_matrix* m, icv::KParams& K, const icv::Layout& lay,
+                    hipStream_t st) {
+    if (m->format == ICV_CSR) by_dtype(m->dtype, [&](auto t) { zero_row<decltype(t)>(pl, K, st); });
+    if (lay.win_global) {
+        if (int rc = grow(pl->d_win_scratch, pl->win_scratch_cap, r.grid * (int64_t)pl->p.W)) return rc;
+        K.win_scratch = pl->d_win_scratch;
+    }
+    return ICV_OK;
+}
+
+int smooth_split(icv_plan_t pl, const icv_matrix* m, const icv::KParams& K, hipStream_t st);
+
+// Carry a route out: the set-up of its kind, THE launch, the moment finish and the hand-back of the kernels that have
+// them.  kernel_done (optional) is recorded right after the smoothing kernel itself, before those later launches, so
+// that profiling reports the dominant kernel's own duration.  A call without rows launches nothing.
+int run_route(icv_plan_t pl, const SmoothRoute& r, const icv_matrix* m, icv::KParams K, const icv::Layout& lay,
+              hipStream_t st, hipEvent_t kernel_done = nullptr) {
+    const icv::Plan& p = pl->p;
+    if ((K.win_out && !r.writes_windows) || ((K.chunk_part != nullptr) != (r.moment_slots > 0)))
+        return fail(ICV_ERR_INVALID, "the smoothing route and the call's parameters disagree");
+    const bool hands_back = r.kind == ICV_KERNEL_WS || r.kind == ICV_KERNEL_WS_CSR || r.kind == ICV_KERNEL_X16 ||
+                            r.kind == ICV_KERNEL_SD;
+    AsyncBuf tmp[4];
+    int rc = ICV_OK;
+    if (r.kind == ICV_KERNEL_SPLIT) {
+        if ((rc = smooth_split(pl, m, K, st))) return rc;
+    } else if (r.grid >= 1) {
+        if (r.kind == ICV_KERNEL_SD) rc = prepare_se(pl, r, K, st, tmp);
+        else if (hands_back) rc = prepare_fast(pl, m, K, st, tmp);
+        else rc = prepare_generic(pl, r, m, K, lay, st);
+        if (rc) return rc;
+        icv::KParams L = K;  // (K itself goes on to the hand-back launch)
+        if (r.kind == ICV_KERNEL_X16) {
+            L.win_off = p.x16_s01_off;
+            L.hist_off = p.x16_hist_off;
+            L.scratch_off = p.x16_scratch_off;
+        }
+        if ((rc = run_kernel(r, L, st))) return rc;
+    }
+    if (kernel_done) HIP_TRY(hipEventRecord(kernel_done, st));
+    if (hands_back && r.grid >= 1) {
+        // per-wavefront partial moments -> cell_stats (cells handed back are overwritten by k_smooth below); in
+        // chunk-moment mode the kernel has reduced them per chunk itself
+        const dim3 fg((unsigned)((K.n_rows + 255) / 256));
+        if (!K.chunk_part && r.kind == ICV_KERNEL_X16)
+            hipLaunchKernelGGL(icv::k_stats_finish_n, fg, dim3(256), 0, st, K.cell_part, K.n_rows, icv::XWAVE, K.cell_stats);
+        else if (!K.chunk_part)
+            hipLaunchKernelGGL(icv::k_stats_finish, fg, dim3(256), 0, st, K.cell_part, K.n_rows, K.cell_stats);
+        if ((rc = launch_hand_back(pl, K, st, m->format == ICV_CSR))) return rc;
+    }
+    pl->last_kernel = r.kind;
+    return ICV_OK;
 }
 
 // float64 windows of all cells, chromosome group by chromosome group (every pass re-reads the rows and keeps only
@@ -857,13 +899,11 @@ int split_windows(icv_plan_t pl, const icv_matrix* m, const icv::KParams& K, dou
         P.win_only = 1;
         P.row_list = nullptr;
         P.row_count = nullptr;
-        if (f32)
-            rc = m->format == ICV_DENSE ? launch_smooth_t<float, false>(part, P, lay, st)
-                                        : launch_smooth_t<float, true>(part, P, lay, st);
-        else
-            rc = m->format == ICV_DENSE ? launch_smooth_t<double, false>(part, P, lay, st)
-                                        : launch_smooth_t<double, true>(part, P, lay, st);
-        if (rc) return rc;
+        // (the generic kernel whatever the group's geometry: the median and the centring run on the collected windows)
+        const SmoothRoute r = by_matrix(m, [&](auto t, auto csr) {
+            return generic_route<decltype(t), decltype(csr)::value>(part, lay, P.n_rows);
+        });
+        if ((rc = run_route(part, r, m, P, lay, st))) return rc;
     }
     return ICV_OK;
 }
@@ -893,58 +933,13 @@ int smooth_split(icv_plan_t pl, const icv_matrix* m, const icv::KParams& K, hipS
     return rc;
 }
 
-int launch_smooth(icv_plan_t pl, const icv_matrix* m, const icv::KParams& K, const icv::Layout& lay,
-                  hipStream_t st, hipEvent_t kernel_done = nullptr, bool* recorded = nullptr) {
-    if (recorded) *recorded = false;
-    if (!lay.fits) {
-        pl->last_kernel = ICV_KERNEL_SPLIT;
-        return smooth_split(pl, m, K, st);
-    }
-    const bool want_win = K.win_out != nullptr;
-    const bool fast_allowed = m->dtype == ICV_F32 && std::isfinite(K.cap) && !knobs().force_generic;
-    if (fast_allowed && m->format == ICV_DENSE && pl->p.ws_ok && K.vec_ok) {
-        const int rc = launch_smooth_fast(pl, K, st, false, 0, 0, kernel_done);
-        if (rc >= 0) {
-            if (recorded) *recorded = kernel_done != nullptr;
-            return rc;
-        }
-    }
-    if (fast_allowed && m->format == ICV_CSR && m->csr_end > m->csr_begin) {
-        if (stored_entries_kernel(pl, m, K, lay) && (!want_win || K.chunk_part)) {
-            if (recorded) *recorded = kernel_done != nullptr;
-            return launch_smooth_se(pl, K, st, kernel_done, m->csr_end - m->csr_begin, m->_pad > 0 ? m->_pad : 0);
-        }
-        if (pl->p.ws_ok && aligned16(K.ref_lo) && !want_win) {
-            const int rc = launch_smooth_fast(pl, K, st, true, m->csr_begin, m->csr_end, kernel_done);
-            if (rc >= 0) {
-                if (recorded) *recorded = kernel_done != nullptr;
-                return rc;
-            }
-        }
-    }
-    pl->last_kernel = ICV_KERNEL_GENERIC;
-    if (m->dtype == ICV_F32)
-        return m->format == ICV_DENSE ? launch_smooth_t<float, false>(pl, K, lay, st)
-                                      : launch_smooth_t<float, true>(pl, K, lay, st);
-    return m->format == ICV_DENSE ? launch_smooth_t<double, false>(pl, K, lay, st)
-                                  : launch_smooth_t<double, true>(pl, K, lay, st);
-}
-
 int launch_apply(const icv_matrix* m, const icv::KParams& K, const double* thr, int64_t chunksize,
                  int64_t row_phase, hipStream_t st) {
     if (K.n_rows < 1) return ICV_OK;
-    dim3 grid((unsigned)K.n_rows), block(256);
-    if (m->dtype == ICV_F32) {
-        if (m->format == ICV_DENSE)
-            hipLaunchKernelGGL((icv::k_apply_thr<float, false>), grid, block, 0, st, K, thr, chunksize, row_phase);
-        else
-            hipLaunchKernelGGL((icv::k_apply_thr<float, true>), grid, block, 0, st, K, thr, chunksize, row_phase);
-    } else {
-        if (m->format == ICV_DENSE)
-            hipLaunchKernelGGL((icv::k_apply_thr<double, false>), grid, block, 0, st, K, thr, chunksize, row_phase);
-        else
-            hipLaunchKernelGGL((icv::k_apply_thr<double, true>), grid, block, 0, st, K, thr, chunksize, row_phase);
-    }
+    by_matrix(m, [&](auto t, auto csr) {
+        hipLaunchKernelGGL((icv::k_apply_thr<decltype(t), decltype(csr)::value>), dim3((unsigned)K.n_rows), dim3(256), 0, st,
+                           K, thr, chunksize, row_phase);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -1241,13 +1236,7 @@ int icv_colsum(const icv_matrix* m, const int32_t* row_group, int32_t n_groups, 
     const int nc = m->n_cols;
     if (m->format == ICV_CSR) {
         // one 1024-thread workgroup per (slab, column tile), the whole LDS of a CU each: two slabs per CU
-        int n_cu = 256;
-        {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                n_cu = prop.multiProcessorCount;
-        }
+        const int n_cu = current_cu_count();
         int rows_per_slab = (int)((m->n_rows + (int64_t)n_cu * 2 - 1) / ((int64_t)n_cu * 2));
         if (rows_per_slab < 64) rows_per_slab = 64;
         const int64_t n_slabs = (m->n_rows + rows_per_slab - 1) / rows_per_slab;
@@ -1257,24 +1246,19 @@ int icv_colsum(const icv_matrix* m, const int32_t* row_group, int32_t n_groups, 
         HIP_TRY(partial_b.alloc((size_t)n_slabs * nc * sizeof(double), st));
         double* partial = partial_b.as<double>();
         dim3 grid((unsigned)n_tiles, (unsigned)n_slabs), block(icv::kCsThreads);
-        typedef void (*kf_t)(const float*, const int64_t*, const int32_t*, int64_t, int, const int32_t*, int, int, double*);
-        typedef void (*kd_t)(const double*, const int64_t*, const int32_t*, int64_t, int, const int32_t*, int, int, double*);
-        const kf_t kf = row_group ? (kf_t)icv::k_colsum_csr<float, true> : (kf_t)icv::k_colsum_csr<float, false>;
-        const kd_t kd = row_group ? (kd_t)icv::k_colsum_csr<double, true> : (kd_t)icv::k_colsum_csr<double, false>;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        for (int g = 0; g < n_groups; ++g) {
-            if (m->dtype == ICV_F32)
-                hipLaunchKernelGGL(kf, grid, block, lds, st, (const float*)m->values, m->indptr, m->indices, m->n_rows,
-                                   nc, row_group, g, rows_per_slab, partial);
-            else
-                hipLaunchKernelGGL(kd, grid, block, lds, st, (const double*)m->values, m->indptr, m->indices, m->n_rows,
-                                   nc, row_group, g, rows_per_slab, partial);
-            hipLaunchKernelGGL(icv::k_colsum_finish, dim3((nc + 63) / 64), dim3(1024), 0, st, partial, (int)n_slabs, nc,
-                               sums + (int64_t)g * nc);
-        }
-        HIP_TRY(hipGetLastError());
-        return ICV_OK;
+        return by_dtype(m->dtype, [&](auto t) {
+            using T = decltype(t);
+            const auto kern = row_group ? icv::k_colsum_csr<T, true> : icv::k_colsum_csr<T, false>;
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            for (int g = 0; g < n_groups; ++g) {
+                hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)m->values, m->indptr, m->indices, m->n_rows, nc,
+                                   row_group, g, rows_per_slab, partial);
+                hipLaunchKernelGGL(icv::k_colsum_finish, dim3((nc + 63) / 64), dim3(1024), 0, st, partial, (int)n_slabs, nc,
+                                   sums + (int64_t)g * nc);
+            }
+            HIP_TRY(hipGetLastError());
+            return (int)ICV_OK;
+        });
     }
     // slab height from the row count alone (the sums must not depend on the device): 1024 rows stream fastest
     // (tools/microbench_colsum.hip), shorter slabs keep every CU busy on small matrices
@@ -1285,12 +1269,11 @@ int icv_colsum(const icv_matrix* m, const int32_t* row_group, int32_t n_groups, 
     double* partial = partial_b.as<double>();
     dim3 grid((nc + 255) / 256, (unsigned)n_slabs), block(256);
     for (int g = 0; g < n_groups; ++g) {
-        if (m->dtype == ICV_F32)
-            hipLaunchKernelGGL(icv::k_colsum_dense<float>, grid, block, 0, st, (const float*)m->values, m->n_rows,
-                               m->ld, nc, row_group, g, rows_per_slab, partial);
-        else
-            hipLaunchKernelGGL(icv::k_colsum_dense<double>, grid, block, 0, st, (const double*)m->values,
-                               m->n_rows, m->ld, nc, row_group, g, rows_per_slab, partial);
+        by_dtype(m->dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(icv::k_colsum_dense<T>, grid, block, 0, st, (const T*)m->values, m->n_rows, m->ld, nc,
+                               row_group, g, rows_per_slab, partial);
+        });
         hipLaunchKernelGGL(icv::k_colsum_finish, dim3((nc + 63) / 64), dim3(1024), 0, st, partial, (int)n_slabs, nc,
                            sums + (int64_t)g * nc);
     }
@@ -1409,26 +1392,24 @@ int icv_colchain(const icv_matrix* m, const int32_t* rows, int64_t n_sel, double
     if (n_sel < 0 || n_sel > m->n_rows) return fail(ICV_ERR_INVALID, "icv_colchain: n_sel out of range");
     if (n_sel == 0 || m->n_cols == 0) return ICV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (m->format == ICV_CSR)
-        return m->dtype == ICV_F32 ? colchain_csr<float>(m, rows, n_sel, scale, (float*)acc, st)
-                                   : colchain_csr<double>(m, rows, n_sel, scale, (double*)acc, st);
-    if (m->format != ICV_DENSE) return fail(ICV_ERR_INVALID, "format must be dense or csr");
-    return m->dtype == ICV_F32 ? colchain_dense<float>(m, rows, n_sel, (float*)acc, st)
-                               : colchain_dense<double>(m, rows, n_sel, (double*)acc, st);
+    if (m->format != ICV_DENSE && m->format != ICV_CSR) return fail(ICV_ERR_INVALID, "format must be dense or csr");
+    return by_matrix(m, [&](auto t, auto csr) {
+        using T = decltype(t);
+        if constexpr (decltype(csr)::value) return colchain_csr<T>(m, rows, n_sel, scale, (T*)acc, st);
+        else return colchain_dense<T>(m, rows, n_sel, (T*)acc, st);
+    });
 }
 
 int icv_colchain_mean(const void* acc, int32_t dtype, int32_t n_cols, int64_t count, void* mean, void* stream) {
     if (!acc || !mean || count < 1 || n_cols < 0) return fail(ICV_ERR_INVALID, "bad colchain_mean arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_cols == 0) return ICV_OK;
-    if (dtype == ICV_F32)
-        hipLaunchKernelGGL(k_chain_mean<float>, dim3((n_cols + 255) / 256), dim3(256), 0, st, (const float*)acc, n_cols,
-                           (float)count, (float*)mean);
-    else if (dtype == ICV_F64)
-        hipLaunchKernelGGL(k_chain_mean<double>, dim3((n_cols + 255) / 256), dim3(256), 0, st, (const double*)acc,
-                           n_cols, (double)count, (double*)mean);
-    else
-        return fail(ICV_ERR_INVALID, "dtype must be ICV_F32 or ICV_F64");
+    if (dtype != ICV_F32 && dtype != ICV_F64) return fail(ICV_ERR_INVALID, "dtype must be ICV_F32 or ICV_F64");
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_chain_mean<T>, dim3((n_cols + 255) / 256), dim3(256), 0, st, (const T*)acc, n_cols, (T)count,
+                           (T*)mean);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -1438,14 +1419,12 @@ int icv_colmean_csc(const void* values, int32_t dtype, const int64_t* colptr, co
     if (!values || !colptr || !row_idx || !mean || n_cols < 0) return fail(ICV_ERR_INVALID, "bad colmean_csc arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_cols == 0) return ICV_OK;
-    if (dtype == ICV_F32)
-        hipLaunchKernelGGL(icv::k_colpair_csc<float>, dim3((n_cols + 63) / 64), dim3(64), 0, st, (const float*)values,
-                           colptr, row_idx, n_cols, row_group, group, (float)scale, (float*)mean);
-    else if (dtype == ICV_F64)
-        hipLaunchKernelGGL(icv::k_colpair_csc<double>, dim3((n_cols + 63) / 64), dim3(64), 0, st, (const double*)values,
-                           colptr, row_idx, n_cols, row_group, group, scale, (double*)mean);
-    else
-        return fail(ICV_ERR_INVALID, "dtype must be ICV_F32 or ICV_F64");
+    if (dtype != ICV_F32 && dtype != ICV_F64) return fail(ICV_ERR_INVALID, "dtype must be ICV_F32 or ICV_F64");
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_colpair_csc<T>, dim3((n_cols + 63) / 64), dim3(64), 0, st, (const T*)values, colptr,
+                           row_idx, n_cols, row_group, group, (T)scale, (T*)mean);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -1455,14 +1434,12 @@ int icv_colsum_pairwise(const void* xt, int32_t dtype, int64_t n_rows, int32_t n
     if (!xt || !sums || n_rows < 0 || n_cols < 0 || ld < n_rows) return fail(ICV_ERR_INVALID, "bad colsum_pairwise arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_cols == 0) return ICV_OK;
-    if (dtype == ICV_F32)
-        hipLaunchKernelGGL(icv::k_colpair_dense<float>, dim3((n_cols + 63) / 64), dim3(64), 0, st, (const float*)xt,
-                           n_rows, n_cols, ld, (float*)sums);
-    else if (dtype == ICV_F64)
-        hipLaunchKernelGGL(icv::k_colpair_dense<double>, dim3((n_cols + 63) / 64), dim3(64), 0, st, (const double*)xt,
-                           n_rows, n_cols, ld, (double*)sums);
-    else
-        return fail(ICV_ERR_INVALID, "dtype must be ICV_F32 or ICV_F64");
+    if (dtype != ICV_F32 && dtype != ICV_F64) return fail(ICV_ERR_INVALID, "dtype must be ICV_F32 or ICV_F64");
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_colpair_dense<T>, dim3((n_cols + 63) / 64), dim3(64), 0, st, (const T*)xt, n_rows, n_cols,
+                           ld, (T*)sums);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -1480,12 +1457,12 @@ int icv_infercnv_smooth(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, 
     const icv::Layout* lay;
     if ((rc = fill_params(pl, m, ref_lo, ref_hi, lfc_clip, flags, out, ldo, cell_median, cell_stats, K, lay)))
         return rc;
-    return launch_smooth(pl, m, K, *lay, static_cast<hipStream_t>(stream));
+    return run_route(pl, pick_route(pl, m, K, *lay, false), m, K, *lay, static_cast<hipStream_t>(stream));
 }
 
 int icv_chunk_thresholds(const double* cell_stats, int64_t n_rows, int64_t chunksize, int64_t row_phase,
                          int32_t n_windows, double dynamic_threshold, double* thr, void* stream) {
-    if (!cell_stats || !thr || chunksize < 1 || row_phase < 0 || row_phase >= chunksize)
+    if (!cell_stats || !thr || !chunk_args_ok(thr, chunksize, row_phase))
         return fail(ICV_ERR_INVALID, "bad chunk threshold arguments");
     if (n_rows < 1) return ICV_OK;
     const int64_t n_chunks = (n_rows + row_phase + chunksize - 1) / chunksize;
@@ -1515,6 +1492,16 @@ int icv_apply_threshold(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, 
 }  // extern "C"
 
 namespace {
+// the stage times of a run from its four events (waits for the last one)
+int read_profile(const hipEvent_t* ev, icv_profile* prof) {
+    HIP_TRY(hipEventSynchronize(ev[3]));
+    HIP_TRY(hipEventElapsedTime(&prof->smooth_ms, ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(&prof->thresholds_ms, ev[1], ev[2]));
+    HIP_TRY(hipEventElapsedTime(&prof->apply_ms, ev[2], ev[3]));
+    HIP_TRY(hipEventElapsedTime(&prof->total_ms, ev[0], ev[3]));
+    return ICV_OK;
+}
+
 // steps 1-5 of the chunk kernel (icv_infercnv_run); win_out != nullptr: the float64 windows before centring as well
 // (icv_infercnv_run_windows).  The caller holds the plan (PLAN_BUSY_GUARD + PLAN_ENTER).
 int run_steps(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void* ref_hi, double lfc_clip,
@@ -1533,7 +1520,6 @@ int run_steps(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void
     // cell_stats == NULL: the caller only wants the thresholds.  The per-row moments then live in a plan-owned
     // buffer, and where k_smooth_x16 runs they are not formed per cell at all: the kernel accumulates them per
     // chunk (one wavefront reduction per chunk instead of per cell).
-    bool chunk_mode = false;
     int64_t n_chunks = 1, cs_eff = m->n_rows > 0 ? m->n_rows : 1, ph_eff = 0;
     if (do_thr) {
         cs_eff = chunksize;
@@ -1541,36 +1527,26 @@ int run_steps(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void
         n_chunks = (m->n_rows + row_phase + chunksize - 1) / chunksize;
         if (n_chunks < 1) n_chunks = 1;
     }
-    if (!cell_stats && m->n_rows > 0) {
-        if (pl->hb_stats_cap < m->n_rows) {
-            (void)hipFree(pl->d_hb_stats);
-            pl->d_hb_stats = nullptr;
-            pl->hb_stats_cap = 0;
-            HIP_TRY(hipMalloc((void**)&pl->d_hb_stats, (size_t)m->n_rows * 2 * sizeof(double)));
-            pl->hb_stats_cap = m->n_rows;
-        }
+    // chunk moments are asked for as long as the partial slots of all chunks stay within 64 MB (slots per chunk: the
+    // larger of k_smooth_x16's n_cu workgroups x 16 wavefronts and k_smooth_se's full grid x 8 wavefronts)
+    const int64_t se_slots = ((int64_t)pl->n_cu * (icv::kLdsLimit / icv::kSeLds)) * icv::NWAVE;
+    const int64_t x16_slots = (int64_t)pl->n_cu * icv::XWAVE;
+    const int64_t n_part = se_slots > x16_slots ? se_slots : x16_slots;
+    const bool lean = !cell_stats && m->n_rows > 0;
+    const SmoothRoute route = pick_route(pl, m, K, *lay, lean && n_chunks * n_part <= (int64_t)(64 << 20) / 16);
+    const int64_t n_slots = route.moment_slots;  // of the launch: slots of absent workgroups do not exist
+    const bool chunk_mode = n_slots > 0;
+    if (lean) {
+        if ((rc = grow(pl->d_hb_stats, pl->hb_stats_cap, m->n_rows, 2 * sizeof(double)))) return rc;
         K.cell_stats = pl->d_hb_stats;
-        // partial-moment slots per chunk: k_smooth_x16: n_cu workgroups x 16 wavefronts; k_smooth_se: its own grid
-        // (se_grid: whatever its LDS map allows per CU) x 8 wavefronts -- sized for the larger of the two
-        const int64_t se_slots = ((int64_t)pl->n_cu * (icv::kLdsLimit / icv::kSeLds)) * icv::NWAVE;
-        const int64_t x16_slots = (int64_t)pl->n_cu * icv::XWAVE;
-        const int64_t n_part = se_slots > x16_slots ? se_slots : x16_slots;
-        if ((x16_applies(pl, m, K, *lay) || stored_entries_kernel(pl, m, K, *lay)) &&
-            n_chunks * n_part <= (int64_t)(64 << 20) / 16) {
-            chunk_mode = true;
-            if (pl->chunk_part_cap < n_chunks * n_part) {
-                (void)hipFree(pl->d_chunk_part);
-                pl->d_chunk_part = nullptr;
-                pl->chunk_part_cap = 0;
-                HIP_TRY(hipMalloc((void**)&pl->d_chunk_part, (size_t)(n_chunks * n_part) * 2 * sizeof(double)));
-                pl->chunk_part_cap = n_chunks * n_part;
-            }
-            HIP_TRY(hipMemsetAsync(pl->d_chunk_part, 0, (size_t)(n_chunks * n_part) * 2 * sizeof(double), st));
-            HIP_TRY(hipMemsetAsync(pl->d_hb_stats, 0, (size_t)m->n_rows * 2 * sizeof(double), st));
-            K.chunk_part = pl->d_chunk_part;
-            K.chunksize = cs_eff;
-            K.row_phase = ph_eff;
-        }
+    }
+    if (chunk_mode) {
+        if ((rc = grow(pl->d_chunk_part, pl->chunk_part_cap, n_chunks * n_slots, 2 * sizeof(double)))) return rc;
+        HIP_TRY(hipMemsetAsync(pl->d_chunk_part, 0, (size_t)(n_chunks * n_slots) * 2 * sizeof(double), st));
+        HIP_TRY(hipMemsetAsync(pl->d_hb_stats, 0, (size_t)m->n_rows * 2 * sizeof(double), st));
+        K.chunk_part = pl->d_chunk_part;
+        K.chunksize = cs_eff;
+        K.row_phase = ph_eff;
     }
     EventSet evs;
     hipEvent_t* ev = evs.ev;
@@ -1580,20 +1556,8 @@ int run_steps(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void
         for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ev[i]));
         HIP_TRY(hipEventRecord(ev[0], st));
     }
-    bool ev1_done = false;
-    if ((rc = launch_smooth(pl, m, K, *lay, st, timed ? ev[1] : nullptr, &ev1_done))) return rc;
-    if (timed && !ev1_done) HIP_TRY(hipEventRecord(ev[1], st));
+    if ((rc = run_route(pl, route, m, K, *lay, st, timed ? ev[1] : nullptr))) return rc;
     if (do_thr && chunk_mode) {
-        // partial slots of the launch: min(CUs, rows) workgroups x 16 wavefronts (k_smooth_x16), min(2 CUs, rows) x 8
-        // (k_smooth_se); slots of absent workgroups are zero
-        int64_t n_slots;
-        if (m->format == ICV_CSR) {
-            n_slots = se_grid(pl, m->n_rows) * icv::NWAVE;  // the grid launch_smooth_se used
-        } else {
-            int64_t gx = pl->n_cu;
-            if (gx > m->n_rows) gx = m->n_rows;
-            n_slots = gx * icv::XWAVE;
-        }
         hipLaunchKernelGGL(icv::k_chunk_thr_part, dim3((unsigned)n_chunks), dim3(256), 0, st, pl->d_chunk_part,
                            (int)n_slots, pl->d_hb_stats, m->n_rows, chunksize, row_phase, pl->p.W,
                            dynamic_threshold, thr);
@@ -1610,11 +1574,7 @@ int run_steps(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void
         for (int i = 0; i < 4; ++i) pl->prof_events.push_back(ev[i]);
         evs.keep = true;
     } else if (prof) {
-        HIP_TRY(hipEventSynchronize(ev[3]));
-        HIP_TRY(hipEventElapsedTime(&prof->smooth_ms, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&prof->thresholds_ms, ev[1], ev[2]));
-        HIP_TRY(hipEventElapsedTime(&prof->apply_ms, ev[2], ev[3]));
-        HIP_TRY(hipEventElapsedTime(&prof->total_ms, ev[0], ev[3]));
+        return read_profile(ev, prof);
     }
     return ICV_OK;
 }
@@ -1634,9 +1594,7 @@ int gene_from_windows(icv_plan_t pl, const double* win, int64_t ldw, int64_t n, 
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int per_cu = (int)((size_t)icv::kLdsLimit / lds);
         if (per_cu > 2048 / icv::kGvThreads) per_cu = 2048 / icv::kGvThreads;  // 32 wavefronts per CU
-        int64_t grid = (int64_t)pl->n_cu * per_cu;
-        if (grid > n) grid = n;
-        hipLaunchKernelGGL(icv::k_gene_fused, dim3((unsigned)grid), dim3(icv::kGvThreads), lds, st, win, ldw, n, W,
+        hipLaunchKernelGGL(icv::k_gene_fused, dim3((unsigned)cu_grid(pl, per_cu, n)), dim3(icv::kGvThreads), lds, st, win, ldw, n, W,
                            pl->d_gv_pk, pl->d_gv_mult, R, n_cov, pl->d_gv_col16, p.n_cols_all, thr,
                            chunksize > 0 ? chunksize : 1, row_phase, gene_out, ldg, pl->gv_mult_bytes, (int)pk_lds);
         HIP_TRY(hipGetLastError());
@@ -1692,7 +1650,7 @@ int icv_infercnv_run_windows(icv_plan_t pl, const icv_matrix* m, const void* ref
     const bool do_thr = !std::isnan(dynamic_threshold);
     if (m->n_rows == 0) return ICV_OK;  // an empty shard: no cell, no chunk, nothing written
     if (!cell_median) return fail(ICV_ERR_INVALID, "cell_median is required");
-    if (do_thr && (!thr || chunksize < 1 || row_phase < 0 || row_phase >= chunksize))
+    if (do_thr && (!thr || !chunk_args_ok(thr, chunksize, row_phase)))
         return fail(ICV_ERR_INVALID, "thr buffer / chunksize / row_phase invalid");
     if (win_out && ldw < pl->p.W) return fail(ICV_ERR_INVALID, "ldw < n_windows");
     if ((rc = ensure_device(pl))) return rc;
@@ -1707,8 +1665,7 @@ int icv_gene_values_from_windows(icv_plan_t pl, const double* win, int64_t ldw, 
     PLAN_BUSY_GUARD(pl);
     if (n_rows < 0 || (n_rows > 0 && (!win || !gene_out)) || ldw < pl->p.W || ldg < pl->p.n_cols_all)
         return fail(ICV_ERR_INVALID, "bad gene_values_from_windows arguments (null buffer, ldw < n_windows or ldg < n_cols)");
-    if (thr && (chunksize < 1 || row_phase < 0 || row_phase >= chunksize))
-        return fail(ICV_ERR_INVALID, "chunksize / row_phase invalid");
+    if (!chunk_args_ok(thr, chunksize, row_phase)) return fail(ICV_ERR_INVALID, "chunksize / row_phase invalid");
     int rc;
     if ((rc = ensure_device(pl))) return rc;
     PLAN_ENTER(stream);
@@ -1729,13 +1686,8 @@ int icv_profile_collect(icv_plan_t pl, icv_profile* out, int32_t max_records, in
     const int n = (int)(pl->prof_events.size() / 4);
     int k = 0;
     for (int i = 0; i < n; ++i) {
-        hipEvent_t* ev = pl->prof_events.data() + 4 * i;
         if (k < max_records) {
-            HIP_TRY(hipEventSynchronize(ev[3]));
-            HIP_TRY(hipEventElapsedTime(&out[k].smooth_ms, ev[0], ev[1]));
-            HIP_TRY(hipEventElapsedTime(&out[k].thresholds_ms, ev[1], ev[2]));
-            HIP_TRY(hipEventElapsedTime(&out[k].apply_ms, ev[2], ev[3]));
-            HIP_TRY(hipEventElapsedTime(&out[k].total_ms, ev[0], ev[3]));
+            if (int rc = read_profile(pl->prof_events.data() + 4 * i, &out[k])) return rc;
             ++k;
         }
     }
@@ -1753,8 +1705,7 @@ int icv_gene_values(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, cons
     if (rc) return rc;
     PLAN_BUSY_GUARD(pl);
     if (!gene_out || ldg < m->n_cols) return fail(ICV_ERR_INVALID, "gene_out is null or ldg < n_cols");
-    if (thr && (chunksize < 1 || row_phase < 0 || row_phase >= chunksize))
-        return fail(ICV_ERR_INVALID, "chunksize / row_phase invalid");
+    if (!chunk_args_ok(thr, chunksize, row_phase)) return fail(ICV_ERR_INVALID, "chunksize / row_phase invalid");
     if ((rc = ensure_device(pl))) return rc;
     PLAN_ENTER(stream);
     const int64_t n = m->n_rows;
@@ -1780,7 +1731,7 @@ int icv_threshold_mask(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, c
     int rc = check_matrix(pl, m);
     if (rc) return rc;
     PLAN_BUSY_GUARD(pl);
-    if (!cell_median || !mask || !row_nnz || (thr && (chunksize < 1 || row_phase < 0 || row_phase >= chunksize)))
+    if (!cell_median || !mask || !row_nnz || !chunk_args_ok(thr, chunksize, row_phase))
         return fail(ICV_ERR_INVALID, "bad threshold_mask arguments");
     if ((rc = ensure_device(pl))) return rc;
     PLAN_ENTER(stream);
@@ -1809,36 +1760,18 @@ int icv_threshold_mask(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, c
                                     hipFuncAttributeMaxDynamicSharedMemorySize, icv::kPmLds));  // (per device: every call)
         hipLaunchKernelGGL(icv::k_thr_mask_ring, dim3(gx), dim3(icv::kPmThreads), lds, st, K, thr, cs, row_phase, mk, n_words,
                            row_nnz, pl->d_tie_n, ties.as<unsigned long long>());
-        if (thr) {
-            dim3 tg(128), tb(256);
-            const auto* tl = ties.as<unsigned long long>();
-            if (m->dtype == ICV_F32) {
-                if (m->format == ICV_DENSE)
-                    hipLaunchKernelGGL((icv::k_thr_mask_ties<float, false>), tg, tb, 0, st, K, thr, cs, row_phase, mk, n_words, row_nnz, pl->d_tie_n, tl);
-                else
-                    hipLaunchKernelGGL((icv::k_thr_mask_ties<float, true>), tg, tb, 0, st, K, thr, cs, row_phase, mk, n_words, row_nnz, pl->d_tie_n, tl);
-            } else {
-                if (m->format == ICV_DENSE)
-                    hipLaunchKernelGGL((icv::k_thr_mask_ties<double, false>), tg, tb, 0, st, K, thr, cs, row_phase, mk, n_words, row_nnz, pl->d_tie_n, tl);
-                else
-                    hipLaunchKernelGGL((icv::k_thr_mask_ties<double, true>), tg, tb, 0, st, K, thr, cs, row_phase, mk, n_words, row_nnz, pl->d_tie_n, tl);
-            }
-        }
+        if (thr)
+            by_matrix(m, [&](auto t, auto csr) {
+                hipLaunchKernelGGL((icv::k_thr_mask_ties<decltype(t), decltype(csr)::value>), dim3(128), dim3(256), 0, st, K, thr,
+                                   cs, row_phase, mk, n_words, row_nnz, pl->d_tie_n, ties.as<unsigned long long>());
+            });
         HIP_TRY(hipGetLastError());
         return ICV_OK;
     }
-    dim3 grid((unsigned)K.n_rows), block(256);
-    if (m->dtype == ICV_F32) {
-        if (m->format == ICV_DENSE)
-            hipLaunchKernelGGL((icv::k_thr_mask<float, false>), grid, block, 0, st, K, thr, cs, row_phase, mk, n_words, row_nnz);
-        else
-            hipLaunchKernelGGL((icv::k_thr_mask<float, true>), grid, block, 0, st, K, thr, cs, row_phase, mk, n_words, row_nnz);
-    } else {
-        if (m->format == ICV_DENSE)
-            hipLaunchKernelGGL((icv::k_thr_mask<double, false>), grid, block, 0, st, K, thr, cs, row_phase, mk, n_words, row_nnz);
-        else
-            hipLaunchKernelGGL((icv::k_thr_mask<double, true>), grid, block, 0, st, K, thr, cs, row_phase, mk, n_words, row_nnz);
-    }
+    by_matrix(m, [&](auto t, auto csr) {
+        hipLaunchKernelGGL((icv::k_thr_mask<decltype(t), decltype(csr)::value>), dim3((unsigned)K.n_rows), dim3(256), 0, st, K,
+                           thr, cs, row_phase, mk, n_words, row_nnz);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -1850,8 +1783,7 @@ int icv_threshold_pack(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, c
     int rc = check_matrix(pl, m);
     if (rc) return rc;
     PLAN_BUSY_GUARD(pl);
-    if (!cell_median || !indptr || !indices || !data || capacity < 0 ||
-        (thr && (chunksize < 1 || row_phase < 0 || row_phase >= chunksize)))
+    if (!cell_median || !indptr || !indices || !data || capacity < 0 || !chunk_args_ok(thr, chunksize, row_phase))
         return fail(ICV_ERR_INVALID, "bad threshold_pack arguments");
     if (pl->p.W > 320 * 64) return fail(ICV_ERR_UNSUPPORTED, "icv_threshold_pack: more than 20480 windows");
     // rows per workgroup (= per look-back ticket): as many as keep their mask words in the workgroup's LDS, at most 16
@@ -1882,17 +1814,10 @@ int icv_threshold_pack(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, c
     auto* gacc = gstat + n_groups;
     auto* ticket = reinterpret_cast<unsigned int*>(gacc + n_groups);
     const int64_t cs = thr ? chunksize : 1;
-    dim3 grid((unsigned)n_tickets), block(256);
-#define ICV_PACK(TT, CC) \
-    hipLaunchKernelGGL((icv::k_thr_pack<TT, CC>), grid, block, 0, st, K, thr, cs, row_phase, rpw, ticket, status, gstat, gacc, indptr, indices, data, capacity)
-    if (m->dtype == ICV_F32) {
-        if (m->format == ICV_DENSE) ICV_PACK(float, false);
-        else ICV_PACK(float, true);
-    } else {
-        if (m->format == ICV_DENSE) ICV_PACK(double, false);
-        else ICV_PACK(double, true);
-    }
-#undef ICV_PACK
+    by_matrix(m, [&](auto t, auto csr) {
+        hipLaunchKernelGGL((icv::k_thr_pack<decltype(t), decltype(csr)::value>), dim3((unsigned)n_tickets), dim3(256), 0, st, K,
+                           thr, cs, row_phase, rpw, ticket, status, gstat, gacc, indptr, indices, data, capacity);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -2775,6 +2700,9 @@ int icv_project(const icv_matrix* m, const double* v, int32_t k, const double* s
 
 // ---- host-side packing of a mostly-zero dense matrix (the upload path of tl.infercnv for dense host input) ---------------
 namespace {
+template <typename T>
+using host_bits = std::conditional_t<sizeof(T) == 4, uint32_t, uint64_t>;  // an element's bit pattern
+
 template <typename T, typename B>
 void host_count_rows(const T* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, int64_t* row_nnz) {
     for (int64_t r = r0; r < r1; ++r) {
@@ -2815,7 +2743,7 @@ void host_pack_rows(const T* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t 
 // [indptr[r], indptr[r + 1]), so rows can be packed by different threads.
 #if defined(__x86_64__)
 __attribute__((target("avx512f,avx512vl,avx512bw,popcnt")))
-void host_count_rows_avx512_f32(const float* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, int64_t* row_nnz) {
+void host_count_rows_avx512(const float* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, int64_t* row_nnz) {
     for (int64_t r = r0; r < r1; ++r) {
         const float* xr = x + r * ld;
         int64_t c = 0, j = 0;
@@ -2829,7 +2757,7 @@ void host_count_rows_avx512_f32(const float* x, int64_t r0, int64_t r1, int64_t 
     }
 }
 __attribute__((target("avx512f,avx512vl,avx512bw,popcnt")))
-void host_count_rows_avx512_f64(const double* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, int64_t* row_nnz) {
+void host_count_rows_avx512(const double* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, int64_t* row_nnz) {
     for (int64_t r = r0; r < r1; ++r) {
         const double* xr = x + r * ld;
         int64_t c = 0, j = 0;
@@ -2843,7 +2771,7 @@ void host_count_rows_avx512_f64(const double* x, int64_t r0, int64_t r1, int64_t
     }
 }
 __attribute__((target("avx512f,avx512vl,avx512bw,popcnt")))
-void host_pack_rows_avx512_f32(const float* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, const int64_t* indptr,
+void host_pack_rows_avx512(const float* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, const int64_t* indptr,
                                int32_t* indices, float* values) {
     const __m512i iota = _mm512_setr_epi32(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
     for (int64_t r = r0; r < r1; ++r) {
@@ -2863,7 +2791,7 @@ void host_pack_rows_avx512_f32(const float* x, int64_t r0, int64_t r1, int64_t n
     }
 }
 __attribute__((target("avx512f,avx512vl,avx512bw,popcnt")))
-void host_pack_rows_avx512_f64(const double* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, const int64_t* indptr,
+void host_pack_rows_avx512(const double* x, int64_t r0, int64_t r1, int64_t n_cols, int64_t ld, const int64_t* indptr,
                                int32_t* indices, double* values) {
     const __m256i iota = _mm256_setr_epi32(0, 1, 2, 3, 4, 5, 6, 7);
     for (int64_t r = r0; r < r1; ++r) {
@@ -2884,7 +2812,7 @@ void host_pack_rows_avx512_f64(const double* x, int64_t r0, int64_t r1, int64_t 
 }
 // one row into a staging area with 16 slots of slack behind the row's worst case: no bound to respect, returns the count
 __attribute__((target("avx512f,avx512vl,avx512bw,popcnt")))
-int64_t host_pack_row_avx512_f32(const float* xr, int64_t n_cols, int32_t* indices, float* values) {
+int64_t host_pack_row_avx512(const float* xr, int64_t n_cols, int32_t* indices, float* values) {
     const __m512i iota = _mm512_setr_epi32(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
     int64_t k = 0, j = 0;
     for (; j + 16 <= n_cols; j += 16) {
@@ -2904,7 +2832,7 @@ int64_t host_pack_row_avx512_f32(const float* xr, int64_t n_cols, int32_t* indic
     return k;
 }
 __attribute__((target("avx512f,avx512vl,avx512bw,popcnt")))
-int64_t host_pack_row_avx512_f64(const double* xr, int64_t n_cols, int32_t* indices, double* values) {
+int64_t host_pack_row_avx512(const double* xr, int64_t n_cols, int32_t* indices, double* values) {
     const __m256i iota = _mm256_setr_epi32(0, 1, 2, 3, 4, 5, 6, 7);
     int64_t k = 0, j = 0;
     for (; j + 8 <= n_cols; j += 8) {
@@ -3025,8 +2953,7 @@ int host_pack_fused(const T* x, int64_t n_rows, int64_t n_cols, int64_t ld, int6
                 int64_t c;
 #if defined(__x86_64__)
                 if (vec) {
-                    if constexpr (sizeof(T) == 4) c = host_pack_row_avx512_f32((const float*)xr, n_cols, s_idx_p + n, (float*)s_val_p + n);
-                    else c = host_pack_row_avx512_f64((const double*)xr, n_cols, s_idx_p + n, (double*)s_val_p + n);
+                    c = host_pack_row_avx512(xr, n_cols, s_idx_p + n, s_val_p + n);
                 } else
 #endif
                     c = host_pack_row_scalar<T, B>(xr, n_cols, s_idx_p + n, s_val_p + n);
@@ -3115,20 +3042,15 @@ int icv_host_dense_row_nnz(const void* h_x, int32_t dtype, int64_t n_rows, int64
         return fail(ICV_ERR_INVALID, "bad host_dense_row_nnz arguments");
     try {
         const bool vec = host_has_avx512();
-        if (dtype == ICV_F32)
+        by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
             host_parallel_rows(n_rows, n_threads, [&](int64_t a, int64_t b) {
 #if defined(__x86_64__)
-                if (vec) return host_count_rows_avx512_f32((const float*)h_x, a, b, n_cols, ld, h_row_nnz);
+                if (vec) return host_count_rows_avx512((const T*)h_x, a, b, n_cols, ld, h_row_nnz);
 #endif
-                host_count_rows<float, uint32_t>((const float*)h_x, a, b, n_cols, ld, h_row_nnz);
+                host_count_rows<T, host_bits<T>>((const T*)h_x, a, b, n_cols, ld, h_row_nnz);
             });
-        else
-            host_parallel_rows(n_rows, n_threads, [&](int64_t a, int64_t b) {
-#if defined(__x86_64__)
-                if (vec) return host_count_rows_avx512_f64((const double*)h_x, a, b, n_cols, ld, h_row_nnz);
-#endif
-                host_count_rows<double, uint64_t>((const double*)h_x, a, b, n_cols, ld, h_row_nnz);
-            });
+        });
     } catch (const std::exception& e) {
         return fail(ICV_ERR_NOMEM, std::string("host_dense_row_nnz: ") + e.what());
     }
@@ -3142,25 +3064,15 @@ int icv_host_dense_pack(const void* h_x, int32_t dtype, int64_t n_rows, int64_t 
         return fail(ICV_ERR_INVALID, "bad host_dense_pack arguments");
     try {
         const bool vec = host_has_avx512();
-        if (dtype == ICV_F32)
+        by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
             host_parallel_rows(n_rows, n_threads, [&](int64_t a, int64_t b) {
 #if defined(__x86_64__)
-                if (vec)
-                    return host_pack_rows_avx512_f32((const float*)h_x, a, b, n_cols, ld, h_indptr, h_indices,
-                                                     (float*)h_values);
+                if (vec) return host_pack_rows_avx512((const T*)h_x, a, b, n_cols, ld, h_indptr, h_indices, (T*)h_values);
 #endif
-                host_pack_rows<float, uint32_t>((const float*)h_x, a, b, n_cols, ld, h_indptr, h_indices, (float*)h_values);
+                host_pack_rows<T, host_bits<T>>((const T*)h_x, a, b, n_cols, ld, h_indptr, h_indices, (T*)h_values);
             });
-        else
-            host_parallel_rows(n_rows, n_threads, [&](int64_t a, int64_t b) {
-#if defined(__x86_64__)
-                if (vec)
-                    return host_pack_rows_avx512_f64((const double*)h_x, a, b, n_cols, ld, h_indptr, h_indices,
-                                                     (double*)h_values);
-#endif
-                host_pack_rows<double, uint64_t>((const double*)h_x, a, b, n_cols, ld, h_indptr, h_indices,
-                                                 (double*)h_values);
-            });
+        });
     } catch (const std::exception& e) {
         return fail(ICV_ERR_NOMEM, std::string("host_dense_pack: ") + e.what());
     }
@@ -3174,13 +3086,11 @@ int icv_host_dense_pack_fused(const void* h_x, int32_t dtype, int64_t n_rows, in
         (capacity > 0 && (!h_indices || !h_values)) || (dtype != ICV_F32 && dtype != ICV_F64))
         return fail(ICV_ERR_INVALID, "bad host_dense_pack_fused arguments");
     try {
-        int over;
-        if (dtype == ICV_F32)
-            over = host_pack_fused<float, uint32_t>((const float*)h_x, n_rows, n_cols, ld, h_indptr, h_indices,
-                                                    (float*)h_values, capacity, n_threads, h_nnz);
-        else
-            over = host_pack_fused<double, uint64_t>((const double*)h_x, n_rows, n_cols, ld, h_indptr, h_indices,
-                                                     (double*)h_values, capacity, n_threads, h_nnz);
+        const int over = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return host_pack_fused<T, host_bits<T>>((const T*)h_x, n_rows, n_cols, ld, h_indptr, h_indices, (T*)h_values,
+                                                    capacity, n_threads, h_nnz);
+        });
         if (over)
             return fail(ICV_ERR_NOMEM, "host_dense_pack_fused: the matrix holds more stored entries than `capacity` "
                                        "(*h_nnz has the count: call again with larger buffers)");
@@ -3201,13 +3111,11 @@ int icv_csr_scatter_dense(const void* data, int32_t dtype, const int64_t* indptr
         HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_rows * n_cols * esz, st));
     else
         HIP_TRY(hipMemset2DAsync(out, (size_t)ldo * esz, 0, (size_t)n_cols * esz, (size_t)n_rows, st));
-    dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
-    if (dtype == ICV_F32)
-        hipLaunchKernelGGL(icv::k_csr_scatter_rows<float>, grid, block, 0, st, static_cast<const float*>(data), indptr,
-                           indices, n_rows, static_cast<float*>(out), ldo);
-    else
-        hipLaunchKernelGGL(icv::k_csr_scatter_rows<double>, grid, block, 0, st, static_cast<const double*>(data), indptr,
-                           indices, n_rows, static_cast<double*>(out), ldo);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_csr_scatter_rows<T>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st,
+                           static_cast<const T*>(data), indptr, indices, n_rows, static_cast<T*>(out), ldo);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -3559,14 +3467,11 @@ int icv_leiden_quantise(const int64_t* indptr, const int32_t* indices, const voi
     HIP_TRY(flg.alloc(32, st));
     HIP_TRY(hipMemsetAsync(flg.p, 0, 32, st));
     unsigned long long* sums = reinterpret_cast<unsigned long long*>(static_cast<char*>(flg.p) + 8);
-    if (dtype == ICV_F32)
-        hipLaunchKernelGGL(icv::k_ld_quantise<float>, ld_grid(n, 4), dim3(256), 0, st, indptr, indices,
-                           static_cast<const float*>(data), n, use_weights, wq.as<long long>(), keep.as<long long>(),
-                           flg.as<unsigned>(), sums);
-    else
-        hipLaunchKernelGGL(icv::k_ld_quantise<double>, ld_grid(n, 4), dim3(256), 0, st, indptr, indices,
-                           static_cast<const double*>(data), n, use_weights, wq.as<long long>(), keep.as<long long>(),
-                           flg.as<unsigned>(), sums);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_ld_quantise<T>, ld_grid(n, 4), dim3(256), 0, st, indptr, indices, static_cast<const T*>(data),
+                           n, use_weights, wq.as<long long>(), keep.as<long long>(), flg.as<unsigned>(), sums);
+    });
     HIP_TRY(hipGetLastError());
     unsigned long long h[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h, flg.p, 24, hipMemcpyDeviceToHost, st));
