@@ -745,6 +745,28 @@ int icv_profile_corr(const icv_matrix *m, const double *profiles_t, const double
 int icv_profile_corr_best(const double *r, int64_t n_rows, int64_t n_profiles, double *best_r, int32_t *best_g,
                           void *stream);
 
+/* ---- tl.cnv_changepoints: exact penalised least-squares segmentation of every chromosome of every row ---
+ * icv_changepoint_levels: m and chr_start as for icv_states_viterbi (stored values are used as float64, an entry that is
+ * not stored is 0.0; CSR columns need not be sorted; a column outside [0, n_cols) is passed over), except that n_cols has
+ * no limit: one wavefront runs one (row, chromosome) and keeps 28 bytes of LDS per window of the chromosome, so every
+ * chromosome has at most ICV_CHANGEPOINT_MAX_CHR_WINDOWS windows and n_rows x n_chr <= 2^31 - 1 (ICV_ERR_UNSUPPORTED
+ * beyond).  Per row and chromosome with the values x_1 .. x_L: P_0 = Q_0 = +0.0, P_j = P_{j-1} + x_j,
+ * Q_j = Q_{j-1} + x_j x_j; the cost of the segment (i, j] is c = (Q_j - Q_i) - (d d) / (double)(j - i) with d = P_j - P_i,
+ * a c < 0.0 becomes 0.0; F_0 = 0.0 and F_j = the smallest ((F_i + c) + beta) over the i with (i == 0 or i >= min_windows)
+ * and j - i >= min_windows, ties to the lowest i (i = 0 always counts for j = L; a j without such an i has F_j = +inf and
+ * is never chosen); the backtrack from L gives the segments, each with the level (P_j - P_i) / (double)(j - i).  levels
+ * (device float64, n_rows x n_cols) receives the level of every window's segment and starts (device uint8, the same
+ * shape) 1 at the first window of every segment, 0 elsewhere.  Every operation is a correctly rounded float64 one in the
+ * written order: a pure function of the arguments.  beta is finite and >= 0, min_windows >= 1.
+ * icv_changepoint_diffsq: d[i] (device float64, n_rows) = the sum over the chromosomes in ascending order, from +0.0, of
+ * each chromosome's sum, from +0.0 and in ascending order, of (x_{t+1} - x_t)^2 over its adjacent windows.
+ * Both copy the n_chr + 1 starts to the host to size the launch (one synchronisation of the stream) and return
+ * ICV_ERR_INVALID unless they ascend from 0 to n_cols with no chromosome above the cap. */
+#define ICV_CHANGEPOINT_MAX_CHR_WINDOWS 4096
+int icv_changepoint_levels(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, double beta, int32_t min_windows,
+                           double *levels, uint8_t *starts, void *stream);
+int icv_changepoint_diffsq(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, double *d, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -1897,14 +1897,14 @@ def flag_and_absmax(flag, absmax):
 def _hmm_call(entry, dm: DeviceMatrix, chr_start, scalars, outputs):
     """The call shape of the three chain kernels: ``chr_start`` (host int32 array of C + 1 ascending window numbers from 0
     to W) is uploaded, ``outputs(torch)`` allocates the tuple of result tensors (None for one that is not wanted) on
-    ``dm``'s device, and ``entry(matrix, chr_start, C, *scalars, *outputs, stream)`` is enqueued on the current stream.
-    Returns the outputs; nothing is read back."""
+    ``dm``'s device, and ``entry(matrix, chr_start, C, *scalars, *outputs, stream)`` is enqueued on the current stream
+    (a scalar that is an int is passed as one, every other as a float).  Returns the outputs; nothing is read back."""
     torch = _torch()
     with torch.cuda.device(dm.device):
         cs, n_chr = _chr_start_upload(torch, chr_start)
         out = outputs(torch)
         m = dm.c_struct()
-        _lib.check(entry(C.byref(m), _ptr(cs), n_chr, *(float(v) for v in scalars),
+        _lib.check(entry(C.byref(m), _ptr(cs), n_chr, *(v if isinstance(v, int) else float(v) for v in scalars),
                          *(_ptr(t) for t in out), _stream_ptr(torch)))
     return out
 
@@ -1927,6 +1927,24 @@ def states_fraction(count, n_windows):
         out = torch.empty(count.shape[0], dtype=torch.float64, device="cuda")
         _lib.check(lib.icv_states_fraction(_ptr(count), count.shape[0], int(n_windows), _ptr(out), _stream_ptr(torch)))
     return out
+
+
+def changepoint_levels(dm: DeviceMatrix, chr_start, *, beta, min_windows):
+    """(levels, starts, n_segments): device float64 ``n x W`` level of every window's segment, device uint8 ``n x W`` with 1
+    at the first window of every segment, and their integer row sums as device int32 (DESIGN.md 4.19 rules 1-5).
+    ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W, no chromosome above
+    ``ICV_CHANGEPOINT_MAX_CHR_WINDOWS``.  Enqueued on the current stream; no result is read back."""
+    n, w = dm.shape
+    levels, starts = _hmm_call(_lib.load().icv_changepoint_levels, dm, chr_start, (beta, int(min_windows)), lambda torch: (
+        torch.empty((n, w), dtype=torch.float64, device="cuda"), torch.empty((n, w), dtype=torch.uint8, device="cuda")))
+    return levels, starts, starts.sum(dim=1, dtype=_torch().int32)
+
+
+def changepoint_diffsq(dm: DeviceMatrix, chr_start):
+    """Device float64 vector of the ``d_r`` of DESIGN.md 4.19 rule 6: per row the sum over the chromosomes, in ascending
+    order, of each chromosome's chain of squared differences of adjacent windows.  No result is read back."""
+    return _hmm_call(_lib.load().icv_changepoint_diffsq, dm, chr_start, (), lambda torch: (
+        _empty(torch, dm.shape[0], torch.float64),))[0]
 
 
 # ---- tl.cnv_posteriors / tl.cnv_states_filter: forward-backward chains and the posterior filter (DESIGN.md 4.15) --------

@@ -49,6 +49,7 @@
 #include "icv_posterior.hpp"
 #include "icv_pseudobulk.hpp"
 #include "icv_profile_corr.hpp"
+#include "icv_changepoint.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -4280,6 +4281,90 @@ int icv_profile_corr_best(const double* r, int64_t n_rows, int64_t n_profiles, d
     if ((n_rows + 255) / 256 > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "profile_corr_best: too many rows for one call");
     hipLaunchKernelGGL(icv::k_profile_corr_best, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), r, n_rows, n_profiles, best_r, best_g);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_changepoints: exact penalised segmentation of every chromosome of every row -------------------
+static_assert(icv::kCpMaxChrWindows == ICV_CHANGEPOINT_MAX_CHR_WINDOWS, "the header's chromosome cap is the kernel's");
+static_assert((size_t)(icv::kCpMaxChrWindows + 1) * icv::kCpLdsPerWindow <= (size_t)icv::kLdsLimit,
+              "one chromosome fits a CU's LDS");
+
+}  // extern "C"
+
+namespace {
+
+// What icv_changepoint_levels and icv_changepoint_diffsq check and do alike.  who: the entry point without icv_; ok: its
+// verdict on its own arguments.  The n_chr + 1 starts are copied to the host (the one synchronisation of the stream) and must
+// be ascending from 0 to n_cols with no chromosome above the cap; *longest receives the longest chromosome, which sizes the
+// launch's LDS.  ICV_OK with *longest = 0: no rows, nothing to launch.
+int cp_check(const std::string& who, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, bool ok, hipStream_t st,
+             int32_t* longest) {
+    *longest = 0;
+    if (!matrix_header_ok(m) || !chr_start || !ok || n_chr < 1 || m->n_cols < 1 || (m->format == ICV_DENSE && m->ld < m->n_cols))
+        return fail(ICV_ERR_INVALID, "bad " + who + " arguments");
+    if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, who + ": more chromosomes than windows");
+    if (m->n_rows == 0) return ICV_OK;
+    if (!matrix_complete(m)) return fail(ICV_ERR_INVALID, who + ": incomplete matrix");
+    if (m->n_rows > kSegMaxBlocks / n_chr)
+        return fail(ICV_ERR_UNSUPPORTED, who + ": more than 2^31 - 1 rows x chromosomes in one call");
+    std::vector<int32_t> cs((size_t)n_chr + 1);
+    HIP_TRY(hipMemcpyAsync(cs.data(), chr_start, cs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (cs.front() != 0 || cs.back() != m->n_cols)
+        return fail(ICV_ERR_INVALID, who + ": chr_start must run from 0 to n_cols");
+    for (int32_t c = 0; c < n_chr; ++c) {
+        if (cs[c + 1] < cs[c]) return fail(ICV_ERR_INVALID, who + ": chr_start must be ascending");
+        const int32_t len = cs[c + 1] - cs[c];
+        if (len > ICV_CHANGEPOINT_MAX_CHR_WINDOWS)
+            return fail(ICV_ERR_INVALID, who + ": a chromosome of " + std::to_string(len) + " windows is above " +
+                                             std::to_string(ICV_CHANGEPOINT_MAX_CHR_WINDOWS) + " (" +
+                                             std::to_string(icv::kCpLdsPerWindow) + " bytes of LDS per window)");
+        *longest = std::max(*longest, len);
+    }
+    return ICV_OK;
+}
+
+// one wavefront per (row, chromosome) with lds bytes of dynamic LDS; pick and args as for hmm_launch
+template <typename Pick, typename... Args>
+int cp_launch(Pick pick, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, size_t lds, hipStream_t st, Args... args) {
+    return by_matrix(m, [&](auto t, auto csr) {
+        auto kern = pick(t, csr);
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)(m->n_rows * n_chr)), dim3(64), lds, st, (const decltype(t)*)m->values,
+                           m->indptr, m->indices, m->ld, m->n_cols, chr_start, n_chr, args...);
+        HIP_TRY(hipGetLastError());
+        return (int)ICV_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int icv_changepoint_levels(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, double beta, int32_t min_windows,
+                           double* levels, uint8_t* starts, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t longest = 0;
+    ICV_TRY(cp_check("changepoint_levels", m, chr_start, n_chr,
+                     levels && starts && std::isfinite(beta) && beta >= 0.0 && min_windows >= 1, st, &longest));
+    if (longest == 0) return ICV_OK;
+    // (a min_windows above the longest chromosome acts as longest + 1: every chromosome is one segment)
+    return cp_launch([](auto t, auto csr) { return icv::k_changepoint_levels<decltype(t), decltype(csr)::value>; }, m,
+                     chr_start, n_chr, icv::cp_lds_bytes(longest), st, longest, beta, std::min(min_windows, longest + 1), levels, starts);
+}
+
+int icv_changepoint_diffsq(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, double* d, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t longest = 0;
+    ICV_TRY(cp_check("changepoint_diffsq", m, chr_start, n_chr, d != nullptr, st, &longest));
+    if (longest == 0) return ICV_OK;
+    AsyncBuf e;
+    HIP_TRY(e.alloc((size_t)m->n_rows * (size_t)n_chr * sizeof(double), st));
+    ICV_TRY(cp_launch([](auto t, auto csr) { return icv::k_changepoint_diffsq<decltype(t), decltype(csr)::value>; }, m,
+                      chr_start, n_chr, (size_t)longest * 16, st, longest, e.as<double>()));
+    hipLaunchKernelGGL(icv::k_changepoint_rowsum, dim3((unsigned)((m->n_rows + 255) / 256)), dim3(256), 0, st, e.as<double>(),
+                       m->n_rows, n_chr, d);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }

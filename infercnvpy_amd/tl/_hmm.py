@@ -19,33 +19,33 @@ import numpy as np
 from .. import _engine
 
 
-def chromosome_bounds(chr_pos, n_windows):
+def chromosome_bounds(chr_pos, n_windows, who="tl.cnv_states"):
     """int32 array of C + 1 window numbers: the sorted starts of ``chr_pos`` followed by ``n_windows``.
 
     ``ValueError`` for a start that is not an integer inside ``[0, n_windows)``, duplicate starts, an empty table or no
-    chromosome starting at window 0 (every window belongs to exactly one chromosome)."""
+    chromosome starting at window 0 (every window belongs to exactly one chromosome); ``who`` prefixes the message."""
     try:
         raw = list(chr_pos.values())
     except AttributeError:
-        raise ValueError("tl.cnv_states: chr_pos must map chromosome names to their first window") from None
+        raise ValueError(f"{who}: chr_pos must map chromosome names to their first window") from None
     if not raw:
-        raise ValueError("tl.cnv_states: chr_pos is empty")
+        raise ValueError(f"{who}: chr_pos is empty")
     starts = []
     for v in raw:
         try:
             i = int(v)
         except (TypeError, ValueError):
-            raise ValueError(f"tl.cnv_states: chr_pos start {v!r} is not an integer") from None
+            raise ValueError(f"{who}: chr_pos start {v!r} is not an integer") from None
         if isinstance(v, bool) or i != v:
-            raise ValueError(f"tl.cnv_states: chr_pos start {v!r} is not an integer")
+            raise ValueError(f"{who}: chr_pos start {v!r} is not an integer")
         if not 0 <= i < n_windows:
-            raise ValueError(f"tl.cnv_states: chr_pos start {i} is outside [0, {n_windows})")
+            raise ValueError(f"{who}: chr_pos start {i} is outside [0, {n_windows})")
         starts.append(i)
     starts.sort()
     if any(a == b for a, b in zip(starts, starts[1:])):
-        raise ValueError("tl.cnv_states: two chromosomes of chr_pos start at the same window")
+        raise ValueError(f"{who}: two chromosomes of chr_pos start at the same window")
     if starts[0] != 0:
-        raise ValueError("tl.cnv_states: no chromosome of chr_pos starts at window 0")
+        raise ValueError(f"{who}: no chromosome of chr_pos starts at window 0")
     return np.asarray(starts + [int(n_windows)], dtype=np.int32)
 
 
