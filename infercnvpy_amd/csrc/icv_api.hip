@@ -1606,8 +1606,10 @@ int gene_from_windows(icv_plan_t pl, const double* win, int64_t ldw, int64_t n, 
     HIP_TRY(b_med.alloc((size_t)n * sizeof(double), st));
     double *gv = b_gv.as<double>(), *med = b_med.as<double>();
     {
-        const int64_t total = n * ldg;
-        hipLaunchKernelGGL(icv::k_fill_nan, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gene_out, total);
+        const int64_t total = n * (int64_t)p.n_cols_all;
+        if (total > 0)
+            hipLaunchKernelGGL(icv::k_fill_nan, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gene_out, n,
+                               (int64_t)p.n_cols_all, ldg);
     }
     if (n_cov > 0) {
         for (int64_t r0 = 0; r0 < n; r0 += 32768) {

@@ -1534,9 +1534,10 @@ __global__ void __launch_bounds__(256) k_gene_finish(const double* gv, const dou
     out[cell * ldg + cov_col[q]] = v;
 }
 
-__global__ void __launch_bounds__(256) k_fill_nan(double* out, int64_t n) {
+// (the n_cols columns of every row only: `out` may be a view into a wider buffer, ld > n_cols)
+__global__ void __launch_bounds__(256) k_fill_nan(double* out, int64_t n_rows, int64_t n_cols, int64_t ld) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = __builtin_nan("");
+    if (i < n_rows * n_cols) out[(i / n_cols) * ld + i % n_cols] = __builtin_nan("");
 }
 
 // ---------------------------------------------------------------------------------------
