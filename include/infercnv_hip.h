@@ -295,12 +295,7 @@ int icv_gene_values(icv_plan_t plan, const icv_matrix *m, const void *ref_lo, co
                     double lfc_clip, int32_t flags, const double *thr, int64_t chunksize,
                     int64_t row_phase, double *gene_out, int64_t ldg, void *stream);
 
-/* ---- CSR packing of X_cnv (reference :455 `csr_matrix(x_res)`, :137 vstack) ------------------
- * Two steps around a caller-side prefix sum: count the non-zeros of every row of the dense float32
- * result, then write column indices (int32) and values (float64) at indptr[row]. */
-int icv_csr_count(const float *x, int64_t n_rows, int32_t n_cols, int64_t ld, int64_t *row_nnz, void *stream);
-int icv_csr_fill(const float *x, int64_t n_rows, int32_t n_cols, int64_t ld, const int64_t *indptr,
-                 int32_t *indices, double *data, void *stream);
+/* ---- CSR packing of X_cnv (reference :455 `csr_matrix(x_res)`, :137 vstack) ------------------ */
 
 /* Geometry of the streamed pack kernels for rows of n_windows float32 (host logic, no GPU needed): whether
  * icv_threshold_mask / icv_csr_fill_masked take the LDS-ring kernels at this width (given aligned rows), how the 160 KB
@@ -340,19 +335,6 @@ int icv_csr_fill_masked(const float *x, int64_t n_rows, int32_t n_cols, int64_t 
 /* the prefix sum between the two: indptr[0] = 0, indptr[r + 1] = row_nnz[0] + ... + row_nnz[r] (device arrays; two
  * launches over blocks of 4 096 rows, 8 bytes of temporary device memory per block) */
 int icv_row_offsets(const int64_t *row_nnz, int64_t n_rows, int64_t *indptr, void *stream);
-
-/* Step 5b and the packing in ONE pass (kept for comparison: 0.7 ms per 100 000 cells of config 2 against 0.33 ms for
- * the three calls above, profiles/r04_pack_experiments.txt): the decision of
- * icv_threshold_mask, the rows' offsets from a two-level decoupled look-back over the rows (no mask array, no prefix-sum call,
- * no second kernel) and the kept entries written from the row: x_res is read from HBM once.  `indptr` n_rows + 1
- * offsets starting at 0; `indices` / `data` hold `capacity` entries (n_rows * n_windows can never overflow; entries
- * past the capacity are dropped, indptr[n_rows] still tells how many there are).  Deterministic: the output does not
- * depend on the order in which the rows finish.  At most 20 480 windows (ICV_ERR_UNSUPPORTED beyond: use the
- * two-step form).  Needs less than n_rows bytes of temporary device memory (stream-ordered). */
-int icv_threshold_pack(icv_plan_t plan, const icv_matrix *m, const void *ref_lo, const void *ref_hi, double lfc_clip,
-                       int32_t flags, const float *out, int64_t ldo, const double *cell_median, const double *thr,
-                       int64_t chunksize, int64_t row_phase, int64_t *indptr, int32_t *indices, double *data,
-                       int64_t capacity, void *stream);
 
 /* ---- ithcna / ithgex (tl/_scores.py:77-221) -------------------------------------------------
  * Interquartile range of all n x n entries of np.corrcoef(x) for one group of cells: x is a dense
@@ -793,7 +775,7 @@ int icv_csr_scatter_dense(const void *data, int32_t dtype, const int64_t *indptr
 /* ---- misc --------------------------------------------------------------------------------- */
 const char *icv_last_error(void);
 int icv_version(void);
-/* The developer knobs (environment variables ICV_FORCE_GENERIC, ICV_NO_X16, ICV_NO_SD, ICV_WGS_PER_CU, ICV_WARD_IN_PLACE,
+/* The developer knobs (environment variables ICV_FORCE_GENERIC, ICV_NO_X16, ICV_NO_SD, ICV_WARD_IN_PLACE,
  * ICV_WARD_COMPACT_X, ICV_PHASE_PROFILE: kernel routes / geometries for A/B timing and kernel-against-kernel tests) are
  * read once, at the first dispatch; a process that changes them afterwards calls this to have them read again. */
 void icv_developer_knobs_reload(void);

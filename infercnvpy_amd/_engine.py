@@ -817,15 +817,13 @@ class PackedCsr:
 
 
 def threshold_csr(plan: GenePlan, dm: DeviceMatrix, ref_lo, ref_hi, res, *, lfc_clip, chunksize, row_phase=0,
-                  flags=0, row0=0, row1=None, capacity=None, single_pass=False):
+                  flags=0, row0=0, row1=None):
     """Step 5b + ``csr_matrix(x_res)`` (reference :449-455) on the device without a host round trip: the un-thresholded
-    ``res.out`` of :func:`run_hot_path` (``apply=False``) -> :class:`PackedCsr`.  ``capacity`` (entries) defaults to the
+    ``res.out`` of :func:`run_hot_path` (``apply=False``) -> :class:`PackedCsr`.  The entry buffers hold the
     worst case rows x windows; nothing is read back, the call is asynchronous.
 
-    Default: keep-mask + row counts (``icv_threshold_mask``: ``k_thr_mask_ring``, x_res streamed through an LDS ring),
-    ``icv_row_offsets``, ``icv_csr_fill_masked`` (``k_csr_fill_ring``) -- 0.33 ms per 100 000 cells.
-    ``single_pass=True``: ``icv_threshold_pack`` (one kernel with a decoupled look-back; 0.7 ms, kept for comparison --
-    profiles/r04_pack_experiments.txt)."""
+    Keep-mask + row counts (``icv_threshold_mask``: ``k_thr_mask_ring``, x_res streamed through an LDS ring),
+    ``icv_row_offsets``, ``icv_csr_fill_masked`` (``k_csr_fill_ring``) -- 0.33 ms per 100 000 cells."""
     torch = _torch()
     lib = _lib.load()
     rows = res.out.shape[0]
@@ -833,14 +831,9 @@ def threshold_csr(plan: GenePlan, dm: DeviceMatrix, ref_lo, ref_hi, res, *, lfc_
     if (dm.shape[0] if row1 is None else row1) - row0 == 0:  # an empty shard packs to an empty matrix
         return PackedCsr(torch.zeros(1, dtype=torch.int64, device="cuda"), torch.empty(1, dtype=torch.int32, device="cuda"),
                          torch.empty(1, dtype=torch.float64, device="cuda"), W, res.thr)
-    if single_pass and W <= 20480:
-        return threshold_pack(plan, dm, ref_lo, ref_hi, res, lfc_clip=lfc_clip, chunksize=chunksize,
-                              row_phase=row_phase, flags=flags, row0=row0, row1=row1, capacity=capacity)
     part = threshold_mask(plan, dm, ref_lo, ref_hi, res, lfc_clip=lfc_clip, chunksize=chunksize, row_phase=row_phase,
                           flags=flags, row0=row0, row1=row1)
-    # (the fill kernels write at the row offsets without a bound: never less than the worst case here; a smaller
-    # ``capacity`` is honoured by the single-pass form only, which drops the overflow)
-    cap = rows * W if capacity is None else max(int(capacity), rows * W)
+    cap = rows * W  # (the fill kernels write at the row offsets without a bound: the worst case)
     indptr = torch.empty(rows + 1, dtype=torch.int64, device="cuda")
     indices = torch.empty(max(cap, 1), dtype=torch.int32, device="cuda")
     data = torch.empty(max(cap, 1), dtype=torch.float64, device="cuda")
@@ -850,42 +843,6 @@ def threshold_csr(plan: GenePlan, dm: DeviceMatrix, ref_lo, ref_hi, res, *, lfc_
         _lib.check(lib.icv_csr_fill_masked(_ptr(part.out), rows, W, part.out.stride(0), _ptr(part.mask), _ptr(indptr),
                                            _ptr(indices), _ptr(data), st))
     return PackedCsr(indptr, indices, data, W, res.thr)
-
-
-def threshold_pack(plan: GenePlan, dm: DeviceMatrix, ref_lo, ref_hi, res, *, lfc_clip, chunksize, row_phase=0,
-                   flags=0, row0=0, row1=None, capacity=None):
-    """The single-pass form (``icv_threshold_pack``, at most 20 480 windows): see :func:`threshold_csr`."""
-    torch = _torch()
-    lib = _lib.load()
-    rows = res.out.shape[0]
-    W = plan.n_windows
-    cap = rows * W if capacity is None else int(capacity)
-    indptr = torch.empty(rows + 1, dtype=torch.int64, device="cuda")
-    indices = torch.empty(max(cap, 1), dtype=torch.int32, device="cuda")
-    data = torch.empty(max(cap, 1), dtype=torch.float64, device="cuda")
-    m = dm.c_struct(row0, row1)
-    _lib.check(lib.icv_threshold_pack(
-        plan.handle, C.byref(m), _ptr(ref_lo), _ptr(ref_hi), float(lfc_clip), int(flags), _ptr(res.out),
-        res.out.stride(0), _ptr(res.cell_median), _ptr(res.thr), int(chunksize), int(row_phase), _ptr(indptr),
-        _ptr(indices), _ptr(data), cap, _stream_ptr(torch)))
-    return PackedCsr(indptr, indices, data, W, res.thr)
-
-
-def fill_from_mask(part, n_cols):
-    """Two-step packing of a :class:`PackedRows` keep-mask (window lists too long for ``icv_threshold_pack``):
-    prefix sum, read-back of the count, ``icv_csr_fill_masked`` -> :class:`PackedCsr`."""
-    torch = _torch()
-    lib = _lib.load()
-    n = part.counts.shape[0]
-    ip = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-    torch.cumsum(part.counts, 0, out=ip[1:])
-    nnz = int(ip[-1].item())
-    idx = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
-    dat = torch.empty(max(nnz, 1), dtype=torch.float64, device="cuda")
-    if nnz:
-        _lib.check(lib.icv_csr_fill_masked(_ptr(part.out), n, n_cols, part.out.stride(0), _ptr(part.mask), _ptr(ip),
-                                           _ptr(idx), _ptr(dat), _stream_ptr(torch)))
-    return PackedCsr(ip, idx, dat, n_cols, part.thr)
 
 
 def concat_packed(parts):
@@ -1020,12 +977,11 @@ def release_pinned_buffers():
 class CsrDrain:
     """CSR pack + copy back of finished pieces on a side stream while the caller computes the next ones.
 
-    ``submit(part)`` (a :class:`PackedCsr` -- the piece packed on the device by ``icv_threshold_pack`` -- or a
-    :class:`PackedRows` mask for the two-step form; consecutive row ranges in order) returns at once, or blocks while
-    ``max_pending`` pieces are still queued (a packed piece holds a worst-case buffer).  A helper thread waits for the
-    piece on its own stream, reads the row offsets back and copies the packed entries into the final host arrays (sized
-    from the first piece's density, grown if that was too small).  ``finish()`` returns the scipy CSR matrix of all
-    rows."""
+    ``submit(part)`` (a :class:`PackedCsr`: the piece packed on the device by :func:`threshold_csr`; consecutive row
+    ranges in order) returns at once, or blocks while ``max_pending`` pieces are still queued (a packed piece holds a
+    worst-case buffer).  A helper thread waits for the piece on its own stream, reads the row offsets back and copies
+    the packed entries into the final host arrays (sized from the first piece's density, grown if that was too small).
+    ``finish()`` returns the scipy CSR matrix of all rows."""
 
     def __init__(self, n_rows, n_cols, max_pending=2):
         import queue
@@ -1045,7 +1001,6 @@ class CsrDrain:
         self.rows_done, self.nnz = 0, 0
         self.busy_seconds = 0.0
         device = torch.cuda.current_device()
-        lib = _lib.load()
         ring = None if os.environ.get("ICV_NO_PINNED_D2H") else _PinnedRing.get(torch)  # knob: A/B timing
         self._pending = []  # futures of chunks on their way into indices_h / data_h
         settle = self._settle
@@ -1086,28 +1041,12 @@ class CsrDrain:
                         part, ev = item
                         t0 = time.perf_counter()
                         self._stream.wait_event(ev)
-                        if isinstance(part, PackedCsr):
-                            n = part.n_rows
-                            ip, idx_d, dat_d = part.indptr, part.indices, part.data
-                            ip_h = ip.cpu().numpy()
-                            nnz = int(ip_h[-1])
-                            if nnz > idx_d.shape[0]:
-                                raise RuntimeError(f"icv_threshold_pack: {nnz} entries for a capacity of {idx_d.shape[0]}")
-                            held = (ip, idx_d, dat_d)
-                        else:
-                            n = part.counts.shape[0]
-                            ip = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-                            torch.cumsum(part.counts, 0, out=ip[1:])
-                            ip_h = ip.cpu().numpy()
-                            nnz = int(ip_h[-1])
-                            idx_d = dat_d = None
-                            held = (part.out, part.mask, part.counts)
-                            if nnz:
-                                idx_d = torch.empty(nnz, dtype=torch.int32, device="cuda")
-                                dat_d = torch.empty(nnz, dtype=torch.float64, device="cuda")
-                                _lib.check(lib.icv_csr_fill_masked(
-                                    _ptr(part.out), n, self.n_cols, part.out.stride(0), _ptr(part.mask), _ptr(ip),
-                                    _ptr(idx_d), _ptr(dat_d), self._stream.cuda_stream))
+                        n = part.n_rows
+                        ip, idx_d, dat_d = part.indptr, part.indices, part.data
+                        ip_h = ip.cpu().numpy()
+                        nnz = int(ip_h[-1])
+                        if nnz > idx_d.shape[0]:
+                            raise RuntimeError(f"threshold_csr: {nnz} entries for a capacity of {idx_d.shape[0]}")
                         reserve(nnz, self.rows_done + n)
                         if nnz:
                             o = self.nnz
@@ -1118,12 +1057,11 @@ class CsrDrain:
                                 torch.from_numpy(self.indices_h[o:o + nnz]).copy_(idx_d[:nnz])
                                 torch.from_numpy(self.data_h[o:o + nnz]).copy_(dat_d[:nnz])
                         # the piece's buffers were allocated on the CONSUMER's stream and are read here on the drain's
-                        # (fill kernel, asynchronous copies): the caching allocator must not hand them out before this
-                        # stream is done with them
-                        for t in held:
-                            if t is not None:
-                                t.record_stream(self._stream)
-                        del idx_d, dat_d, held
+                        # (asynchronous copies): the caching allocator must not hand them out before this stream is done
+                        # with them
+                        for t in (ip, idx_d, dat_d):
+                            t.record_stream(self._stream)
+                        del idx_d, dat_d
                         self.indptr_h[self.rows_done + 1:self.rows_done + n + 1] = ip_h[1:] + self.nnz
                         self.rows_done += n
                         self.nnz += nnz
@@ -1323,24 +1261,6 @@ def gene_values_from_windows(plan: GenePlan, windows, *, thr=None, chunksize=500
         plan.handle, _ptr(windows), windows.stride(0), rows, _ptr(thr), int(chunksize), int(row_phase), _ptr(out),
         out.stride(0), _stream_ptr(torch)))
     return out
-
-
-def dense_to_host_csr(out, n_cols):
-    """Dense float32 device result -> scipy CSR float64 on the host, packed on the GPU first."""
-    torch = _torch()
-    lib = _lib.load()
-    rows = out.shape[0]
-    counts = torch.empty(rows, dtype=torch.int64, device="cuda")
-    _lib.check(lib.icv_csr_count(_ptr(out), rows, n_cols, out.stride(0), _ptr(counts), _stream_ptr(torch)))
-    indptr = torch.zeros(rows + 1, dtype=torch.int64, device="cuda")
-    torch.cumsum(counts, 0, out=indptr[1:])
-    nnz = int(indptr[-1].item())
-    indices = torch.empty(max(nnz, 1), dtype=torch.int32, device="cuda")
-    data = torch.empty(max(nnz, 1), dtype=torch.float64, device="cuda")
-    _lib.check(lib.icv_csr_fill(_ptr(out), rows, n_cols, out.stride(0), _ptr(indptr), _ptr(indices), _ptr(data),
-                                _stream_ptr(torch)))
-    return sp.csr_matrix((data[:nnz].cpu().numpy(), indices[:nnz].cpu().numpy(), indptr.cpu().numpy()),
-                         shape=(rows, n_cols))
 
 
 def corr_iqr(x):

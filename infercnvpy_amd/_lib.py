@@ -36,7 +36,7 @@ EXPORTS = (
     "icv_infercnv_run_windows", "icv_gene_values_from_windows",
     "icv_colchain_blocks_workspace", "icv_colchain_blocks_sums", "icv_colchain_blocks_records", "icv_colchain_blocks_scan",
     "icv_profile_begin", "icv_profile_collect",
-    "icv_gene_values", "icv_csr_count", "icv_csr_fill", "icv_threshold_mask", "icv_csr_fill_masked", "icv_row_offsets", "icv_pack_geometry", "icv_threshold_pack", "icv_corr_iqr",
+    "icv_gene_values", "icv_threshold_mask", "icv_csr_fill_masked", "icv_row_offsets", "icv_pack_geometry", "icv_corr_iqr",
     "icv_pairwise_sqeuclidean", "icv_ward_linkage", "icv_pairwise_sqeuclidean_tiles",
     "icv_ward_create", "icv_ward_destroy", "icv_ward_merge", "icv_ward_gather", "icv_ward_scatter", "icv_ward_scan", "icv_ward_pack_nn",
     "icv_ward_unpack_nn", "icv_ward_pairs", "icv_ward_round_pairs", "icv_ward_finish", "icv_row_abs_sum", "icv_csr_row_abs_sum", "icv_group_sums", "icv_csr_check", "icv_csr_densify", "icv_gram_f64", "icv_project", "icv_host_dense_row_nnz", "icv_host_dense_pack", "icv_host_dense_pack_fused", "icv_csr_scatter_dense", "icv_last_error", "icv_version",
@@ -138,10 +138,7 @@ def load():
     lib.icv_profile_begin.argtypes = [vp]
     lib.icv_profile_collect.argtypes = [vp, P(Profile), i32, P(i32)]
     lib.icv_gene_values.argtypes = [vp, P(Matrix), vp, vp, dbl, i32, vp, i64, i64, vp, i64, vp]
-    lib.icv_csr_count.argtypes = [vp, i64, i32, i64, vp, vp]
-    lib.icv_csr_fill.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp]
     lib.icv_threshold_mask.argtypes = [vp, P(Matrix), vp, vp, dbl, i32, vp, i64, vp, vp, i64, i64, vp, vp, vp]
-    lib.icv_threshold_pack.argtypes = [vp, P(Matrix), vp, vp, dbl, i32, vp, i64, vp, vp, i64, i64, vp, vp, vp, i64, vp]
     lib.icv_row_offsets.argtypes = [vp, i64, vp, vp]
     lib.icv_pack_geometry.argtypes = [i32, P(PackInfo)]
     lib.icv_csr_fill_masked.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, vp]

@@ -97,9 +97,8 @@ bool matrix_complete(const icv_matrix* m) { return m->format == ICV_DENSE ? m->v
 // getenv per dispatch, and a production call's route must not follow an environment edited under it); a test that
 // changes them calls icv_developer_knobs_reload().
 struct Knobs {
-    bool force_generic, no_x16, no_sd, phase_profile, ward_in_place, no_mask_ring, no_fill_ring, no_chain_queues, se_maxw4,
+    bool force_generic, no_x16, no_sd, phase_profile, ward_in_place, no_mask_ring, no_fill_ring, no_chain_queues,
          no_gene_fused;
-    int wgs_per_cu;        // 0 = not set
     int chain_far;         // ICV_CHAIN_FAR: entries a buffer offset may span in k_colchain_csrq (tests: a small value)
     int chain_pieces;      // ICV_CHAIN_PIECES: lanes per row of k_colchain_csrq (2 / 4 / 8 / 16; 0 = from the density)
     double ward_compact_x; // 0 = not set
@@ -112,11 +111,8 @@ struct Knobs {
         no_mask_ring = std::getenv("ICV_NO_MASK_RING") != nullptr;
         no_fill_ring = std::getenv("ICV_NO_FILL_RING") != nullptr;
         no_chain_queues = std::getenv("ICV_NO_CHAIN_QUEUES") != nullptr;
-        se_maxw4 = std::getenv("ICV_SE_MAXW4") != nullptr;
         no_gene_fused = std::getenv("ICV_NO_GENE_FUSED") != nullptr;  // gene values through the three round-1 kernels
-        const char* e = std::getenv("ICV_WGS_PER_CU");
-        wgs_per_cu = e ? std::atoi(e) : 0;
-        e = std::getenv("ICV_CHAIN_FAR");
+        const char* e = std::getenv("ICV_CHAIN_FAR");
         chain_far = e ? std::atoi(e) : 0;
         e = std::getenv("ICV_CHAIN_PIECES");
         chain_pieces = e ? std::atoi(e) : 0;
@@ -639,7 +635,7 @@ SmoothKernel x16_kernel(const icv::Plan& p, bool chunk, bool win) {
 // 1 472), else 4; entry slots per thread from the mean row length: PF x 512 slots should hold mean + 4 sigma (binomial)
 // entries -- longer rows take the in-phase loop, any PF gives the same bits
 SmoothKernel se_kernel(const icv::Plan& p, const icv_matrix* m, bool bounded, bool chunk, bool win) {
-    const bool w3 = p.W <= 3 * icv::NT && !knobs().se_maxw4;
+    const bool w3 = p.W <= 3 * icv::NT;
     if (win) {
         // calculate_gene_values: the float64 windows leave the kernel as well (four entry slots per thread whatever
         // the row length: any slot count gives the same bits, and this path is bound by the cells x genes output)
@@ -651,7 +647,7 @@ SmoothKernel se_kernel(const icv::Plan& p, const icv_matrix* m, bool bounded, bo
         return bounded ? icv::k_smooth_se<4, false, true> : icv::k_smooth_se<4, false, false>;
     }
     int pf = 4;
-    if (!knobs().se_maxw4 && m->n_rows > 0) {
+    if (m->n_rows > 0) {
         double want = 0.0;
         if (m->_pad > 0) {
             want = (double)m->_pad;  // the caller's figure: the length most rows stay under (icv_matrix._pad)
@@ -709,8 +705,6 @@ SmoothRoute pick_route(const icv_plan_t pl, const icv_matrix* m, const icv::KPar
     const bool want_win = K.win_out != nullptr, csr = m->format == ICV_CSR;
     const bool fast_allowed = m->dtype == ICV_F32 && std::isfinite(K.cap) && !kn.force_generic;
     const bool win_ok = !want_win || want_chunk_moments;  // the x16 / se instantiations that write windows form chunk moments
-    // ICV_WGS_PER_CU: developer knob for occupancy experiments
-    auto knob_per_cu = [&](int per_cu) { return kn.wgs_per_cu >= 1 && kn.wgs_per_cu < per_cu ? kn.wgs_per_cu : per_cu; };
     if (fast_allowed && !csr && p.ws_ok && K.vec_ok) {
         // ICV_NO_X16=1: developer knob, the previous generation
         const SmoothKernel xk = (K.bounded || kn.no_x16) ? nullptr : x16_kernel(p, want_chunk_moments, want_win);
@@ -728,7 +722,7 @@ SmoothRoute pick_route(const icv_plan_t pl, const icv_matrix* m, const icv::KPar
             r.kind = ICV_KERNEL_WS;
             r.kern = ws_kernel(p, false);
             r.lds = p.fast_lds;
-            r.grid = cu_grid(pl, knob_per_cu(std::min(icv::kLdsLimit / r.lds, 4)), K.n_rows);
+            r.grid = cu_grid(pl, std::min(icv::kLdsLimit / r.lds, 4), K.n_rows);
             return r;
         }
     }
@@ -737,7 +731,7 @@ SmoothRoute pick_route(const icv_plan_t pl, const icv_matrix* m, const icv::KPar
             r.kind = ICV_KERNEL_SD;
             r.kern = se_kernel(p, m, K.bounded != 0, want_chunk_moments, want_win);
             r.lds = icv::kSeLds;
-            r.grid = cu_grid(pl, knob_per_cu(icv::kLdsLimit / icv::kSeLds), K.n_rows);  // workgroups per CU from its LDS map
+            r.grid = cu_grid(pl, icv::kLdsLimit / icv::kSeLds, K.n_rows);  // workgroups per CU from its LDS map
             r.moment_slots = want_chunk_moments ? r.grid * icv::NWAVE : 0;
             r.writes_windows = want_win;
             return r;
@@ -746,7 +740,7 @@ SmoothRoute pick_route(const icv_plan_t pl, const icv_matrix* m, const icv::KPar
             r.kind = ICV_KERNEL_WS_CSR;
             r.kern = ws_kernel(p, true);
             r.lds = p.fast_lds;
-            r.grid = cu_grid(pl, knob_per_cu(std::min(icv::kLdsLimit / r.lds, 4)), K.n_rows);
+            r.grid = cu_grid(pl, std::min(icv::kLdsLimit / r.lds, 4), K.n_rows);
             return r;
         }
     }
@@ -1079,7 +1073,7 @@ int colchain_csr(const icv_matrix* m, const int32_t* rows, int64_t n_sel, double
 extern "C" {
 
 const char* icv_last_error(void) { return g_err.c_str(); }
-int icv_version(void) { return 100; }
+int icv_version(void) { return 101; }
 
 void icv_developer_knobs_reload(void) {
     std::lock_guard<std::mutex> lk(g_knobs_mu);
@@ -1779,52 +1773,6 @@ int icv_threshold_mask(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, c
     return ICV_OK;
 }
 
-int icv_threshold_pack(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void* ref_hi, double lfc_clip,
-                       int32_t flags, const float* out, int64_t ldo, const double* cell_median, const double* thr,
-                       int64_t chunksize, int64_t row_phase, int64_t* indptr, int32_t* indices, double* data,
-                       int64_t capacity, void* stream) {
-    int rc = check_matrix(pl, m);
-    if (rc) return rc;
-    PLAN_BUSY_GUARD(pl);
-    if (!cell_median || !indptr || !indices || !data || capacity < 0 || !chunk_args_ok(thr, chunksize, row_phase))
-        return fail(ICV_ERR_INVALID, "bad threshold_pack arguments");
-    if (pl->p.W > 320 * 64) return fail(ICV_ERR_UNSUPPORTED, "icv_threshold_pack: more than 20480 windows");
-    // rows per workgroup (= per look-back ticket): as many as keep their mask words in the workgroup's LDS, at most 16
-    const int n_words = (pl->p.W + 63) / 64;
-    int rpw = icv::kPackWords / n_words;
-    rpw = rpw < 1 ? 1 : (rpw > icv::kPackMaxRows ? icv::kPackMaxRows : rpw);
-    if ((rc = ensure_device(pl))) return rc;
-    PLAN_ENTER(stream);
-    icv::KParams K;
-    const icv::Layout* lay;
-    if ((rc = fill_params(pl, m, ref_lo, ref_hi, lfc_clip, flags, const_cast<float*>(out), ldo,
-                          const_cast<double*>(cell_median), nullptr, K, lay)))
-        return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (K.n_rows < 1) {
-        HIP_TRY(hipMemsetAsync(indptr, 0, sizeof(int64_t), st));
-        return ICV_OK;
-    }
-    if (K.n_rows > 0xffffffffll) return fail(ICV_ERR_UNSUPPORTED, "icv_threshold_pack: more than 2^32 rows per call");
-    // look-back workspace: one status word per ticket, two per group of 64 tickets, the ticket counter; zeroed in
-    // stream order
-    const int64_t n_tickets = (K.n_rows + rpw - 1) / rpw, n_groups = (n_tickets + 63) / 64;
-    AsyncBuf ws;
-    HIP_TRY(ws.alloc((size_t)(n_tickets + 2 * n_groups + 1) * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(ws.p, 0, (size_t)(n_tickets + 2 * n_groups + 1) * sizeof(unsigned long long), st));
-    auto* status = ws.as<unsigned long long>();
-    auto* gstat = status + n_tickets;
-    auto* gacc = gstat + n_groups;
-    auto* ticket = reinterpret_cast<unsigned int*>(gacc + n_groups);
-    const int64_t cs = thr ? chunksize : 1;
-    by_matrix(m, [&](auto t, auto csr) {
-        hipLaunchKernelGGL((icv::k_thr_pack<decltype(t), decltype(csr)::value>), dim3((unsigned)n_tickets), dim3(256), 0, st, K,
-                           thr, cs, row_phase, rpw, ticket, status, gstat, gacc, indptr, indices, data, capacity);
-    });
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
-}
-
 int icv_pack_geometry(int32_t n_windows, icv_pack_info* info) {
     if (!info || n_windows < 1) return fail(ICV_ERR_INVALID, "bad pack_geometry arguments");
     const icv::PackRing pr(n_windows);
@@ -1877,26 +1825,6 @@ int icv_csr_fill_masked(const float* x, int64_t n_rows, int32_t n_cols, int64_t 
     }
     hipLaunchKernelGGL(icv::k_csr_fill_masked, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, x, n_rows, n_cols, ld,
                        reinterpret_cast<const unsigned long long*>(mask), (n_cols + 63) / 64, indptr, indices, data);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
-}
-
-int icv_csr_count(const float* x, int64_t n_rows, int32_t n_cols, int64_t ld, int64_t* row_nnz, void* stream) {
-    if (!x || !row_nnz || n_cols < 0 || ld < n_cols) return fail(ICV_ERR_INVALID, "bad csr_count arguments");
-    if (n_rows < 1) return ICV_OK;
-    hipLaunchKernelGGL(icv::k_csr_count, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, n_rows, n_cols, ld, row_nnz);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
-}
-
-int icv_csr_fill(const float* x, int64_t n_rows, int32_t n_cols, int64_t ld, const int64_t* indptr, int32_t* indices,
-                 double* data, void* stream) {
-    if (!x || !indptr || !indices || !data || n_cols < 0 || ld < n_cols)
-        return fail(ICV_ERR_INVALID, "bad csr_fill arguments");
-    if (n_rows < 1) return ICV_OK;
-    hipLaunchKernelGGL(icv::k_csr_fill, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, n_rows, n_cols, ld, indptr, indices, data);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }

@@ -220,6 +220,15 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// 64-bit add across the lanes of a wavefront (every lane gets the total)
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
 
 // workgroup-wide sum of an int; `par` alternates between consecutive calls (no WAR hazard)
 __device__ __forceinline__ int wg_sum_i(int v, Scratch* sc, int par) {
@@ -960,217 +969,6 @@ __global__ void __launch_bounds__(256) k_thr_mask(const KParams P, const double*
     if (threadIdx.x == 0) row_nnz[cell] = (int64_t)(cnt[0] + cnt[1] + cnt[2] + cnt[3] - dropped);
 }
 
-// Step 5b + `csr_matrix(x_res)` (reference :449-455) in ONE pass over x_res: the decision of k_thr_mask, the rows' kept
-// counts, their offsets in the packed output from a decoupled look-back, and the entries (int32 column, float64 value)
-// written straight from the rows -- x_res is read from HBM once (the packing re-reads the workgroup's rows from L2),
-// no mask array in HBM, no separate scan, no second kernel.
-//   A workgroup takes `rpw` consecutive rows per ticket (ticket counter: every predecessor of a waiting workgroup is
-//   running or done).  status[t]: 64-bit word per ticket {2-bit flag, 62-bit value}: 1 = the ticket's own
-//   count, 2 = the inclusive prefix of tickets 0..t (one relaxed agent-scope 8-byte store: value and flag cannot tear).
-//   The look-back examines 64 predecessors per step and waits only for those nearer than the nearest known prefix; a
-//   step covers 64 x rpw rows.  `ticket` and `status` are zeroed by the caller.
-//   indptr[0 .. n_rows] from 0; indices / data of capacity `cap` entries: an entry beyond `cap` is dropped (the caller
-//   sizes for the worst case or checks indptr[n_rows]).  The output does not depend on the order of completion.
-constexpr unsigned long long kPackAgg = 1ull << 62, kPackPfx = 2ull << 62, kPackVal = (1ull << 62) - 1;
-constexpr int kPackWords = 1024;  // mask words per workgroup in LDS: rpw * ceil(W / 64) <= 1024
-constexpr int kPackMaxRows = 16;
-
-// 64-bit add across the lanes of a wavefront (every lane gets the total)
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
-// Wavefront 0 of a pack workgroup: offsets of the mask words inside their rows, the rows' bases (row_base[0..n_here]) and
-// the ticket's offset in the packed output from a TWO-LEVEL decoupled look-back.  Tickets form groups of 64:
-//   status[t]  = kPackAgg | count of ticket t              (read by the later tickets of the same group)
-//   gacc[g]   += (1 << 56) + count, one atomic per ticket: the ticket that completes the group publishes
-//   gstat[g]   = kPackAgg | count of group g, later kPackPfx | entries of groups 0..g (by the group's last ticket)
-// so a ticket needs ONE load for its own group and one per 64 groups (4096 tickets) behind it, however many workgroups
-// are in flight (a flat look-back walked ~28 windows of 64 tickets at 1800 resident workgroups: a third of the kernel).
-__device__ __forceinline__ void pack_lookback(int lane, int64_t tk, int64_t n_tickets, int n_here, int n_words,
-                                              const unsigned long long* mwords, int* woff, long long* row_base,
-                                              unsigned long long* status, unsigned long long* gstat,
-                                              unsigned long long* gacc, int64_t* indptr) {
-    long long run_rows = 0;
-    for (int rr = 0; rr < n_here; ++rr) {
-        int run = 0;
-        for (int w0 = 0; w0 < n_words; w0 += 64) {
-            const int cnt = w0 + lane < n_words ? __popcll(mwords[rr * n_words + w0 + lane]) : 0;
-            const int incl = wave_scan_dpp(cnt);
-            if (w0 + lane < n_words) woff[rr * n_words + w0 + lane] = run + incl - cnt;
-            run += __builtin_amdgcn_readlane(incl, 63);
-        }
-        if (lane == 0) row_base[rr] = run_rows;
-        run_rows += run;
-    }
-    const unsigned long long mine = (unsigned long long)run_rows;
-    unsigned long long excl = 0;
-#if !(defined(ICV_DEV_EXPERIMENTS) && defined(ICV_PACK_EXP_NOLOOKBACK))  // (experiment: wrong offsets on purpose)
-    const int64_t g = tk >> 6;
-    const int i = (int)(tk & 63);
-    const int in_group = (int)((n_tickets - g * 64) < 64 ? (n_tickets - g * 64) : 64);
-    if (lane == 0) {
-        __hip_atomic_store(status + tk, kPackAgg | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long old =
-            __hip_atomic_fetch_add(gacc + g, (1ull << 56) + mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((int)(old >> 56) + 1 == in_group && i != in_group - 1)  // (the group's last ticket publishes the prefix itself)
-            __hip_atomic_store(gstat + g, kPackAgg | ((old & ((1ull << 56) - 1)) + mine), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // own group: the counts of the tickets before this one
-    unsigned long long sv = kPackAgg;
-    while (true) {
-        if (lane < i) sv = __hip_atomic_load(status + g * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__builtin_amdgcn_ballot_w64((sv >> 62) == 0) == 0) break;
-        __builtin_amdgcn_s_sleep(8);
-    }
-    excl = wave_sum_u64(lane < i ? (sv & kPackVal) : 0ull);
-    // the groups before: 64 per step, up to and including the nearest one whose prefix is known
-    int64_t hi = g - 1;
-    while (hi >= 0) {
-        const int64_t r = hi - lane;
-        unsigned long long gv, pfx;
-        int first;
-        while (true) {
-            gv = r >= 0 ? __hip_atomic_load(gstat + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kPackPfx;
-            pfx = __builtin_amdgcn_ballot_w64((gv >> 62) == 2);
-            first = pfx ? __builtin_ctzll(pfx) : 64;
-            if (__builtin_amdgcn_ballot_w64(lane < first && (gv >> 62) == 0) == 0) break;
-            __builtin_amdgcn_s_sleep(8);  // pollers cost the streaming workgroups bandwidth: back off
-        }
-        excl += wave_sum_u64(lane <= first ? (gv & kPackVal) : 0ull);
-        if (pfx) break;
-        hi -= 64;
-    }
-    if (lane == 0 && i == in_group - 1)
-        __hip_atomic_store(gstat + g, kPackPfx | (excl + mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-    if (lane == 0) {
-        row_base[n_here] = run_rows;
-        if (tk == 0) indptr[0] = 0;
-    }
-    if (lane <= n_here) row_base[lane] += (long long)excl;  // (lane 0's writes above: same wavefront, in order)
-}
-
-// (Measured and dropped, profiles/r04_pack_experiments.txt: the 16 rows kept in registers between the decision and the
-// packing -- 211 VGPRs, two workgroups per CU; one wavefront per row with 16-byte loads and four ballots per 256
-// windows -- 140 VGPRs; non-temporal loads of x_res, which push the packing's second read out of L2.)
-template <typename T, bool CSR>
-__global__ void __launch_bounds__(256) k_thr_pack(const KParams P, const double* thr, int64_t chunksize,
-                                                  int64_t row_phase, int rpw, unsigned int* ticket,
-                                                  unsigned long long* status, unsigned long long* gstat,
-                                                  unsigned long long* gacc, int64_t* indptr, int32_t* indices,
-                                                  double* data, int64_t cap) {
-    __shared__ int ticket_s;
-    __shared__ unsigned long long mwords[kPackWords], twords[kPackWords];
-    __shared__ int woff[kPackWords];
-    __shared__ long long row_base[kPackMaxRows + 1];
-    if (threadIdx.x == 0) ticket_s = (int)atomicAdd(ticket, 1u);
-    __syncthreads();
-    const int64_t tk = ticket_s;
-    const int64_t cell0 = tk * rpw;
-    const int n_here = (int)((P.n_rows - cell0) < rpw ? (P.n_rows - cell0) : rpw);
-    const bool has_thr = thr != nullptr;
-    const int n_words = (P.W + 63) >> 6;
-    // ---- decide: float32 decides; a value within one ulp of the threshold is kept for now and flagged in a second mask
-    // (twords) for the exact float64 recomputation after the pass: the streaming body is a compare and two ballots.
-    // The first eight windows per thread of the NEXT row are requested before the current row is decided.
-    float nxt[8];
-    const auto request = [&](int rr) {
-        const float* orow = P.out + (cell0 + (rr < n_here ? rr : 0)) * P.ldo;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int j = u * 256 + (int)threadIdx.x;
-            nxt[u] = (rr < n_here && j < P.W) ? orow[j] : 0.0f;
-        }
-    };
-    request(0);
-    for (int rr = 0; rr < n_here; ++rr) {
-        const int64_t cell = cell0 + rr;
-        const float thf = has_thr ? (float)thr[(cell + row_phase) / chunksize] : 0.0f;
-        const float* orow = P.out + cell * P.ldo;
-        for (int j0 = 0; j0 < P.W; j0 += 8 * 256) {
-            float yv[8];
-            if (j0 == 0) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) yv[u] = nxt[u];
-            } else {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int j = j0 + u * 256 + (int)threadIdx.x;
-                    yv[u] = j < P.W ? orow[j] : 0.0f;
-                }
-            }
-            if (j0 + 8 * 256 >= P.W) request(rr + 1);  // (in flight while this batch is decided)
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int j = j0 + u * 256 + (int)threadIdx.x;
-                const float y = yv[u];
-                bool keep = y != 0.0f && j < P.W;  // NaN: kept (stored explicitly, like csr_matrix(x_res))
-                bool tie = false;
-                if (has_thr) {
-                    const int cmp = thr_compare(fabsf(y), thf);
-                    if (cmp < 0) keep = false;
-                    tie = cmp == 0 && keep;
-                }
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(keep), tm = __builtin_amdgcn_ballot_w64(tie);
-                if ((threadIdx.x & 63) == 0 && j < P.W) {
-                    mwords[rr * n_words + (j >> 6)] = m;
-                    twords[rr * n_words + (j >> 6)] = tm;
-                }
-            }
-        }
-    }
-    __syncthreads();  // the mask words of the workgroup's rows are complete
-    // ---- ties (about one window in 1e7): each recomputed in float64 by the thread that finds it (one thread per word) ----
-    for (int w = threadIdx.x; w < n_here * n_words; w += 256) {
-        unsigned long long tm = twords[w];
-        while (tm) {
-            const int bit = __builtin_ctzll(tm);
-            tm &= tm - 1;
-            const int rr = w / n_words, j = (w - rr * n_words) * 64 + bit;
-            const int64_t cell = cell0 + rr;
-            const double th = thr[(cell + row_phase) / chunksize];
-            const int st = P.w_start[j];
-            const double yd = window_canonical(P, j, [&](int k) { return value_at<T, CSR>(P, cell, st + k); }) -
-                              P.cell_median[cell];
-            if (fabs(yd) < th) mwords[w] &= ~(1ull << bit);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64)
-        pack_lookback(threadIdx.x, tk, (P.n_rows + rpw - 1) / rpw, n_here, n_words, mwords, woff, row_base, status, gstat,
-                      gacc, indptr);
-    __syncthreads();
-    // ---- pack: the rows again (L2), entries in window order ----------------------------------------------------------
-    if ((int)threadIdx.x < n_here) indptr[cell0 + threadIdx.x + 1] = row_base[threadIdx.x + 1];
-    const int lane = threadIdx.x & 63;
-    for (int rr = 0; rr < n_here; ++rr) {
-        const float* orow = P.out + (cell0 + rr) * P.ldo;
-        const int64_t base = row_base[rr];
-        for (int j = threadIdx.x; j < P.W; j += 256) {
-            const unsigned long long m = mwords[rr * n_words + (j >> 6)];
-            if ((m >> lane) & 1ull) {
-                const int64_t pos = base + woff[rr * n_words + (j >> 6)] +
-                                    __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-#if defined(ICV_DEV_EXPERIMENTS) && defined(ICV_PACK_EXP_NOSTORE)
-                if (pos < 0) {
-#else
-                if (pos < cap) {
-#endif
-                    indices[pos] = j;
-                    data[pos] = (double)orow[j];
-                }
-            }
-        }
-    }
-}
-
 // x_res = window - median (float32), per-cell moments and median, from float64 windows resident in HBM (the
 // last step of the chromosome-group fallback; same DPP reduction tree as the smoothing kernels)
 __global__ void __launch_bounds__(256) k_win_finish(const double* win, int64_t n_rows, int W, const double* med,
@@ -1541,40 +1339,9 @@ __global__ void __launch_bounds__(256) k_fill_nan(double* out, int64_t n_rows, i
 }
 
 // ---------------------------------------------------------------------------------------
-// X_cnv is returned as CSR float64 (reference :455, :137): count / pack the non-zeros of the dense
-// float32 result on the device, so that only ~13 % of the matrix crosses PCIe.  One wavefront per row.
+// X_cnv is returned as CSR float64 (reference :455, :137): the kept entries of the dense float32
+// result are packed on the device, so that only ~13 % of the matrix crosses PCIe.
 // ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_csr_count(const float* x, int64_t n_rows, int n_cols, int64_t ld,
-                                                   int64_t* row_nnz) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_rows) return;
-    const float* xr = x + row * ld;
-    int c = 0;
-    for (int j = threadIdx.x & 63; j < n_cols; j += 64) c += (xr[j] != 0.0f) ? 1 : 0;  // NaN counts as stored
-    c = wave_sum_i(c);
-    if ((threadIdx.x & 63) == 0) row_nnz[row] = c;
-}
-
-__global__ void __launch_bounds__(256) k_csr_fill(const float* x, int64_t n_rows, int n_cols, int64_t ld,
-                                                  const int64_t* indptr, int32_t* indices, double* data) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* xr = x + row * ld;
-    int64_t base = indptr[row];
-    for (int j0 = 0; j0 < n_cols; j0 += 64) {
-        const int j = j0 + lane;
-        const float v = j < n_cols ? xr[j] : 0.0f;
-        const bool nz = v != 0.0f;
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(nz);
-        if (nz) {
-            const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-            indices[base + pos] = j;
-            data[base + pos] = (double)v;
-        }
-        base += __popcll(m);
-    }
-}
 
 // cnv_score on a CSR X_cnv: per-row sum |data| over the stored entries (implicit zeros add nothing), float64,
 // one wavefront per row, fixed reduction order

@@ -1,7 +1,6 @@
 """GPU tests (``-m gpu``) of the device-side CSR packing of X_cnv: step 5b and ``csr_matrix(x_res)`` (reference
-tl/_infercnv.py:449-455) as keep-mask + ``icv_row_offsets`` + fill (the public path's default) and in one pass with a
-decoupled look-back over the rows (``icv_threshold_pack``), against each other, against a torch prefix sum and against
-the in-place threshold: identical CSR arrays, run after run."""
+tl/_infercnv.py:449-455) as keep-mask + ``icv_row_offsets`` + fill (the public path), against a torch prefix sum with
+``icv_csr_fill_masked`` and against the in-place threshold packed by scipy: identical CSR arrays, run after run."""
 import numpy as np
 import pandas as pd
 import pytest
@@ -57,18 +56,12 @@ def test_pack_equals_mask_and_fill(fmt, dtype, genes, window, step, dyn, n):
     try:
         res = _engine.run_hot_path(plan, dm, ref, dynamic_threshold=dyn, chunksize=chunksize, apply=False)
         ip2, ix2, dv2 = _two_step(torch, _engine, _lib, plan, dm, ref, res, chunksize)
-        for rep in range(3):  # the look-back must give the same arrays whatever order the rows finish in
-            pk = _engine.threshold_pack(plan, dm, ref, None, res, lfc_clip=3.0, chunksize=chunksize)
-            ip = pk.indptr.cpu().numpy()
-            nnz = int(ip[-1])
-            np.testing.assert_array_equal(ip, ip2)
+        nnz = int(ip2[-1])
+        for rep in range(3):  # the public path (mask + icv_row_offsets + fill, nothing read back): the same run after run
+            pk = _engine.threshold_csr(plan, dm, ref, None, res, lfc_clip=3.0, chunksize=chunksize)
+            np.testing.assert_array_equal(pk.indptr.cpu().numpy(), ip2)
             np.testing.assert_array_equal(pk.indices[:nnz].cpu().numpy(), ix2)
             np.testing.assert_array_equal(pk.data[:nnz].cpu().numpy(), dv2)
-        # the default of the public path: mask + icv_row_offsets + fill, nothing read back
-        pk = _engine.threshold_csr(plan, dm, ref, None, res, lfc_clip=3.0, chunksize=chunksize)
-        np.testing.assert_array_equal(pk.indptr.cpu().numpy(), ip2)
-        np.testing.assert_array_equal(pk.indices[:nnz].cpu().numpy(), ix2)
-        np.testing.assert_array_equal(pk.data[:nnz].cpu().numpy(), dv2)
         # ... and the in-place threshold of the same x_res, packed by scipy
         res_a = _engine.run_hot_path(plan, dm, ref, dynamic_threshold=dyn, chunksize=chunksize, apply=True)
         exp = sp.csr_matrix(res_a.out.cpu().numpy().astype(np.float64))
@@ -77,11 +70,6 @@ def test_pack_equals_mask_and_fill(fmt, dtype, genes, window, step, dyn, n):
         np.testing.assert_array_equal(got.indptr, exp.indptr)
         np.testing.assert_array_equal(got.indices, exp.indices)
         np.testing.assert_array_equal(got.data, exp.data)
-        # a capacity that is too small drops the overflow but still reports the count
-        if nnz > 10:
-            small = _engine.threshold_pack(plan, dm, ref, None, res, lfc_clip=3.0, chunksize=chunksize, capacity=nnz // 2)
-            assert small.nnz() == nnz
-            np.testing.assert_array_equal(small.indices[: nnz // 2].cpu().numpy(), ix2[: nnz // 2])
     finally:
         plan.close()
 

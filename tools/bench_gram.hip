@@ -55,18 +55,18 @@ __global__ void __launch_bounds__(256) k_mfma_only(float* out, int iters) {
         for (int r = 0; r < 16; ++r) s += acc[a][r];
     if (s == 123.456f) out[0] = s;
 }
-static void mfma_only(float* out, int wgs_per_cu, int iters, const char* what) {
+static void mfma_only(float* out, int wg_per_cu, int iters, const char* what) {
     hipEvent_t a, b;
     hipEventCreate(&a);
     hipEventCreate(&b);
     hipEventRecord(a, 0);
-    hipLaunchKernelGGL(k_mfma_only, dim3(256 * wgs_per_cu), dim3(256), 0, 0, out, iters);
+    hipLaunchKernelGGL(k_mfma_only, dim3(256 * wg_per_cu), dim3(256), 0, 0, out, iters);
     hipEventRecord(b, 0);
     hipEventSynchronize(b);
     float ms = 0;
     hipEventElapsedTime(&ms, a, b);
-    const double flop = 256.0 * wgs_per_cu * 4 * iters * 4 * 4096.0;
-    printf("mfma only, %d wavefront(s) per SIMD, %s: %.2f ms  %.1f TFLOP/s\n", wgs_per_cu, what, ms, flop / (ms * 1e-3) / 1e12);
+    const double flop = 256.0 * wg_per_cu * 4 * iters * 4 * 4096.0;
+    printf("mfma only, %d wavefront(s) per SIMD, %s: %.2f ms  %.1f TFLOP/s\n", wg_per_cu, what, ms, flop / (ms * 1e-3) / 1e12);
 }
 
 int main(int argc, char** argv) {
