@@ -749,6 +749,47 @@ int icv_changepoint_levels(const icv_matrix *m, const int32_t *chr_start, int32_
                            double *levels, uint8_t *starts, void *stream);
 int icv_changepoint_diffsq(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, double *d, void *stream);
 
+/* ---- tl.cnv_rank_groups: the exact doubled mid-rank sums of every group of rows in every window -----------
+ * A value is what it is for icv_group_profiles: stored values are used as float64, an entry that is not stored is 0, a
+ * stored 0.0 or -0.0 is the same 0; CSR columns need not be sorted but are unique within a row (a duplicate would be
+ * ranked as a cell of its own); a column outside [0, n_cols) is passed over.  code (device
+ * int32, n_rows) gives every row its group: a row with code < 0 is outside the population, the N others are ranked
+ * against each other, N < ICV_RANK_MAX_CELLS so that N^3 fits an int64 (icv_rank_sums and icv_rank_finish return
+ * ICV_ERR_INVALID beyond, before anything is launched).  All five enqueue on the stream and synchronise nothing.
+ * icv_rank_count: stored (device int32, n_cols) is zeroed and receives per window the number of the population's values
+ * that are neither 0 nor non-finite; *flags (device int32) is set to 0 and bit 0 is then set where a value of the
+ * population is not finite.  n_cols has no limit.
+ * The caller cuts the windows into consecutive tiles [w0, w0 + n_win) and forms seg_off (device int32, n_win + 1): the
+ * exclusive prefix sum of stored over the tile, from 0; n_entries = seg_off[n_win] <= 2^31 - 1.
+ * icv_rank_scatter: cursor (device int32, n_win) is zeroed; every counted value of the tile is written to a slot of its
+ * window's segment of keys (device uint64, n_entries) and payload (device int32, n_entries): the key is the
+ * order-preserving image of the float64 (bit pattern with the sign bit set for a positive value, all bits inverted for a
+ * negative one), the payload the row's code.  The order inside a segment is arbitrary.  A value that finds its segment
+ * full (the matrix is not the one that was counted) is dropped.
+ * icv_rank_sort: keys_sorted / payload_sorted receive every segment sorted by key (rocprim's segmented radix sort; the
+ * order of equal keys is arbitrary and nothing reads it).
+ * icv_rank_sums: longest = the longest segment of the tile (it sizes the grid).  r2 (device int64) and cnt (device int32)
+ * are n_codes x n_cols tables, tie (device int64) and neg (device int32) have n_cols elements; the caller zeroes all four
+ * before the first tile.  For the entry at position p of its sorted segment, with [s, e) its run of equal keys and
+ * z0 = n_pop - (segment length): 2r = s + e + 1, plus 2 z0 for a positive value, is added to r2[code, w] and 1 to
+ * cnt[code, w] (a code outside [0, n_codes) adds nothing); the first entry of a run of c > 1 adds c^3 - c to tie[w];
+ * neg[w] receives the number of negative values.  A run may have any length.  Integer atomic adds only: a pure function
+ * of the arguments.
+ * icv_rank_finish: after the last tile, for the first n_groups codes (n_cells, device int64, their sizes):
+ * r2[g,w] += (n_cells[g] - cnt[g,w]) (2 neg[w] + z0 + 1) and tie[w] += z0^3 - z0 with z0 = n_pop - stored[w], the block of
+ * the cells whose value is 0.  r2 then holds R2 and tie holds T of DESIGN.md 4.20 rule 2. */
+#define ICV_RANK_MAX_CELLS (1 << 21)
+int icv_rank_count(const icv_matrix *m, const int32_t *code, int32_t *stored, int32_t *flags, void *stream);
+int icv_rank_scatter(const icv_matrix *m, const int32_t *code, int32_t w0, int32_t n_win, const int32_t *seg_off,
+                     int32_t *cursor, uint64_t *keys, int32_t *payload, void *stream);
+int icv_rank_sort(const uint64_t *keys, const int32_t *payload, int64_t n_entries, const int32_t *seg_off, int32_t n_win,
+                  uint64_t *keys_sorted, int32_t *payload_sorted, void *stream);
+int icv_rank_sums(const uint64_t *keys, const int32_t *payload, const int32_t *seg_off, int32_t w0, int32_t n_win,
+                  int32_t longest, int32_t n_cols, int64_t n_pop, int32_t n_codes, int64_t *r2, int32_t *cnt, int64_t *tie,
+                  int32_t *neg, void *stream);
+int icv_rank_finish(const int32_t *stored, const int32_t *neg, const int32_t *cnt, const int64_t *n_cells, int64_t n_groups,
+                    int32_t n_cols, int64_t n_pop, int64_t *r2, int64_t *tie, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -2061,3 +2061,107 @@ def profile_corr_best(r):
         best_r, best_g = _empty(torch, n, torch.float64), _empty(torch, n, torch.int32)
         _lib.check(lib.icv_profile_corr_best(_ptr(r) if g else None, n, g, _ptr(best_r), _ptr(best_g), _stream_ptr(torch)))
     return best_r, best_g
+
+
+# ---- tl.cnv_rank_groups: exact doubled mid-rank sums on the device (icv_rank_*, DESIGN.md 4.20) ---------------------------
+RANK_STAGES = ("count", "scatter", "sort", "rank_sums", "finish")
+
+
+def rank_window_tiles(counts, max_entries):
+    """[(w0, w1), ...]: the windows cut into consecutive tiles whose ``counts`` (host int64 per window) sum to at most
+    ``max_entries``; a tile has at least one window, whatever its count."""
+    ends = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    tiles, w0, n_windows = [], 0, int(counts.shape[0])
+    while w0 < n_windows:
+        w1 = int(np.searchsorted(ends, ends[w0] + int(max_entries), side="right")) - 1
+        w1 = min(n_windows, max(w1, w0 + 1))
+        tiles.append((w0, w1))
+        w0 = w1
+    return tiles
+
+
+def rank_tables(dm: DeviceMatrix, code, n_cells, *, max_entries=1 << 28, stage_ms=None, info=None):
+    """(R2, T, flags): device int64 ``G x W`` and ``W`` tables of DESIGN.md 4.20 rule 2 and the flag word as an int (bit
+    0: a value of the population is not finite; R2 and T are None then and nothing but the count has run).  ``code``:
+    host int32 per row, -1 outside the population, 0 .. G - 1 for the G tested groups, G for the cells that are ranked
+    but belong to no tested group; ``n_cells``: host int64 sizes of the G groups.  The windows are ranked in consecutive
+    tiles of at most ``max_entries`` ranked values (never below the population, so that a window always fits), which
+    bounds the workspace at 24 bytes per entry of the largest tile; ``MemoryError`` when that does not fit the free
+    HBM.  The window counts and the flag word are read back in one copy.  ``stage_ms``: a dict that receives the
+    device-event milliseconds of ``RANK_STAGES`` (one more synchronisation at the end); ``info``: a dict that receives
+    ``n_entries`` and ``n_tiles``."""
+    torch = _torch()
+    lib = _lib.load()
+    n, w = int(dm.shape[0]), int(dm.shape[1])
+    code = np.ascontiguousarray(code, dtype=np.int32)
+    n_cells = np.ascontiguousarray(n_cells, dtype=np.int64)
+    g = int(n_cells.shape[0])
+    n_pop = int(np.count_nonzero(code >= 0))
+    assert code.shape == (n,) and g >= 1 and int(code.max(initial=-1)) <= g
+    if n_pop >= _lib.ICV_RANK_MAX_CELLS:
+        raise ValueError(f"rank_tables: {n_pop} cells are ranked against each other; at most {_lib.ICV_RANK_MAX_CELLS - 1} "
+                         f"are supported (N^3 in an int64)")
+    marks = []
+
+    def mark(name):
+        if stage_ms is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            marks.append((name, ev))
+
+    with torch.cuda.device(dm.device):
+        st = _stream_ptr(torch)
+        m = dm.c_struct()
+        d_code = torch.from_numpy(code).cuda() if n else torch.zeros(1, dtype=torch.int32, device="cuda")
+        head = torch.empty(1 + w, dtype=torch.int32, device="cuda")  # the flag word, then the window counts
+        flags, stored = head[:1], head[1:]
+        mark(None)
+        _lib.check(lib.icv_rank_count(C.byref(m), _ptr(d_code), _ptr(stored), _ptr(flags), st))
+        mark("count")
+        host = head.cpu().numpy()
+        bits, counts = int(host[0]), host[1:].astype(np.int64)
+        if bits & 1:
+            return None, None, bits
+        cap = min(max(int(max_entries), n_pop, 1), 2 ** 31 - 1)
+        tiles = rank_window_tiles(counts, cap)
+        ends = np.concatenate([[0], np.cumsum(counts)])
+        largest = max(int(ends[w1] - ends[w0]) for w0, w1 in tiles)
+        need = 24 * largest + (g + 1) * w * 12 + w * 12
+        if need > free_hbm_bytes():
+            raise MemoryError(f"rank_tables: the workspace of {largest} ranked values per window tile and the tables of "
+                              f"{g + 1} x {w} sums take {need} bytes, more than the {free_hbm_bytes()} bytes of free HBM; "
+                              f"lower max_entries (now {cap})")
+        r2 = torch.zeros((g + 1, w), dtype=torch.int64, device="cuda")
+        cnt = torch.zeros((g + 1, w), dtype=torch.int32, device="cuda")
+        tie = torch.zeros(w, dtype=torch.int64, device="cuda")
+        neg = torch.zeros(w, dtype=torch.int32, device="cuda")
+        keys = torch.empty((2, max(largest, 1)), dtype=torch.int64, device="cuda")  # (uint64 keys, as bits)
+        payload = torch.empty((2, max(largest, 1)), dtype=torch.int32, device="cuda")
+        d_cells = torch.from_numpy(n_cells).cuda()
+        for w0, w1 in tiles:
+            n_entries = int(ends[w1] - ends[w0])
+            if n_entries == 0:
+                continue
+            seg = torch.from_numpy((ends[w0:w1 + 1] - ends[w0]).astype(np.int32)).cuda()
+            cursor = torch.empty(w1 - w0, dtype=torch.int32, device="cuda")
+            mark(None)
+            _lib.check(lib.icv_rank_scatter(C.byref(m), _ptr(d_code), w0, w1 - w0, _ptr(seg), _ptr(cursor), _ptr(keys[0]),
+                                            _ptr(payload[0]), st))
+            mark("scatter")
+            _lib.check(lib.icv_rank_sort(_ptr(keys[0]), _ptr(payload[0]), n_entries, _ptr(seg), w1 - w0, _ptr(keys[1]),
+                                         _ptr(payload[1]), st))
+            mark("sort")
+            _lib.check(lib.icv_rank_sums(_ptr(keys[1]), _ptr(payload[1]), _ptr(seg), w0, w1 - w0, int(counts[w0:w1].max()),
+                                         w, n_pop, g + 1, _ptr(r2), _ptr(cnt), _ptr(tie), _ptr(neg), st))
+            mark("rank_sums")
+        mark(None)
+        _lib.check(lib.icv_rank_finish(_ptr(stored), _ptr(neg), _ptr(cnt), _ptr(d_cells), g, w, n_pop, _ptr(r2), _ptr(tie), st))
+        mark("finish")
+        if stage_ms is not None:
+            torch.cuda.current_stream().synchronize()
+            for (_, a), (name, b) in zip(marks, marks[1:]):
+                if name is not None:
+                    stage_ms[name] = stage_ms.get(name, 0.0) + float(a.elapsed_time(b))
+    if info is not None:
+        info.update(n_entries=int(ends[-1]), n_tiles=len(tiles))
+    return r2[:g], tie, bits

@@ -24,6 +24,7 @@ ICV_GRAM_BLOCK = 8192  # rows per split-K block of icv_gram_f64 (include/infercn
 ICV_STATES_MAX_WINDOWS = 16384  # windows icv_states_viterbi keeps in LDS per cell (include/infercnv_hip.h)
 ICV_POSTERIOR_MAX_WINDOWS = 4096  # windows icv_posterior_chains keeps in LDS per cell (include/infercnv_hip.h)
 ICV_CHANGEPOINT_MAX_CHR_WINDOWS = 4096  # windows of one chromosome icv_changepoint_levels keeps in LDS (include/infercnv_hip.h)
+ICV_RANK_MAX_CELLS = 1 << 21  # cells icv_rank_sums ranks against each other: N^3 in an int64 (include/infercnv_hip.h)
 ICV_FILTER_MAX_WINDOWS = 1 << 22  # windows per row of icv_states_filter: a run's int64 sum (include/infercnv_hip.h)
 (ICV_KERNEL_NONE, ICV_KERNEL_GENERIC, ICV_KERNEL_WS, ICV_KERNEL_WS_CSR, ICV_KERNEL_X16, ICV_KERNEL_SD,
  ICV_KERNEL_SPLIT) = range(7)
@@ -54,6 +55,7 @@ EXPORTS = (
     "icv_group_profiles", "icv_group_profiles_finish",
     "icv_profile_corr", "icv_profile_corr_best",
     "icv_changepoint_levels", "icv_changepoint_diffsq",
+    "icv_rank_count", "icv_rank_scatter", "icv_rank_sort", "icv_rank_sums", "icv_rank_finish",
 )
 
 
@@ -207,6 +209,11 @@ def load():
     lib.icv_profile_corr_best.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.icv_changepoint_levels.argtypes = [P(Matrix), vp, i32, dbl, i32, vp, vp, vp]
     lib.icv_changepoint_diffsq.argtypes = [P(Matrix), vp, i32, vp, vp]
+    lib.icv_rank_count.argtypes = [P(Matrix), vp, vp, vp, vp]
+    lib.icv_rank_scatter.argtypes = [P(Matrix), vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.icv_rank_sort.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp]
+    lib.icv_rank_sums.argtypes = [vp, vp, vp, i32, i32, i32, i32, i64, i32, vp, vp, vp, vp, vp]
+    lib.icv_rank_finish.argtypes = [vp, vp, vp, vp, i64, i32, i64, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

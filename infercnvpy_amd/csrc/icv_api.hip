@@ -25,6 +25,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include "icv_kernels.hpp"
 #include "icv_kernel_ws.hpp"
@@ -50,6 +51,7 @@
 #include "icv_pseudobulk.hpp"
 #include "icv_profile_corr.hpp"
 #include "icv_changepoint.hpp"
+#include "icv_rank.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -4295,6 +4297,109 @@ int icv_changepoint_diffsq(const icv_matrix* m, const int32_t* chr_start, int32_
                       chr_start, n_chr, (size_t)longest * 16, st, longest, e.as<double>()));
     hipLaunchKernelGGL(icv::k_changepoint_rowsum, dim3((unsigned)((m->n_rows + 255) / 256)), dim3(256), 0, st, e.as<double>(),
                        m->n_rows, n_chr, d);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_rank_groups: exact doubled mid-rank sums of every group in every window -------------------------
+static_assert((size_t)icv::kRkTile * 4 <= 32 * 1024, "the counters of a window tile take 32 KB of LDS");
+static_assert((size_t)icv::kRkLdsGroups * 12 + 16 <= 32 * 1024, "the sums of a workgroup take 24 KB of LDS");
+static_assert(icv::kRkMaxCells == ICV_RANK_MAX_CELLS, "the header's population cap is the kernel's");
+static_assert(icv::kRkChunk % icv::kRkSumThreads == 0, "every thread of the rank sums takes the same share of a chunk");
+
+int icv_rank_count(const icv_matrix* m, const int32_t* code, int32_t* stored, int32_t* flags, void* stream) {
+    if (!matrix_header_ok(m) || !stored || !flags || m->n_cols < 1 || (m->n_rows > 0 && !code) ||
+        (m->format == ICV_DENSE && m->ld < m->n_cols))
+        return fail(ICV_ERR_INVALID, "bad rank_count arguments");
+    if (m->n_rows > 0 && !matrix_complete(m)) return fail(ICV_ERR_INVALID, "rank_count: incomplete matrix");
+    const int64_t n_tiles = ((int64_t)m->n_cols + icv::kRkTile - 1) / icv::kRkTile;
+    const int64_t slabs = (m->n_rows + icv::kRkSlab - 1) / icv::kRkSlab;
+    if (slabs > kSegMaxBlocks / n_tiles) return fail(ICV_ERR_UNSUPPORTED, "rank_count: too many rows x windows for one call");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(stored, 0, (size_t)m->n_cols * sizeof(int32_t), st));
+    if (m->n_rows == 0) return ICV_OK;
+    const dim3 grid((unsigned)(slabs * n_tiles)), block(icv::kRkThreads);
+    by_matrix(m, [&](auto t, auto csr) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((icv::k_rank_count<T, decltype(csr)::value>), grid, block, 0, st, (const T*)m->values, m->indptr,
+                           m->indices, m->ld, m->n_rows, m->n_cols, code, (uint32_t)n_tiles, stored, flags);
+    });
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_rank_scatter(const icv_matrix* m, const int32_t* code, int32_t w0, int32_t n_win, const int32_t* seg_off,
+                     int32_t* cursor, uint64_t* keys, int32_t* payload, void* stream) {
+    if (!matrix_header_ok(m) || m->n_cols < 1 || (m->n_rows > 0 && !code) || w0 < 0 || n_win < 1 || w0 > m->n_cols - n_win ||
+        !seg_off || !cursor || !keys || !payload || (m->format == ICV_DENSE && m->ld < m->n_cols))
+        return fail(ICV_ERR_INVALID, "bad rank_scatter arguments");
+    if (m->n_rows > 0 && !matrix_complete(m)) return fail(ICV_ERR_INVALID, "rank_scatter: incomplete matrix");
+    const int64_t n_tiles = ((int64_t)n_win + icv::kRkTile - 1) / icv::kRkTile;
+    const int64_t slabs = (m->n_rows + icv::kRkSlab - 1) / icv::kRkSlab;
+    if (slabs > kSegMaxBlocks / n_tiles) return fail(ICV_ERR_UNSUPPORTED, "rank_scatter: too many rows x windows for one call");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)n_win * sizeof(int32_t), st));
+    if (m->n_rows == 0) return ICV_OK;
+    by_matrix(m, [&](auto t, auto csr) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((icv::k_rank_scatter<T, decltype(csr)::value>), dim3((unsigned)(slabs * n_tiles)),
+                           dim3(icv::kRkThreads), 0, st, (const T*)m->values, m->indptr, m->indices, m->ld, m->n_rows, code, w0,
+                           n_win, (uint32_t)n_tiles, seg_off, cursor, reinterpret_cast<unsigned long long*>(keys), payload);
+    });
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_rank_sort(const uint64_t* keys, const int32_t* payload, int64_t n_entries, const int32_t* seg_off, int32_t n_win,
+                  uint64_t* keys_sorted, int32_t* payload_sorted, void* stream) {
+    if (n_entries < 0 || n_entries > 0x7fffffffLL || n_win < 1 || !seg_off ||
+        (n_entries > 0 && (!keys || !payload || !keys_sorted || !payload_sorted)))
+        return fail(ICV_ERR_INVALID, "bad rank_sort arguments");
+    if (n_entries == 0) return ICV_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned long long* in = reinterpret_cast<const unsigned long long*>(keys);
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(keys_sorted);
+    size_t tb = 0;
+    HIP_TRY(rocprim::segmented_radix_sort_pairs(nullptr, tb, in, out, payload, payload_sorted, (unsigned)n_entries,
+                                                (unsigned)n_win, seg_off, seg_off + 1, 0, 64, st));
+    AsyncBuf tmp;
+    HIP_TRY(tmp.alloc(tb, st));
+    HIP_TRY(rocprim::segmented_radix_sort_pairs(tmp.p, tb, in, out, payload, payload_sorted, (unsigned)n_entries,
+                                                (unsigned)n_win, seg_off, seg_off + 1, 0, 64, st));
+    return ICV_OK;
+}
+
+int icv_rank_sums(const uint64_t* keys, const int32_t* payload, const int32_t* seg_off, int32_t w0, int32_t n_win,
+                  int32_t longest, int32_t n_cols, int64_t n_pop, int32_t n_codes, int64_t* r2, int32_t* cnt, int64_t* tie,
+                  int32_t* neg, void* stream) {
+    if (!seg_off || w0 < 0 || n_win < 1 || n_cols < 1 || w0 > n_cols - n_win || longest < 0 || n_pop < 0 ||
+        n_pop >= ICV_RANK_MAX_CELLS || longest > n_pop || n_codes < 1 || !r2 || !cnt || !tie || !neg ||
+        (longest > 0 && (!keys || !payload)))
+        return fail(ICV_ERR_INVALID, "bad rank_sums arguments");
+    if (longest == 0) return ICV_OK;
+    const dim3 grid((unsigned)n_win, (unsigned)((longest + icv::kRkChunk - 1) / icv::kRkChunk)), block(icv::kRkSumThreads);
+    auto launch = [&](auto lds) {
+        hipLaunchKernelGGL((icv::k_rank_sums<decltype(lds)::value>), grid, block, 0, static_cast<hipStream_t>(stream),
+                           reinterpret_cast<const unsigned long long*>(keys), payload, seg_off, w0, n_cols, n_pop, n_codes,
+                           reinterpret_cast<unsigned long long*>(r2), cnt, reinterpret_cast<unsigned long long*>(tie), neg);
+    };
+    if (n_codes <= icv::kRkLdsGroups) launch(std::true_type{}); else launch(std::false_type{});
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_rank_finish(const int32_t* stored, const int32_t* neg, const int32_t* cnt, const int64_t* n_cells, int64_t n_groups,
+                    int32_t n_cols, int64_t n_pop, int64_t* r2, int64_t* tie, void* stream) {
+    if (n_groups < 0 || n_cols < 1 || n_pop < 0 || n_pop >= ICV_RANK_MAX_CELLS ||
+        (n_groups > 0 && (!stored || !neg || !cnt || !n_cells || !r2 || !tie)))
+        return fail(ICV_ERR_INVALID, "bad rank_finish arguments");
+    if (n_groups == 0) return ICV_OK;
+    const int64_t blocks = (n_groups * (int64_t)n_cols + 255) / 256;
+    if (n_groups > kSegMaxBlocks || blocks > kSegMaxBlocks)
+        return fail(ICV_ERR_UNSUPPORTED, "rank_finish: too many groups x windows for one call");
+    hipLaunchKernelGGL(icv::k_rank_finish, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), stored, neg,
+                       cnt, n_cells, n_groups, n_cols, n_pop, r2, tie);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
