@@ -97,6 +97,55 @@ def partition_vectorised(xs, beta, m):
     return F.tolist(), back, P
 
 
+# ---- rule 3 as the kernel shares it out ----------------------------------------------------------------------------------
+LANES = 64  # lanes of the wavefront that takes one (row, chromosome) in k_changepoint_levels
+NO_CANDIDATE = 0x7fffffff
+LANE_MODES = ("kernel", "lane_le", "lowest_lane", "highest_i", "no_clamp")
+
+
+def lane_partition(xs, beta, m, mode="kernel"):
+    """(F, back, P) of rule 3 formed the way k_changepoint_levels forms it (csrc/icv_changepoint.hpp): the admissible i of
+    one j are numbered k = 0 (i = 0, where ``with_zero`` admits it), 1, 2, ... (i = m + k - 1); lane l of 64 walks
+    k = l, l + 64, ... and keeps its own best under a strict <; the least of the 64 bests is found, and among the lanes
+    that hold it the lowest i.  ``mode`` "kernel" is that; every other mode is one mistake the kernel could make:
+
+    - "lane_le": a lane replaces its best on <= (the highest of a lane's equal candidates survives);
+    - "lowest_lane": among the lanes that hold the least value the lowest lane wins, not the lowest i;
+    - "highest_i": ties go to the highest i, inside a lane and across the lanes;
+    - "no_clamp": rule 2 without ``c < 0.0 -> 0.0``.
+
+    It exists so that a host test can show which case tells the kernel from which mutant."""
+    assert mode in LANE_MODES
+    L = len(xs)
+    P, Q = prefix_chains(xs)
+    F, back = [0.0] + [math.inf] * L, [0] * (L + 1)
+    replace_equal = mode in ("lane_le", "highest_i")
+    for j in range(1, L + 1):
+        with_zero = j >= m or j == L
+        n_cand = 1 + max(j - 2 * m + 1, 0)
+        best, bi = [math.inf] * LANES, [NO_CANDIDATE] * LANES
+        for k in range(0 if with_zero else 1, n_cand):  # (ascending k: every lane meets its own k in ascending order)
+            lane = k % LANES
+            i = 0 if k == 0 else m + k - 1
+            d = P[j] - P[i]
+            c = (Q[j] - Q[i]) - (d * d) / float(j - i)
+            if c < 0.0 and mode != "no_clamp":
+                c = 0.0
+            v = (F[i] + c) + beta
+            if v < best[lane] or (replace_equal and v == best[lane]):
+                best[lane], bi[lane] = v, i
+        least = min(best)
+        holders = [bi[lane] for lane in range(LANES) if best[lane] == least]  # (in ascending lane order)
+        if mode == "lowest_lane":
+            who = holders[0]
+        elif mode == "highest_i":
+            who = max([i for i in holders if i != NO_CANDIDATE], default=NO_CANDIDATE)
+        else:
+            who = min(holders)
+        F[j], back[j] = least, 0 if who == NO_CANDIDATE else who
+    return F, back, P
+
+
 # ---- rules 4-5 -----------------------------------------------------------------------------------------------------------
 def backtrack(back, L):
     """The segments (i, j] of rule 4, ascending."""
@@ -110,11 +159,12 @@ def backtrack(back, L):
     return out
 
 
-def segment_chromosome(xs, beta, m, vectorised=False):
-    """(levels, starts, segments, cost) of one chromosome: two lists of L entries, the list of (i, j] and F_L."""
+def segment_chromosome(xs, beta, m, vectorised=False, part=None):
+    """(levels, starts, segments, cost) of one chromosome: two lists of L entries, the list of (i, j] and F_L.  ``part``: a
+    function like ``partition`` to take rule 3 from instead (the lane model below and its mutants)."""
     xs = [float(v) for v in xs]
     L = len(xs)
-    F, back, P = (partition_vectorised if vectorised else partition)(xs, float(beta), int(m))
+    F, back, P = (part or (partition_vectorised if vectorised else partition))(xs, float(beta), int(m))
     segs = backtrack(back, L)
     levels, starts = [0.0] * L, [0] * L
     for i, j in segs:
@@ -192,9 +242,10 @@ def check_values(rows, beta, who="cnv_changepoints"):
 
 
 # ---- the whole function ----------------------------------------------------------------------------------------------------
-def cnv_changepoints(x, chr_pos, penalty=2.0, sigma=None, min_windows=1, vectorised=True):
+def cnv_changepoints(x, chr_pos, penalty=2.0, sigma=None, min_windows=1, vectorised=True, part=None):
     """dict(levels float64 n x W, starts uint8 n x W, n_segments int32 n, sigma, beta, table) of rules 1-7; ``table`` is the
-    list of (cell, chromosome, start, end, n_windows, mean) ordered by (cell, start)."""
+    list of (cell, chromosome, start, end, n_windows, mean) ordered by (cell, start).  ``part``: as for
+    ``segment_chromosome``."""
     n, w = x.shape
     rows = rows_of(x)
     edges = bounds(chr_pos, w)
@@ -209,7 +260,7 @@ def cnv_changepoints(x, chr_pos, penalty=2.0, sigma=None, min_windows=1, vectori
     table = []
     for r, row in enumerate(rows):
         for c, (s0, s1) in enumerate(zip(edges[:-1], edges[1:])):
-            lv, st, segs, _ = segment_chromosome(row[s0:s1], beta, min_windows, vectorised)
+            lv, st, segs, _ = segment_chromosome(row[s0:s1], beta, min_windows, vectorised, part)
             levels[r, s0:s1] = lv
             starts[r, s0:s1] = st
             table.extend((r, names[c], s0 + i, s0 + j, j - i, lv[i]) for i, j in segs)
@@ -304,6 +355,18 @@ def exact_ties(lengths=(12, 7, 1, 9, 16)):
     return sp.csr_matrix(np.stack(rows)), chr_pos_of(lengths)
 
 
+def shuffled_rows(x, seed):
+    """(indptr int64, indices int32, data float64) of the canonical CSR matrix ``x`` with the entries of every row in an
+    order of their own (a permutation seeded per row): the same matrix, its columns unique and not sorted."""
+    x = x.tocsr()
+    indices, data = x.indices.astype(np.int32), x.data.astype(np.float64)
+    for r in range(x.shape[0]):
+        a, b = int(x.indptr[r]), int(x.indptr[r + 1])
+        order = np.random.default_rng([seed, r]).permutation(b - a)
+        indices[a:b], data[a:b] = indices[a:b][order], data[a:b][order]
+    return x.indptr.astype(np.int64), indices, data
+
+
 @functools.lru_cache(maxsize=None)
 def expected(name):
     """The named GPU case with the oracle's answer, computed once: dict(x, chr_pos, kwargs, want)."""
@@ -324,9 +387,59 @@ def _empty_row():
     return _case(sp.csr_matrix(x), (40, 9, 70))
 
 
-def _ties(**kwargs):
-    x, chr_pos = exact_ties()
+def _ties(lengths=None, **kwargs):
+    x, chr_pos = exact_ties() if lengths is None else exact_ties(lengths)
     return {"x": x, "chr_pos": chr_pos, "kwargs": kwargs}
+
+
+# Chromosomes in which a lane of the kernel has a second (65, 129) and up to a fourth (200) candidate and the candidates
+# lie in all four rows of 16 lanes; 64 is the longest in which every lane still has at most one.
+TIES_LONG_LENGTHS = (65, 129, 200, 64)
+# The penalty that makes beta exactly 1/8 at sigma = 0.5 and W = 458: (penalty 0.25) log(458) rounds to 0.125.  A beta of
+# the form c log(W) with a dyadic c, as in "ties", "ties_m3" and "ties_long_m3", is no multiple of 1/4: F_j = cost + k beta
+# is rounded differently along different segmentations, and the best one of every such row is the only best one in float64
+# (tests/test_changepoint_oracle.py records it): those cases cannot tell one tie rule from another, this one can.
+EIGHTH_PENALTY = 0.08160774858657104
+
+CLAMP_VALUES = (0.1, 0.3, -0.7, 1.0 / 3.0, 1e-3, 123.456)
+CLAMP_LENGTHS = (65, 130)
+TINY_BETA = {"sigma": 1e-10, "penalty": 1.0}  # beta = 1e-20 log(195) = 5.3e-20: far below every cost that is more than rounding
+
+
+def _clamp_constant_rows(**kwargs):
+    """Values that are no multiples of a power of two, as constant rows and as two plateaus (v, then 3 v, the step in the
+    middle of every chromosome): the cost of a constant stretch is 0 but for the rounding of Q and of (d d) / n, which
+    leaves some of them below 0.0 -- the clamp of rule 2 decides what the ties between the segmentations look like."""
+    w = int(sum(CLAMP_LENGTHS))
+    step = np.concatenate([np.where(np.arange(n) < n // 2, 1.0, 3.0) for n in CLAMP_LENGTHS])
+    rows = [np.full(w, v) for v in CLAMP_VALUES] + [v * step for v in CLAMP_VALUES]
+    return _case(sp.csr_matrix(np.stack(rows)), CLAMP_LENGTHS, **kwargs)
+
+
+EVERY_LANE_WINDOWS = 131
+
+
+def _minimum_in_every_lane():
+    """Row r - 1 (r = 1 .. 130) is 0.0 on [0, r) and 1.0 on [r, 131): with beta = log(131) / 16 the two exact pieces cost
+    2 beta and everything else more, so the back-pointer of j = L is r and nothing else comes near it: candidate k = r,
+    lane r % 64, in the first (r < 64), second and third (r >= 128) round of k."""
+    w = EVERY_LANE_WINDOWS
+    x = (np.arange(w)[None, :] >= np.arange(1, w)[:, None]).astype(np.float64)
+    return _case(sp.csr_matrix(x), (w,), sigma=0.25, penalty=1.0, min_windows=1)
+
+
+REFUSAL_BOUND_WINDOWS = 70
+REFUSAL_BOUND_A = 3e151   # (a a) W = 6.3e304 and (a W) (a W) = 4.41e306: inside rule 7; 3e152 is outside
+
+
+def _values_at_the_refusal_bound():
+    w = REFUSAL_BOUND_WINDOWS
+    rng = np.random.default_rng(23)
+    a = REFUSAL_BOUND_A
+    rows = [rng.choice([-a, a, 0.0, a / 2], size=w) for _ in range(3)]
+    rows.append(rng.choice([-1e-160, 1e-160, 0.0, 0.5e-160], size=w))  # the squares are subnormal
+    rows.append(rng.choice([-5e-324, 5e-324], size=w))                  # the squares are 0.0: every cost is, all ties
+    return _case(sp.csr_matrix(np.stack(rows)), (w,), penalty=0.0, sigma=1.0)
 
 
 SEVENTY = tuple(int(v) for v in np.random.default_rng(5).integers(1, 12, size=70))
@@ -347,4 +460,18 @@ CASES = {
     "ties_beta_0": lambda: _ties(penalty=0.0),
     "ties_m3": lambda: _ties(sigma=0.5, penalty=0.5, min_windows=3),
     "chromosome_4096": lambda: _case(steps(1, (MAX_CHR_WINDOWS, 5), 22, density=0.5), (MAX_CHR_WINDOWS, 5)),
+    # the limits of the lane share-out, of the clamp and of rule 7 (tests/test_changepoint_oracle.py shows on the host what
+    # each of them tells apart)
+    "ties_long": lambda: _ties(TIES_LONG_LENGTHS, penalty=0.0),
+    "ties_long_m2": lambda: _ties(TIES_LONG_LENGTHS, penalty=0.0, min_windows=2),
+    "ties_long_m3": lambda: _ties(TIES_LONG_LENGTHS, sigma=0.5, penalty=0.5, min_windows=3),
+    "ties_long_m3_beta_eighth": lambda: _ties(TIES_LONG_LENGTHS, sigma=0.5, penalty=EIGHTH_PENALTY, min_windows=3),
+    "clamp_constant_rows": lambda: _clamp_constant_rows(penalty=0.0),
+    "clamp_constant_rows_tiny_beta": lambda: _clamp_constant_rows(**TINY_BETA),
+    "minimum_in_every_lane": _minimum_in_every_lane,
+    "values_at_the_refusal_bound": _values_at_the_refusal_bound,
 }
+EDGE_CASES = ("ties_long", "ties_long_m2", "ties_long_m3", "ties_long_m3_beta_eighth", "clamp_constant_rows",
+                   "clamp_constant_rows_tiny_beta", "minimum_in_every_lane", "values_at_the_refusal_bound")
+TIES_CASES = ("ties", "ties_beta_0", "ties_m3", "ties_long", "ties_long_m2", "ties_long_m3", "ties_long_m3_beta_eighth")
+TIES_CASES_WITHOUT_A_TIE = ("ties", "ties_m3", "ties_long_m3")  # beta = c log(W): see EIGHTH_PENALTY

@@ -24,6 +24,7 @@ SUM_THREADS = 256    # threads per workgroup of the rank sums (csrc/icv_rank.hpp
 CHUNK = 2048         # sorted entries per workgroup of the rank sums (kRkChunk)
 SLAB = 128           # rows per workgroup of the count and the scatter (kRkSlab)
 TILE = 8192          # windows per workgroup of the count and the scatter (kRkTile)
+LDS_GROUPS = 2048    # codes whose sums a workgroup of the rank sums keeps in LDS (kRkLdsGroups); more go to global atomics
 MAX_CELLS = 1 << 21
 
 
@@ -206,9 +207,50 @@ def run_column(n, run, start, seed, lower=True):
     return col[rng.permutation(n)]
 
 
+LDS_TABLE_CELLS = 2300  # above CHUNK: the segment of a window stored in every cell spans two workgroups of the rank sums
+
+
+def lds_table_matrix():
+    """2300 cells x 5 windows, dense float64: a window stored in every cell without ties, a run of 1025 equal values across
+    the chunk boundary, one-decimal values of both signs at 40 % density, a window with nothing stored and a window of
+    negatives only."""
+    n = LDS_TABLE_CELLS
+    rng = np.random.default_rng(31)
+    x = np.zeros((n, 5))
+    x[:, 0] = rng.normal(0.0, 1.0, n)
+    assert np.unique(x[:, 0]).shape[0] == n and (x[:, 0] != 0).all()
+    x[:, 1] = run_column(n, 1025, CHUNK - 500, seed=4)
+    x[:, 2] = np.round(rng.normal(0.0, 0.5, n), 1) * (rng.random(n) < 0.4)
+    x[:, 4] = -np.abs(rng.normal(0.0, 1.0, n)) - 0.1
+    return x
+
+
+def group_codes(n, n_groups, n_untested, n_outside, seed):
+    """n codes in shuffled order: every tested group 0 .. G - 1 has a cell, the cells left over go to the first G // 500
+    groups (sizes from 1 to a few dozen), ``n_untested`` cells have the code G (ranked, in no tested group) and
+    ``n_outside`` the code -1."""
+    rng = np.random.default_rng(seed)
+    spare = n - n_groups - n_untested - n_outside
+    assert spare >= 0
+    code = np.concatenate([np.arange(n_groups), rng.integers(0, max(n_groups // 500, 1), size=spare),
+                           np.full(n_untested, n_groups), np.full(n_outside, -1)])
+    return code[rng.permutation(n)].astype(np.int64)
+
+
+def lds_table_cases():
+    """The number of codes, G tested groups and the code G of the rest, at and past what the rank sums keep in LDS: the
+    last LDS slot in use (G + 1 == LDS_GROUPS), one code more (the form with global atomics per entry), and far more with
+    cells outside the population."""
+    x = lds_table_matrix()
+    n = x.shape[0]
+    return [("groups_fill_the_lds_table", x, group_codes(n, LDS_GROUPS - 1, 100, 0, seed=41), LDS_GROUPS - 1),
+            ("groups_one_past_the_lds_table", x, group_codes(n, LDS_GROUPS, 100, 0, seed=42), LDS_GROUPS),
+            ("groups_far_past_the_lds_table", x, group_codes(n, 2200, 90, 5, seed=43), 2200)]
+
+
 def limit_cases():
     """[(name, x, code, n_groups)]: the limits of DESIGN.md 4.20; ``code`` as the engine binding takes it.  Every case is a
-    handful of columns of 1 to about 1 100 cells."""
+    handful of columns of 1 to about 2 300 cells."""
     cases = []
     rng = np.random.default_rng(7)
     # runs of equal values across the wavefront (64), workgroup-stride (256) and chunk (2048) positions of the sorted
@@ -262,4 +304,4 @@ def limit_cases():
     # a CSR row longer than one wavefront step, with an untested code among the tested
     wide = sp.csr_matrix(np.round(rng.normal(0, 1, (6, 200)), 1))
     cases.append(("rows_of_200_entries", wide, np.asarray([0, 1, 2, 0, 1, 2]), 2))
-    return cases
+    return cases + lds_table_cases()

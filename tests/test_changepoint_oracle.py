@@ -1,6 +1,7 @@
 """The oracle of tl.cnv_changepoints (tests/_changepoint_oracle.py) against a brute force over all
-segmentations, its scalar against its vectorised form, its fixed behaviours, the planted case, and everything the function
-and its two entry points refuse before they touch the device.  No GPU."""
+segmentations, its scalar against its vectorised form, its fixed behaviours, the lane model of the kernel with the mutants
+that each limit case tells apart, the planted case, and everything the function and its two entry points refuse before they
+touch the device.  No GPU."""
 import ctypes
 import functools
 import itertools
@@ -163,6 +164,159 @@ def test_values_that_could_overflow_are_refused():
     with pytest.raises(ValueError, match="beta"):
         co.cnv_changepoints(np.asarray([[0.0, 1.0, 1.0]]), chr_pos, sigma=1e150, penalty=1e10)
     assert co.cnv_changepoints(np.asarray([[0.0, 1e150, 1.0]]), chr_pos, sigma=0.1)["n_segments"].tolist() == [3]
+
+
+# ---- the lane model of the kernel, its mutants, and what each limit case tells apart ----------------------------------------------
+def _chromosomes(name):
+    """[(row number, chromosome number, its values as Python floats)] of a named case."""
+    c = co.expected(name)
+    edges = co.bounds(c["chr_pos"], c["x"].shape[1])
+    return [(r, k, row[s0:s1]) for r, row in enumerate(co.rows_of(c["x"]))
+            for k, (s0, s1) in enumerate(zip(edges[:-1], edges[1:]))]
+
+
+@pytest.mark.parametrize("name", co.EDGE_CASES)
+def test_the_lane_model_is_the_oracle_on_every_chromosome_of_the_limit_cases(name):
+    c = co.expected(name)
+    beta, m = c["want"]["beta"], c["kwargs"].get("min_windows", 1)
+    for r, k, xs in _chromosomes(name):
+        lane = co.lane_partition(xs, beta, m, "kernel")
+        for other in (co.partition(xs, beta, m), co.partition_vectorised(xs, beta, m)):
+            assert np.asarray(lane[0]).tobytes() == np.asarray(other[0]).tobytes(), (r, k)  # F bit for bit
+            assert lane[1] == other[1], (r, k)
+
+
+@functools.lru_cache(maxsize=None)
+def _rows_a_mutant_changes(name, mode):
+    """The rows of a named case whose starts or levels (bytes) differ when rule 3 is taken from the lane model in
+    ``mode``."""
+    c = co.expected(name)
+    got = co.cnv_changepoints(c["x"], c["chr_pos"], part=functools.partial(co.lane_partition, mode=mode), **c["kwargs"])
+    want = c["want"]
+    differs = (got["starts"] != want["starts"]).any(axis=1)
+    differs |= (got["levels"].view(np.int64) != want["levels"].view(np.int64)).any(axis=1)
+    return np.flatnonzero(differs).tolist()
+
+
+@pytest.mark.parametrize("name", co.EDGE_CASES + co.TIES_CASES[:3])
+def test_the_lane_model_gives_the_oracles_bytes(name):
+    assert _rows_a_mutant_changes(name, "kernel") == []
+
+
+@pytest.mark.parametrize("name, mode", [("ties_long", "lane_le"), ("ties_long", "lowest_lane"), ("ties_long_m2", "lane_le"),
+                                        ("ties_long_m2", "lowest_lane"), ("ties_long_m3_beta_eighth", "lowest_lane"),
+                                        ("clamp_constant_rows", "no_clamp"), ("clamp_constant_rows_tiny_beta", "no_clamp")]
+                         + [(name, "highest_i") for name in co.TIES_CASES if name not in co.TIES_CASES_WITHOUT_A_TIE])
+def test_every_mutant_of_the_lane_model_is_told_apart_by_its_case(name, mode):
+    """A kernel that made the mistake ``mode`` would fail the GPU comparison of ``name``: the mutant's starts or levels
+    differ from the oracle's in at least one row."""
+    rows = _rows_a_mutant_changes(name, mode)
+    print(f"{name}: {mode} changes the rows {rows}")
+    assert len(rows) >= 1
+
+
+def test_the_short_ties_case_cannot_tell_the_lanes_apart():
+    """Why the long cases exist: with at most 16 windows every lane has one candidate, in lanes 0 .. 15, where the lowest
+    lane is the lowest i -- neither mutant changes a byte of any of the three short cases."""
+    for name in co.TIES_CASES[:3]:
+        assert max(np.diff(co.bounds(co.expected(name)["chr_pos"], co.expected(name)["x"].shape[1]))) <= 16
+        assert _rows_a_mutant_changes(name, "lane_le") == [] and _rows_a_mutant_changes(name, "lowest_lane") == []
+
+
+@pytest.mark.parametrize("name", co.TIES_CASES_WITHOUT_A_TIE)
+def test_a_beta_that_is_no_multiple_of_a_quarter_leaves_no_tie_to_break(name):
+    """beta = c log(W) of "ties", "ties_m3" and "ties_long_m3" (sigma and penalty given, W = 45 or 458): F_j = cost + k beta
+    is rounded, two segmentations of one cost are rounded differently, and on these rows the best segmentation is the only
+    one in float64 -- not one candidate on the backtracked path equals the chosen one, so no rule for ties, right or wrong,
+    changes a byte.  "ties_long_m3_beta_eighth" is the m = 3 case with ties."""
+    c = co.expected(name)
+    beta, m = c["want"]["beta"], c["kwargs"].get("min_windows", 1)
+    assert beta > 0 and beta * 4 != round(beta * 4)
+    for mode in ("lane_le", "lowest_lane", "highest_i"):
+        assert _rows_a_mutant_changes(name, mode) == []
+    for r, k, xs in _chromosomes(name):  # the same, seen directly: the candidates of every j on the path
+        F, back, P = co.partition(xs, beta, m)
+        Q = co.prefix_chains(xs)[1]
+        for i, j in co.backtrack(back, len(xs)):
+            equal = [t for t in range(j) if co.admissible(t, j, len(xs), m)
+                     and (F[t] + co.segment_cost(P, Q, t, j)) + beta == F[j]]
+            assert equal == [i], (r, k, j)
+
+
+def test_the_limit_cases_hold_what_they_are_named_for():
+    lengths = lambda name: np.diff(co.bounds(co.expected(name)["chr_pos"], co.expected(name)["x"].shape[1])).tolist()
+    for name in ("ties_long", "ties_long_m2", "ties_long_m3", "ties_long_m3_beta_eighth"):
+        assert lengths(name) == [65, 129, 200, 64] and co.expected(name)["x"].shape[0] == 14
+    assert co.expected("ties_long")["want"]["beta"] == 0.0 == co.expected("ties_long_m2")["want"]["beta"]
+    assert co.expected("ties_long_m3_beta_eighth")["want"]["beta"] == 0.125
+    # the existing cases keep their bytes: exact_ties() without lengths is what it was
+    x, chr_pos = co.exact_ties()
+    assert x.shape == (14, 45) and sorted(chr_pos.values()) == [0, 12, 19, 20, 29]
+    assert (co.exact_ties((12, 7, 1, 9, 16))[0] != x).nnz == 0
+
+    # the clamp: twelve rows over 65 and 130 windows, beta = 0 and a beta of 5e-20
+    c = co.expected("clamp_constant_rows")
+    assert lengths("clamp_constant_rows") == [65, 130] and c["x"].shape == (12, 195) and c["want"]["beta"] == 0.0
+    dense = c["x"].toarray()
+    assert (dense[:6] == np.asarray(co.CLAMP_VALUES)[:, None]).all()
+    assert (dense[6:, :32] == dense[:6, :32]).all() and (dense[6:, 32:65] == 3 * dense[:6, 32:65]).all()
+    assert (dense[6:, 65:130] == dense[:6, 65:130]).all() and (dense[6:, 130:] == 3 * dense[:6, 130:]).all()
+    tiny = co.expected("clamp_constant_rows_tiny_beta")["want"]["beta"]
+    assert tiny == (1.0 * (1e-10 * 1e-10)) * math.log(195) == co.penalty_of(1.0, 1e-10, 195) and 5.2e-20 < tiny < 5.3e-20
+    fired = sum(1 for _, _, xs in _chromosomes("clamp_constant_rows") for P, Q in [co.prefix_chains(xs)]
+                for j in range(1, len(xs) + 1) for i in range(j)
+                if (Q[j] - Q[i]) - ((P[j] - P[i]) * (P[j] - P[i])) / float(j - i) < 0.0)
+    assert fired > 1000  # (the costs below 0.0 that the clamp meets)
+
+    # a unique minimum in every lane, in three rounds of k
+    c = co.expected("minimum_in_every_lane")
+    w = co.EVERY_LANE_WINDOWS
+    assert c["x"].shape == (w - 1, w) == (130, 131) and lengths("minimum_in_every_lane") == [w]
+    assert c["want"]["beta"] == (1.0 * (0.25 * 0.25)) * math.log(w)
+    lanes, rows = set(), co.rows_of(c["x"])
+    for r in range(1, w):
+        xs = rows[r - 1]
+        assert xs == [0.0] * r + [1.0] * (w - r)
+        F, back, P = co.partition(xs, c["want"]["beta"], 1)
+        Q = co.prefix_chains(xs)[1]
+        v = [(F[i] + co.segment_cost(P, Q, i, w)) + c["want"]["beta"] for i in range(w)]
+        assert back[w] == r and sorted(v)[0] == v[r] < sorted(v)[1]  # candidate k = i = r, and no other equals it
+        assert np.flatnonzero(c["want"]["starts"][r - 1]).tolist() == [0, r]
+        lanes.add((r % co.LANES, r // co.LANES))
+    assert {lane for lane, _ in lanes} == set(range(co.LANES)) and {t for _, t in lanes} == {0, 1, 2}
+    assert all((lane, 1) in lanes for lane in range(co.LANES))  # the second round of k meets every lane
+
+    # values at the bound of rule 7
+    c = co.expected("values_at_the_refusal_bound")
+    a, w = co.REFUSAL_BOUND_A, co.REFUSAL_BOUND_WINDOWS
+    dense = c["x"].toarray()
+    assert dense.shape == (5, w) and lengths("values_at_the_refusal_bound") == [w] and c["want"]["beta"] == 0.0
+    assert np.abs(dense).max() == a and 4e306 < (a * w) * (a * w) < math.inf and math.isfinite((a * a) * w)
+    assert set(np.unique(np.abs(dense[:3]))) == {0.0, a / 2, a}
+    assert 0 < 1e-160 * 1e-160 < 2.3e-308 and 5e-324 * 5e-324 == 0.0  # subnormal squares, and squares that vanish
+    assert np.isfinite(c["want"]["levels"]).all()
+    assert c["want"]["n_segments"][4] == 1 and (c["want"]["n_segments"][:4] > 10).all()
+    co.check_values(co.rows_of(c["x"]), 0.0)  # accepted
+    dense[0, 0] = 3e152
+    with pytest.raises(ValueError, match="magnitude 3e\\+152"):
+        co.check_values(co.rows_of(dense), 0.0)
+    with pytest.raises(ValueError, match="magnitude 3e\\+152"):
+        co.cnv_changepoints(dense, c["chr_pos"], **c["kwargs"])
+
+
+def test_shuffled_rows_hold_the_same_matrix_in_another_order():
+    for name in ("mixed_n3", "ties_long"):
+        x = co.expected(name)["x"]
+        indptr, indices, data = co.shuffled_rows(x, seed=5)
+        assert (indptr == x.indptr).all() and indices.dtype == np.int32 and data.dtype == np.float64
+        out_of_order = 0
+        for r in range(x.shape[0]):
+            a, b = indptr[r], indptr[r + 1]
+            assert len(set(indices[a:b].tolist())) == b - a  # unique columns
+            order = np.argsort(indices[a:b], kind="stable")
+            assert (indices[a:b][order] == x.indices[a:b]).all() and data[a:b][order].tobytes() == x.data[a:b].tobytes()
+            out_of_order += int((np.diff(indices[a:b]) < 0).any())
+        assert out_of_order >= x.shape[0] - 2  # (an empty row or a row of one entry cannot be out of order)
 
 
 # ---- the planted case ----------------------------------------------------------------------------------------------------------

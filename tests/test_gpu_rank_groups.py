@@ -1,6 +1,7 @@
 """tl.cnv_rank_groups on the GPU equals the oracle of DESIGN.md 4.20 (tests/_rank_oracle.py): the int64 tables R2 and T
 exactly and the float64 results on the bytes, for every kind of input, at the limits of the kernels (runs of equal values
-across every boundary of the rank-sum kernel, zeros of both signs, one-sided columns, extreme values, tiny populations),
+across every boundary of the rank-sum kernel, zeros of both signs, one-sided columns, extreme values, tiny populations,
+as many groups as the LDS table of the rank sums holds and more, where the sums go to global atomics),
 for any cut of the windows into tiles; non-finite values raise; the planted clones are found."""
 import functools
 
@@ -192,6 +193,19 @@ def test_the_limit_cases_hold_what_they_are_for():
         assert np.searchsorted(col, 2.0, side="left") < ro.CHUNK < np.searchsorted(col, 2.0, side="right")
     _, x, _, _ = by_name["rows_of_200_entries"]
     assert np.diff(x.indptr).max() > 2 * ro.WAVE
+    # the codes at and past the LDS table of the rank sums: G tested groups and the code G of the cells in none of them
+    for name, fills in (("groups_fill_the_lds_table", True), ("groups_one_past_the_lds_table", False),
+                        ("groups_far_past_the_lds_table", False)):
+        _, x, code, g = by_name[name]
+        assert (g + 1 == ro.LDS_GROUPS) if fills else (g + 1 > ro.LDS_GROUPS)
+        n_pop = int((code >= 0).sum())
+        assert x.shape[0] >= n_pop > ro.CHUNK and (x[code >= 0, 0] != 0).all()  # window 0: a segment of two chunks
+        sizes = np.bincount(code[(code >= 0) & (code < g)], minlength=g)
+        assert sizes.min() >= 1 and sizes.max() > 2 and int(code.max()) == g and 90 <= int((code == g).sum()) <= 110
+        col = np.sort(x[code >= 0, 1])
+        assert np.searchsorted(col, 2.0, side="left") < ro.CHUNK < np.searchsorted(col, 2.0, side="right")
+    assert by_name["groups_one_past_the_lds_table"][3] == ro.LDS_GROUPS
+    assert (by_name["groups_far_past_the_lds_table"][2] == -1).sum() == 5
 
 
 # ---- tiles -------------------------------------------------------------------------------------------------------------------
@@ -213,6 +227,15 @@ def test_any_cut_into_window_tiles_gives_the_same_tables():
     info = {}
     r2, tie, _ = _tables(c["x"], want["code"], 4, max_entries=1, info=info)
     assert info["n_tiles"] >= 3 and (r2 == want["R2"]).all() and (tie == want["T"]).all()
+
+
+def test_window_tiles_feed_the_same_global_tables_past_the_lds_table():
+    """G + 1 = 2049 codes: every tile's rank sums go to the global tables entry by entry, and the tiles add up."""
+    (_, x, code, g), = [c for c in LIMITS if c[0] == "groups_one_past_the_lds_table"]
+    want_r2, want_tie, _ = ro.tables(x, code, g)
+    info = {}
+    r2, tie, _ = _tables(x, code, g, max_entries=1, info=info)
+    assert info["n_tiles"] >= 3 and (r2 == want_r2).all() and (tie == want_tie).all()
 
 
 # ---- non-finite input ------------------------------------------------------------------------------------------------------

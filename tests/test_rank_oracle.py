@@ -61,6 +61,33 @@ def test_doubled_rank_sums_equal_twice_scipys_average_ranks(case):
         assert int(tie[j]) == int((c.astype(np.int64) ** 3 - c).sum())
 
 
+@pytest.mark.parametrize("case", range(3))
+def test_the_cases_at_the_lds_table_equal_twice_scipys_average_ranks(case):
+    """The oracle's tables of the three cases with about 2 048 groups (tests/test_gpu_rank_groups.py compares the kernels
+    with them) against scipy's ranks, and what the cases are built to hold."""
+    name, x, code, g = ro.lds_table_cases()[case]
+    assert name == ("groups_fill_the_lds_table", "groups_one_past_the_lds_table", "groups_far_past_the_lds_table")[case]
+    assert x.shape == (ro.LDS_TABLE_CELLS, 5) and x.dtype == np.float64 and code.shape == (x.shape[0],)
+    assert g + 1 == (ro.LDS_GROUPS, ro.LDS_GROUPS + 1, 2201)[case] and int(code.max()) == g
+    assert int((code == -1).sum()) == (0, 0, 5)[case] and int(code.min()) == (0, 0, -1)[case]
+    n_pop = int((code >= 0).sum())
+    assert n_pop > ro.CHUNK
+    sizes = np.bincount(code[(code >= 0) & (code < g)], minlength=g)
+    assert sizes.min() >= 1 and sizes.max() > 2
+    pop, group = x[code >= 0], code[code >= 0]
+    assert (pop[:, 0] != 0).all() and 0.3 < (pop[:, 2] != 0).mean() < 0.5 and (pop[:, 2] < 0).any() and (pop[:, 2] > 0).any()
+    assert (pop[:, 3] == 0).all() and (pop[:, 4] < 0).all()
+    r2, tie, flags = ro.tables(x, code, g)
+    assert flags == 0 and r2.shape == (g, 5)
+    ranks2 = 2.0 * scipy.stats.rankdata(pop, method="average", axis=0)
+    want = np.zeros((g + 1, 5), dtype=np.int64)
+    np.add.at(want, group, ranks2.astype(np.int64))
+    assert (ranks2 == np.rint(ranks2)).all() and (r2 == want[:g]).all()
+    assert (r2.sum(axis=0) + want[g] == n_pop * (n_pop + 1)).all() and (want[g] > 0).all()  # the untested cells hold ranks
+    run = int((pop[:, 1] == 2.0).sum())  # (the run ends with the column: what of the 1 025 fits behind CHUNK - 500 values)
+    assert run > 700 and tie[0] == 0 and tie[1] == run ** 3 - run and tie[3] == n_pop ** 3 - n_pop and tie[2] > 0
+
+
 def test_a_stored_minus_zero_is_the_zero_and_dropped_groups_stay_in_the_rest():
     x = sp.csr_matrix((np.asarray([-0.0, 0.0, -0.0, 2.0]), np.asarray([0, 0, 0, 0]), np.asarray([0, 1, 2, 3, 4])), shape=(4, 1))
     r2, tie, _ = ro.tables(x, np.asarray([0, 1, 0, 1]), 2)
@@ -263,7 +290,7 @@ def test_symbols_are_exported_declared_and_bound():
     assert "cnv_rank_groups" in cnv.tl.__all__ and callable(cnv.tl.cnv_rank_groups)
     source = open(os.path.join(ROOT, "infercnvpy_amd", "csrc", "icv_rank.hpp")).read()
     for name, value in (("kRkSumThreads", ro.SUM_THREADS), ("kRkChunk", ro.CHUNK), ("kRkSlab", ro.SLAB),
-                        ("kRkTile", ro.TILE)):
+                        ("kRkTile", ro.TILE), ("kRkLdsGroups", ro.LDS_GROUPS)):
         assert f"{name} = {value};" in source  # (the sizes the limit cases are built around)
     assert f"#define ICV_RANK_MAX_CELLS (1 << 21)" in header and _lib.ICV_RANK_MAX_CELLS == ro.MAX_CELLS == 1 << 21
 
