@@ -790,6 +790,32 @@ int icv_rank_sums(const uint64_t *keys, const int32_t *payload, const int32_t *s
 int icv_rank_finish(const int32_t *stored, const int32_t *neg, const int32_t *cnt, const int64_t *n_cells, int64_t n_groups,
                     int32_t n_cols, int64_t n_pop, int64_t *r2, int64_t *tie, void *stream);
 
+/* ---- tl.cnv_pool_neighbors: the exact mean of every row with the rows of its graph neighbours ------------
+ * The graph is a device CSR structure of n vertices: g_indptr (device int64, n + 1, from 0, non-decreasing: trusted) and
+ * g_indices (device int32, g_indptr[n] entries; never null, whatever the number of entries).  Its values are not an
+ * argument: only the structure is read, and it need not be symmetric.  The neighbourhood of row i is
+ * N(i) = {i} u {g_indices[e] : g_indptr[i] <= e < g_indptr[i + 1]}; an explicit diagonal entry does not count i twice, an
+ * empty row gives {i}, a row may have any length.  Both entries enqueue on the stream and synchronise nothing.
+ * icv_neighbor_pool_sizes: n_cells[i] (device int32, n) = L_i = |N(i)|.  *flags (device int32) is set to 0; then bit 1
+ * (value 2) is set where a column lies outside [0, n) (it is not counted) and bit 2 (value 4) where the columns of a row
+ * do not ascend strictly (a repeated column is counted twice: refuse such a graph).
+ * icv_neighbor_pool: m as for icv_group_profiles (stored values are used as float64, an entry that is not stored is 0, a
+ * stored 0.0 or -0.0 adds nothing; CSR columns need not be sorted but are unique within a row; a column outside
+ * [0, n_cols) is passed over) with m->n_rows == n.  With q = rint(v 2^shift), ties to even, as int64, and S[i,w] the int64
+ * sum of q over the rows of N(i): out[i * ldo + w] (device float64, n rows of ldo >= n_cols elements, 8-byte aligned) =
+ * (double(S) / double(n_cells[i])) 2^-shift -- the conversion rounds to nearest even, the division is correctly rounded,
+ * the scaling exact; S = 0 gives +0.0.  The caller chooses shift in [0, 40] so that 2^(10 + shift) max(L_i) stays below
+ * 2^62 (min(40, 52 - bit_length(max L_i)) with every stored magnitude below 2^10) and passes the n_cells of
+ * icv_neighbor_pool_sizes.  *flags is NOT reset: bit 0 (value 1) is set where a value that was read is not finite (it adds
+ * nothing), bit 1 where a graph column lies outside [0, n) (skipped, never dereferenced).  Every output element is written
+ * exactly once with plain stores; nothing of the size of the output is allocated.  n_cols has no limit.
+ * Both return ICV_ERR_INVALID, before anything is launched, for a null pointer, n < 1 and, icv_neighbor_pool, n_cols < 1,
+ * a shift outside [0, 40], ldo < n_cols, a format / dtype that does not exist, a dense ld < n_cols and m->n_rows != n. */
+int icv_neighbor_pool_sizes(const int64_t *g_indptr, const int32_t *g_indices, int64_t n, int32_t *n_cells, int32_t *flags,
+                            void *stream);
+int icv_neighbor_pool(const icv_matrix *m, const int64_t *g_indptr, const int32_t *g_indices, int64_t n, int32_t shift,
+                      const int32_t *n_cells, double *out, int64_t ldo, int32_t *flags, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

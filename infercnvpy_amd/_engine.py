@@ -2023,6 +2023,58 @@ def group_profiles_finish(total, stored, d_ptr, shift):
     return mean, fraction
 
 
+# ---- tl.cnv_pool_neighbors: exact means over every cell's graph neighbourhood (icv_neighbor_pool*) ----------
+POOL_FLAG_NONFINITE, POOL_FLAG_COLUMN, POOL_FLAG_ORDER = 1, 2, 4
+
+
+def neighbor_pool_graph(who, indptr, indices, data=None):
+    """(indptr, indices): the structure of a device CSR graph as contiguous int64 / int32 CUDA tensors whose row pointers
+    the kernels may trust (:func:`_graph_csr`); the ``indices`` of a graph without entries are one unused element, so that
+    they have an address.  The values are not looked at beyond their number."""
+    torch = _torch()
+    if not (indptr.is_cuda and indices.is_cuda and indptr.dtype == torch.int64 and indices.dtype == torch.int32
+            and indptr.dim() == 1 and indices.dim() == 1):
+        raise ValueError(f"{who}: a device graph is (indptr int64, indices int32, data) of 1-D CUDA tensors")
+    if data is not None and data.numel() != indices.numel():
+        raise ValueError(f"{who}: the graph has {indices.numel()} columns and {data.numel()} values")
+    indptr, indices, _, _, nnz = _graph_csr(who, indptr, indices, indices, (torch.int32,))
+    if nnz == 0:  # (a tensor of no elements has no address: one element that nothing reads)
+        indices = torch.zeros(1, dtype=torch.int32, device=indptr.device)
+    return indptr, indices
+
+
+def neighbor_pool_sizes(indptr, indices):
+    """(n_cells, flags): the device int32 sizes L_i of rule 2 and the device int32 flag word (POOL_FLAG_COLUMN: a column
+    outside [0, n); POOL_FLAG_ORDER: a row that does not ascend strictly) of the graph of :func:`neighbor_pool_graph`.
+    Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    n = int(indptr.numel()) - 1
+    with torch.cuda.device(indptr.device):
+        n_cells = torch.empty(n, dtype=torch.int32, device="cuda")
+        flags = torch.empty(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.icv_neighbor_pool_sizes(_ptr(indptr), _ptr(indices), n, _ptr(n_cells), _ptr(flags),
+                                               _stream_ptr(torch)))
+    return n_cells, flags
+
+
+def neighbor_pool(dm: DeviceMatrix, indptr, indices, shift, n_cells, flags, out=None):
+    """The device float64 ``n x W`` matrix of rules 1, 4 and 5 for ``dm`` and the graph and sizes of
+    :func:`neighbor_pool_sizes`; POOL_FLAG_NONFINITE is added to ``flags`` where a value is not finite.  ``out``: a
+    contiguous result to write into.  Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    n, w = int(dm.shape[0]), int(dm.shape[1])
+    with torch.cuda.device(dm.device):
+        if out is None:
+            out = torch.empty((n, w), dtype=torch.float64, device="cuda")
+        assert out.is_cuda and out.dtype == torch.float64 and out.shape == (n, w) and out.is_contiguous()
+        m = dm.c_struct()
+        _lib.check(lib.icv_neighbor_pool(C.byref(m), _ptr(indptr), _ptr(indices), int(indptr.numel()) - 1, int(shift),
+                                         _ptr(n_cells), _ptr(out), w, _ptr(flags), _stream_ptr(torch)))
+    return out
+
+
 # ---- tl.cnv_correlation / tl.cnv_signal: rows against centred profiles on the device (icv_profile_corr*, DESIGN.md 4.18) ------
 def profile_corr(dm: DeviceMatrix, centred=None, s2=None):
     """(A, B, signal, r, flags): device float64 vectors of rule 2's row sums and of ``B / W``, the device float64 ``n x G``

@@ -56,6 +56,7 @@ EXPORTS = (
     "icv_profile_corr", "icv_profile_corr_best",
     "icv_changepoint_levels", "icv_changepoint_diffsq",
     "icv_rank_count", "icv_rank_scatter", "icv_rank_sort", "icv_rank_sums", "icv_rank_finish",
+    "icv_neighbor_pool_sizes", "icv_neighbor_pool",
 )
 
 
@@ -214,6 +215,8 @@ def load():
     lib.icv_rank_sort.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp]
     lib.icv_rank_sums.argtypes = [vp, vp, vp, i32, i32, i32, i32, i64, i32, vp, vp, vp, vp, vp]
     lib.icv_rank_finish.argtypes = [vp, vp, vp, vp, i64, i32, i64, vp, vp, vp]
+    lib.icv_neighbor_pool_sizes.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.icv_neighbor_pool.argtypes = [P(Matrix), vp, vp, i64, i32, vp, vp, i64, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

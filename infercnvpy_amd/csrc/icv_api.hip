@@ -52,6 +52,7 @@
 #include "icv_profile_corr.hpp"
 #include "icv_changepoint.hpp"
 #include "icv_rank.hpp"
+#include "icv_pool.hpp"
 #include "icv_ward.hpp"
 #include "icv_ward_strip.hpp"
 #include "icv_plan.hpp"
@@ -4400,6 +4401,44 @@ int icv_rank_finish(const int32_t* stored, const int32_t* neg, const int32_t* cn
         return fail(ICV_ERR_UNSUPPORTED, "rank_finish: too many groups x windows for one call");
     hipLaunchKernelGGL(icv::k_rank_finish, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), stored, neg,
                        cnt, n_cells, n_groups, n_cols, n_pop, r2, tie);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_pool_neighbors: exact means over every cell's graph neighbourhood -------------------------------
+static_assert((size_t)icv::kPoolTile * 8 <= 16 * 1024, "a tile's sums take 16 KB of LDS: ten workgroups per CU");
+static_assert(icv::kPoolTile % 2 == 0, "a tile starts at an even window: the 16-byte stores pair windows from there");
+
+int icv_neighbor_pool_sizes(const int64_t* g_indptr, const int32_t* g_indices, int64_t n, int32_t* n_cells, int32_t* flags,
+                            void* stream) {
+    if (!g_indptr || !g_indices || n < 1 || !n_cells || !flags)
+        return fail(ICV_ERR_INVALID, "bad neighbor_pool_sizes arguments");
+    constexpr int64_t rows_per_block = icv::kPoolThreads / 64;
+    const int64_t blocks = (n + rows_per_block - 1) / rows_per_block;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "neighbor_pool_sizes: too many cells for one call");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(icv::k_pool_sizes, dim3((unsigned)blocks), dim3(icv::kPoolThreads), 0, st, g_indptr, g_indices, n,
+                       n_cells, flags);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_neighbor_pool(const icv_matrix* m, const int64_t* g_indptr, const int32_t* g_indices, int64_t n, int32_t shift,
+                      const int32_t* n_cells, double* out, int64_t ldo, int32_t* flags, void* stream) {
+    if (!matrix_header_ok(m) || !g_indptr || !g_indices || n < 1 || m->n_rows != n || m->n_cols < 1 || shift < 0 ||
+        shift > icv::kPbMaxShift || !n_cells || !out || ldo < m->n_cols || !flags ||
+        (m->format == ICV_DENSE && m->ld < m->n_cols) || !matrix_complete(m))
+        return fail(ICV_ERR_INVALID, "bad neighbor_pool arguments");
+    const int64_t n_tiles = ((int64_t)m->n_cols + icv::kPoolTile - 1) / icv::kPoolTile;
+    if (n > kSegMaxBlocks / n_tiles) return fail(ICV_ERR_UNSUPPORTED, "neighbor_pool: too many cells x windows for one call");
+    const dim3 grid((unsigned)(n * n_tiles)), block(icv::kPoolThreads);
+    by_matrix(m, [&](auto t, auto csr) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((icv::k_neighbor_pool<T, decltype(csr)::value>), grid, block, 0, static_cast<hipStream_t>(stream),
+                           (const T*)m->values, m->indptr, m->indices, m->ld, n, m->n_cols, g_indptr, g_indices,
+                           (uint32_t)n_tiles, (int)shift, n_cells, out, ldo, flags);
+    });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }

@@ -7,6 +7,7 @@ from ._pca import pca
 from ._tsne import tsne
 from ._umap import umap
 from ._linkage import cell_linkage, leaves_list, ward_linkage
+from ._pool import cnv_pool_neighbors
 from ._posteriors import cnv_posteriors, cnv_states_filter
 from ._pseudobulk import cnv_pseudobulk
 from ._rank import cnv_rank_groups
@@ -14,4 +15,4 @@ from ._scores import cnv_score, ithcna, ithgex
 from ._segments import cnv_segments
 from ._states import cnv_states
 
-__all__ = ["infercnv", "infercnv_device", "pca", "leiden", "umap", "tsne", "cnv_score", "cnv_states", "cnv_states_fit", "cnv_segments", "cnv_pseudobulk", "cnv_rank_groups", "cnv_correlation", "cnv_signal", "cnv_changepoints", "cnv_posteriors", "cnv_states_filter", "ithcna", "ithgex", "cell_linkage", "ward_linkage", "leaves_list"]
+__all__ = ["infercnv", "infercnv_device", "pca", "leiden", "umap", "tsne", "cnv_score", "cnv_states", "cnv_states_fit", "cnv_segments", "cnv_pseudobulk", "cnv_pool_neighbors", "cnv_rank_groups", "cnv_correlation", "cnv_signal", "cnv_changepoints", "cnv_posteriors", "cnv_states_filter", "ithcna", "ithgex", "cell_linkage", "ward_linkage", "leaves_list"]

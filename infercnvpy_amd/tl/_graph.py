@@ -15,19 +15,27 @@ def _is_tensor(x):
     return type(x).__module__.split(".")[0] == "torch"
 
 
-def _graph(adata, neighbors_key, adjacency, obsp):
+def graph_source(adata, neighbors_key, adjacency, obsp, which="connectivities_key"):
+    """Where the graph comes from: "adjacency", or the key of ``adata.obsp`` (``obsp``, else the one that
+    ``adata.uns[neighbors_key][which]`` names).  ``KeyError`` for a key that is not there."""
     if adjacency is not None:
-        return adjacency
+        return "adjacency"
     if obsp is not None:
         if obsp not in adata.obsp:
             raise KeyError(f"{obsp!r} is not in adata.obsp. Did you run `pp.neighbors`?")
-        return adata.obsp[obsp]
+        return obsp
     if neighbors_key not in adata.uns:
         raise KeyError(f"{neighbors_key!r} is not in adata.uns. Did you run `pp.neighbors`?")
-    key = adata.uns[neighbors_key]["connectivities_key"]
+    key = adata.uns[neighbors_key][which]
     if key not in adata.obsp:
         raise KeyError(f"{key!r} is not in adata.obsp. Did you run `pp.neighbors`?")
-    return adata.obsp[key]
+    return key
+
+
+def _graph(adata, neighbors_key, adjacency, obsp, which="connectivities_key"):
+    if adjacency is not None:
+        return adjacency
+    return adata.obsp[graph_source(adata, neighbors_key, adjacency, obsp, which)]
 
 
 def _host_csr(g, who="tl.leiden"):
@@ -45,10 +53,11 @@ def _host_csr(g, who="tl.leiden"):
     return a.indptr.astype(np.int64), a.indices.astype(np.int32), np.ascontiguousarray(data)
 
 
-def resolve_graph(who, adata, neighbors_key, adjacency, obsp):
+def resolve_graph(who, adata, neighbors_key, adjacency, obsp, which="connectivities_key"):
     """(host, dev, n): the graph as the host arrays of :func:`_host_csr` (scipy matrix) or as the caller's tuple of CUDA
-    tensors (the other one is None), and its number of vertices, which must be ``adata.n_obs``."""
-    g = _graph(adata, neighbors_key, adjacency, obsp)
+    tensors (the other one is None), and its number of vertices, which must be ``adata.n_obs``.  ``which``: the entry of
+    ``adata.uns[neighbors_key]`` that names the default graph."""
+    g = _graph(adata, neighbors_key, adjacency, obsp, which)
     host = dev = None
     if isinstance(g, (tuple, list)) and len(g) == 3 and all(_is_tensor(t) for t in g):
         dev = g
