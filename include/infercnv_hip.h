@@ -816,6 +816,26 @@ int icv_neighbor_pool_sizes(const int64_t *g_indptr, const int32_t *g_indices, i
 int icv_neighbor_pool(const icv_matrix *m, const int64_t *g_indptr, const int32_t *g_indices, int64_t n, int32_t shift,
                       const int32_t *n_cells, double *out, int64_t ldo, int32_t *flags, void *stream);
 
+/* ---- tl.cnv_copy_states: multi-level copy-number calls of X_cnv by a K-state Viterbi chain ------------------
+ * icv_copy_states_viterbi: rules 2-5 of the contract.  m and chr_start as for icv_states_viterbi.  levels (HOST pointer to
+ * n_levels doubles, 2 <= n_levels <= 8, read before the call returns and passed to the kernel by value) holds the state
+ * means: finite, strictly ascending, levels[neutral] == 0 (a -0.0 is used as 0.0), 0 <= neutral < n_levels.
+ * h = 1 / (2 sigma^2) > 0, stay = log(1 - p) and sw = log(p / (n_levels - 1)) are the host's doubles, all finite.
+ * states (device int8, n_rows x n_cols row-major, no padding) receives state - neutral, in
+ * [-neutral, n_levels - 1 - neutral]; sign (the same layout) receives states clipped to -1 / 0 / +1, the format of
+ * icv_states_viterbi; nonneutral[i] (device int32) the number of windows of row i that are not 0.  With the levels
+ * (-a, 0, a) all three equal what icv_states_viterbi gives for the amplitude a, byte for byte.  One wavefront per row,
+ * 10 bytes of LDS per window: 1 <= n_cols <= ICV_COPY_STATES_MAX_WINDOWS.  ICV_ERR_INVALID, with the rule in
+ * icv_last_error and before anything is launched, for a null pointer, n_cols outside that range, n_chr outside
+ * [1, n_cols], n_levels outside [2, 8], a neutral that is no index of a level or whose level is not 0, a level that is
+ * not finite, levels that do not ascend strictly, an h that is not finite and > 0, a stay or sw that is not finite, and
+ * an incomplete matrix.  No rows: ICV_OK, nothing is launched.  The result is a pure function of the arguments.  No
+ * synchronisation. */
+#define ICV_COPY_STATES_MAX_WINDOWS 16384
+int icv_copy_states_viterbi(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, const double *levels,
+                            int32_t n_levels, int32_t neutral, double h, double stay, double sw, int8_t *states,
+                            int8_t *sign, int32_t *nonneutral, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -1818,13 +1818,14 @@ def _hmm_call(entry, dm: DeviceMatrix, chr_start, scalars, outputs):
     """The call shape of the three chain kernels: ``chr_start`` (host int32 array of C + 1 ascending window numbers from 0
     to W) is uploaded, ``outputs(torch)`` allocates the tuple of result tensors (None for one that is not wanted) on
     ``dm``'s device, and ``entry(matrix, chr_start, C, *scalars, *outputs, stream)`` is enqueued on the current stream
-    (a scalar that is an int is passed as one, every other as a float).  Returns the outputs; nothing is read back."""
+    (a scalar that is an int or a ctypes array is passed as it is, every other as a float).  Returns the outputs; nothing
+    is read back."""
     torch = _torch()
     with torch.cuda.device(dm.device):
         cs, n_chr = _chr_start_upload(torch, chr_start)
         out = outputs(torch)
         m = dm.c_struct()
-        _lib.check(entry(C.byref(m), _ptr(cs), n_chr, *(v if isinstance(v, int) else float(v) for v in scalars),
+        _lib.check(entry(C.byref(m), _ptr(cs), n_chr, *(v if isinstance(v, (int, C.Array)) else float(v) for v in scalars),
                          *(_ptr(t) for t in out), _stream_ptr(torch)))
     return out
 
@@ -1836,6 +1837,19 @@ def states_viterbi(dm: DeviceMatrix, chr_start, *, amplitude, h, stay, sw):
     n, w = dm.shape
     return _hmm_call(_lib.load().icv_states_viterbi, dm, chr_start, (amplitude, h, stay, sw), lambda torch: (
         torch.empty((n, w), dtype=torch.int8, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")))
+
+
+def copy_states_viterbi(dm: DeviceMatrix, chr_start, *, levels, neutral, h, stay, sw):
+    """(states, sign, nonneutral): device int8 ``n x W`` of ``state - neutral``, the same clipped to -1 / 0 / +1, and
+    device int32 counts of the windows that are not 0 (DESIGN.md 4.22 rules 2-5).  ``levels``: the K state means (host
+    floats, ``levels[neutral] == 0``); ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The
+    launch is enqueued on the current stream; nothing is read back."""
+    n, w = dm.shape
+    mu = (C.c_double * len(levels))(*(float(v) for v in levels))
+    return _hmm_call(_lib.load().icv_copy_states_viterbi, dm, chr_start, (mu, len(levels), int(neutral), h, stay, sw),
+                     lambda torch: (torch.empty((n, w), dtype=torch.int8, device="cuda"),
+                                    torch.empty((n, w), dtype=torch.int8, device="cuda"),
+                                    torch.empty(n, dtype=torch.int32, device="cuda")))
 
 
 def states_fraction(count, n_windows):

@@ -22,6 +22,7 @@ ICV_FLAG_ROUND_F32 = 2
 ICV_FLAG_NO_APPLY = 4
 ICV_GRAM_BLOCK = 8192  # rows per split-K block of icv_gram_f64 (include/infercnv_hip.h)
 ICV_STATES_MAX_WINDOWS = 16384  # windows icv_states_viterbi keeps in LDS per cell (include/infercnv_hip.h)
+ICV_COPY_STATES_MAX_WINDOWS = 16384  # windows icv_copy_states_viterbi keeps in LDS per cell (include/infercnv_hip.h)
 ICV_POSTERIOR_MAX_WINDOWS = 4096  # windows icv_posterior_chains keeps in LDS per cell (include/infercnv_hip.h)
 ICV_CHANGEPOINT_MAX_CHR_WINDOWS = 4096  # windows of one chromosome icv_changepoint_levels keeps in LDS (include/infercnv_hip.h)
 ICV_RANK_MAX_CELLS = 1 << 21  # cells icv_rank_sums ranks against each other: N^3 in an int64 (include/infercnv_hip.h)
@@ -57,6 +58,7 @@ EXPORTS = (
     "icv_changepoint_levels", "icv_changepoint_diffsq",
     "icv_rank_count", "icv_rank_scatter", "icv_rank_sort", "icv_rank_sums", "icv_rank_finish",
     "icv_neighbor_pool_sizes", "icv_neighbor_pool",
+    "icv_copy_states_viterbi",
 )
 
 
@@ -217,6 +219,7 @@ def load():
     lib.icv_rank_finish.argtypes = [vp, vp, vp, vp, i64, i32, i64, vp, vp, vp]
     lib.icv_neighbor_pool_sizes.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.icv_neighbor_pool.argtypes = [P(Matrix), vp, vp, i64, i32, vp, vp, i64, vp, vp]
+    lib.icv_copy_states_viterbi.argtypes = [P(Matrix), vp, i32, P(dbl), i32, i32, dbl, dbl, dbl, vp, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -45,6 +45,7 @@
 #include "icv_umap.hpp"
 #include "icv_tsne.hpp"
 #include "icv_states.hpp"
+#include "icv_copy_states.hpp"
 #include "icv_segments.hpp"
 #include "icv_hmmfit.hpp"
 #include "icv_posterior.hpp"
@@ -3868,10 +3869,11 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
 
 }  // extern "C"
 
-// ---- the chain kernels of the three-state model (csrc/icv_hmm.hpp): what their three entry points share ---------------------
+// ---- the chain kernels of the HMM functions (csrc/icv_hmm.hpp): what their entry points share --------------------------------
 namespace {
 
-// The argument checks of icv_states_viterbi, icv_posterior_chains and icv_posterior_stats, in the order they are reported.
+// The argument checks of icv_states_viterbi, icv_posterior_chains, icv_posterior_stats and icv_copy_states_viterbi, in the
+// order they are reported.
 // who: the entry point without icv_; outputs_ok: its own pointers; cap, lds_per_window: its window cap and the LDS bytes a
 // window takes; params_ok, params_rule: its verdict on the model's scalars and the words for it.
 int hmm_check(const std::string& who, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, bool outputs_ok, int cap,
@@ -4441,6 +4443,60 @@ int icv_neighbor_pool(const icv_matrix* m, const int64_t* g_indptr, const int32_
     });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
+}
+
+}  // extern "C"
+
+// ---- tl.cnv_copy_states: the K-state Viterbi chain -----------------------------------------------------------
+static_assert(icv::kCsMaxWindows == ICV_COPY_STATES_MAX_WINDOWS, "the header's window cap is the kernel's");
+static_assert((size_t)icv::kCsMaxWindows * icv::kCsLdsPerWindow <= (size_t)icv::kLdsLimit, "one cell fits a CU's LDS");
+
+namespace {
+
+// what is wrong with the model of icv_copy_states_viterbi, in the order it is reported; nullptr when nothing is
+const char* cs_params_fault(const double* levels, int32_t n_levels, int32_t neutral, double h, double stay, double sw) {
+    if (n_levels < 2 || n_levels > icv::kCsMaxStates) return "n_levels must lie in [2, 8]";
+    if (neutral < 0 || neutral >= n_levels) return "neutral must be the index of a level";
+    for (int32_t k = 0; k < n_levels; ++k)
+        if (!std::isfinite(levels[k])) return "the levels must be finite";
+    for (int32_t k = 1; k < n_levels; ++k)
+        if (!(levels[k] > levels[k - 1])) return "the levels must ascend strictly";
+    if (levels[neutral] != 0.0) return "levels[neutral] must be 0";
+    if (!(std::isfinite(h) && h > 0.0 && std::isfinite(stay) && std::isfinite(sw)))
+        return "h must be finite and > 0, stay and sw finite";
+    return nullptr;
+}
+
+template <int K>
+int cs_launch(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const icv::CsParams& P, int8_t* states,
+              int8_t* sign, int32_t* nonneutral, void* stream) {
+    return hmm_launch([](auto t, auto csr) { return icv::k_copy_states_viterbi<decltype(t), decltype(csr)::value, K>; }, m,
+                      chr_start, n_chr, icv::cs_lds_bytes(m->n_cols), stream, P, states, sign, nonneutral);
+}
+
+}  // namespace
+
+extern "C" {
+
+int icv_copy_states_viterbi(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const double* levels,
+                            int32_t n_levels, int32_t neutral, double h, double stay, double sw, int8_t* states,
+                            int8_t* sign, int32_t* nonneutral, void* stream) {
+    const char* fault = levels ? cs_params_fault(levels, n_levels, neutral, h, stay, sw) : nullptr;
+    ICV_TRY(hmm_check("copy_states_viterbi", m, chr_start, n_chr, levels && states && sign && nonneutral,
+                      ICV_COPY_STATES_MAX_WINDOWS, icv::kCsLdsPerWindow, fault == nullptr, fault ? fault : ""));
+    icv::CsParams P{};
+    for (int32_t k = 0; k < n_levels; ++k) P.mu[k] = levels[k];
+    P.mu[neutral] = 0.0;  // (a -0.0 is used as 0.0)
+    P.h = h, P.stay = stay, P.sw = sw, P.z = neutral;
+    switch (n_levels) {
+        case 2: return cs_launch<2>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
+        case 3: return cs_launch<3>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
+        case 4: return cs_launch<4>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
+        case 5: return cs_launch<5>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
+        case 6: return cs_launch<6>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
+        case 7: return cs_launch<7>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
+        default: return cs_launch<8>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
+    }
 }
 
 }  // extern "C"

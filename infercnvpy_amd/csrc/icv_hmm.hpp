@@ -1,4 +1,5 @@
-// What k_states_viterbi, k_posterior_chains and k_posterior_stats share.
+// What k_states_viterbi, k_posterior_chains, k_posterior_stats and k_copy_states_viterbi share (DESIGN.md 4.13, 4.15, 4.16,
+// 4.22).
 // Geometry: one wavefront (a 64-thread workgroup) per cell.  The row lies in LDS as W doubles (zeroed, then the stored
 // entries scattered on top; a dense row is converted in place), lane c runs the chromosomes c, c + 64, ... sequentially.
 // The forward-backward chain of 4.15 is written here once: 4.16 needs b, al_t, c_t, be_t, w and z bit for bit as 4.15
