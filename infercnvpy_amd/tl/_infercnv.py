@@ -11,6 +11,13 @@ Parallelism lives inside the call, as in the reference (``process_map`` over row
 GPU (``n_jobs`` / ``devices``), every shard is streamed from host memory to its own GPU by its own
 uploader, smoothed there, packed to CSR there and copied back; the host concatenates the shards in
 row order (``vstack``, :137).
+
+How the module is laid out: ``infercnv`` / ``infercnv_device`` put their arguments into one ``_Call`` record and hand
+it to ``_infercnv_resident`` (matrix in HBM) or ``_infercnv_host`` (matrix in host memory, which adds to the record the
+matrix and what the row shards share).  What both paths do is written once: ``_reference_request`` (which profile),
+``_compute_dtype`` (in which dtype, with which kernel flags), ``_ref_lo_hi`` (its bounds on the device) and
+``_piece_step`` (smooth, threshold + pack, gene values for some rows).  A ``_Shard`` is everything one GPU does in the
+host path: ``run`` = sizing (``_host_row_bytes``, ``_host_sizing``), ``_reference_pass``, ``_smooth``.
 """
 from __future__ import annotations
 
@@ -20,6 +27,7 @@ import sys
 import threading
 import time as _time
 from collections.abc import Sequence
+from typing import NamedTuple
 
 import numpy as np
 import scipy.sparse as sp
@@ -57,20 +65,24 @@ def _reference_groups(obs, reference_key, reference_cat):
     return groups, counts, cats
 
 
+def _repeat_rows(rows, cats):
+    """Per-category rows in the order the categories were listed (the same label listed twice: its row repeats)."""
+    if cats is None:
+        return rows
+    labels = cats.tolist()
+    if len(set(labels)) == len(labels):
+        return rows
+    first = {c: i for i, c in reversed(list(enumerate(labels)))}
+    return [rows[first[c]] for c in labels]
+
+
 def _means_from_chains(accs, counts, cats, is_sparse):
     """R x G means from the reference-order accumulators of the LAST shard (one array of the matrix dtype per group).
     Dense input: numpy's own last step, ``true_divide(sum, n)`` in that dtype; CSR input: scipy scaled every entry by
     1 / n before adding, the accumulators are the means."""
-    rows = []
-    for gi, acc in enumerate(accs):
-        n = int(counts if cats is None else counts[gi])
-        rows.append(acc if is_sparse else np.true_divide(acc, n))
-    if cats is not None:
-        labels = cats.tolist()
-        if len(set(labels)) != len(labels):  # same label listed twice: rows repeat
-            first = {c: i for i, c in reversed(list(enumerate(labels)))}
-            rows = [rows[first[c]] for c in labels]
-    return np.vstack(rows)
+    cnt = np.atleast_1d(counts)
+    rows = [acc if is_sparse else np.true_divide(acc, int(cnt[gi])) for gi, acc in enumerate(accs)]
+    return np.vstack(_repeat_rows(rows, cats))
 
 
 def _means_from_sums(shard_sums, counts, cats, dtype):
@@ -82,6 +94,63 @@ def _means_from_sums(shard_sums, counts, cats, dtype):
     cnt = np.atleast_1d(np.asarray(counts, dtype=np.float64))
     rows = list((total / cnt[:, None]).astype(dtype))
     return np.vstack(_repeat_rows(rows, cats))
+
+
+def _reference_request(reference, reference_key, reference_cat, obs, n_obs, n_vars):
+    """Which profile the call asks for (reference ``_get_reference``, :359-408): ``(given, groups, counts, cats)``.
+    ``given``: the caller's profile as R x G array -- or None: means over cells, all of them (``counts = [n_obs]``,
+    ``groups`` and ``cats`` None; the reference's warning is logged) or per category (:func:`_reference_groups`)."""
+    if reference is not None:
+        given = np.asarray(reference)
+        if given.ndim == 1:
+            given = given[np.newaxis, :]
+        if given.shape[1] != n_vars:
+            raise ValueError("Reference must match the number of genes in AnnData. ")
+        return given, None, None, None
+    if reference_key is None or reference_cat is None:
+        log.warning("Using mean of all cells as reference. For better results, provide either "
+                    "`reference`, or both `reference_key` and `reference_cat`. ")
+        return None, None, np.array([n_obs], dtype=np.int64), None
+    return (None, *_reference_groups(obs, reference_key, reference_cat))
+
+
+def _check_matrix_dtype(dtype):
+    if dtype.kind not in "iub" and dtype not in (np.float16, np.float32, np.float64):
+        raise ValueError(f"unsupported matrix dtype {dtype}")
+
+
+def _compute_dtype(x_dtype, ref_dtype, n_ref_rows):
+    """``(compute dtype, kernel flags)`` of a host matrix: what numpy's promotion gives the reference (:423, :428).
+    ``ref_dtype``: dtype of the given profile, None for means formed from the matrix (float32 for a float32 matrix, else
+    float64).  A float16 / float32 matrix stays in float32 next to a profile that numpy would not promote it for.
+    With several profile rows the reference subtracts ``np.min`` / ``np.max`` bounds conditionally and writes into the
+    matrix dtype: integers truncate, float32 rounds."""
+    _check_matrix_dtype(x_dtype)
+    narrow = x_dtype in (np.float16, np.float32)
+    if ref_dtype is None:
+        ref_dtype = np.float32 if x_dtype == np.float32 else np.float64
+    compute = np.float32 if narrow and np.result_type(np.float32, ref_dtype) == np.float32 else np.float64
+    flags = 0
+    if n_ref_rows >= 2 and x_dtype.kind in "iub":
+        flags = _lib.ICV_FLAG_TRUNC_TO_INT
+    elif n_ref_rows >= 2 and narrow and compute == np.float64:
+        flags = _lib.ICV_FLAG_ROUND_F32
+    return compute, flags
+
+
+def _ref_lo_hi(ref, compute=None):
+    """The profile as the kernels take it, on the current device: one row gives ``(row, None)``, several rows give
+    their column-wise ``(min, max)``.  A device tensor is reduced by torch where it lies; a host array by numpy, then
+    uploaded as ``compute``."""
+    several = ref.shape[0] != 1
+    if isinstance(ref, np.ndarray):
+        torch = _engine._torch()
+        rows = (np.min(ref, axis=0), np.max(ref, axis=0)) if several else (ref[0],)
+        rows = [torch.from_numpy(np.ascontiguousarray(r.astype(compute))).cuda() for r in rows]
+    else:
+        rows = (ref.min(dim=0).values, ref.max(dim=0).values) if several else (ref[0],)
+        rows = [r.contiguous() for r in rows]
+    return rows[0], (rows[1] if several else None)
 
 
 def _current_first(torch, n_dev):
@@ -125,6 +194,108 @@ def _resolve_devices(n_jobs, devices, n_chunks, torch, n_obs=None):
     return devs[: max(1, n_chunks)]
 
 
+class _Call(NamedTuple):
+    """One call: the arguments both paths read and, for the host path (filled in by :func:`_infercnv_host`), the matrix
+    and what its row shards share."""
+
+    reference_key: object
+    reference_cat: object
+    reference: object
+    lfc_clip: float
+    window_size: int
+    step: int
+    dynamic_threshold: object
+    exclude_chromosomes: object
+    chunksize: int
+    calculate_gene_values: bool
+    mean_order: str
+    # ---- host path ----
+    X: object = None            # ndarray or CSR, read in place by every shard's uploader
+    compute: object = None      # numpy dtype the matrix is uploaded and smoothed in
+    mean_dtype: object = None   # numpy dtype of means formed from the matrix
+    flags: int = 0
+    given: object = None        # R x G profile; None: the shards form the means over cells
+    means_of: tuple = None      # (groups, counts, cats) of those means, as _reference_request returns them
+    plan_args: tuple = None     # (var_chrom, var_start, window_size, step, exclude_chromosomes)
+    plan0: tuple = None         # (cache entry, plan) the caller checked out: shard 0 runs on it
+    shards: tuple = ()
+    barrier: object = None      # several shards: all of them, around forming the profile
+    ref_box: dict = None
+    errors: list = None         # (shard index, exception) of the shard threads
+
+
+def _check_chunksize(chunksize):
+    chunksize = int(chunksize)
+    if chunksize < 1:
+        raise ValueError("chunksize must be >= 1")
+    return chunksize
+
+
+def _warn_skipped(plan):
+    if plan.n_without_position:
+        log.warning(f"Skipped {plan.n_without_position} genes because they don't have a genomic position annotated. ")
+
+
+def _piece_step(call, plan, dm, ref_lo, ref_hi, flags, r0, r1, emit, gene_out=None):
+    """Rows [r0, r1) of the device matrix ``dm`` (whole chunks): one smoothing launch -- with
+    ``calculate_gene_values`` it also writes its float64 windows, as the reference's ``_infercnv_chunk`` returns both
+    from one pass (:438-457) --, then step 5b + ``csr_matrix(x_res)`` on the device (keep-mask, row offsets, fill), whose
+    ``PackedCsr`` goes to ``emit``, then the gene layer of the piece from the windows in one kernel (the piece's
+    thresholds are those of its rows' chunks): into ``gene_out``, or a new tensor.  Returns the gene values (None without)."""
+    tail = dict(lfc_clip=call.lfc_clip, chunksize=call.chunksize, flags=flags, row0=r0, row1=r1)
+    res = _engine.run_hot_path(plan, dm, ref_lo, ref_hi, dynamic_threshold=call.dynamic_threshold, apply=False,
+                               windows=call.calculate_gene_values, **tail)
+    emit(_engine.threshold_csr(plan, dm, ref_lo, ref_hi, res, **tail))
+    if call.calculate_gene_values and r1 > r0:
+        return _engine.gene_values_from_windows(plan, res.windows, thr=res.thr, chunksize=call.chunksize,
+                                                n_vars=dm.shape[1], out=gene_out)
+
+
+# ---- sizing: how many rows travel, compute and stay together ----------------------------------------------------------
+def _host_row_bytes(n_vars, n_windows, esz, gene_values, stored_per_row=None):
+    """Device bytes per row of a slab of the host path: the row itself (``stored_per_row``: mean stored entries of a
+    CSR matrix, None for dense), x_res, and the scratch of the kernels."""
+    if stored_per_row is not None:
+        per_row = max(1.0, stored_per_row) * (esz + 4) + 8 + 4 * n_windows + 64
+    else:
+        per_row = n_vars * esz + 4 * n_windows + 64
+    per_row += 8 * n_windows  # float64 window scratch of the chromosome-group fallback (rows that exceed LDS)
+    if gene_values:  # float64 gene matrix + float64 windows + covered-gene means
+        per_row += 8 * (2 * n_vars + n_windows) + 4 * n_windows
+    return per_row
+
+
+def _host_sizing(n_rows, per_row, free_bytes, share, chunksize, n_windows, piece_bytes=None):
+    """``(piece_rows, slabs)`` of a shard of ``n_rows`` rows.  Pieces of a slab: a few chunks each (~2 GB of input; the
+    developer knob ``ICV_PIECE_BYTES`` sets the pipeline's granularity), copied by a helper thread while earlier ones
+    compute.  Slabs ``[(r0, r1), ...]``: multiples of ``chunksize`` sized to fit this shard's share (one of ``share``
+    shards on the GPU) of the free HBM, next to the packed results of the pieces on their way back (worst case 12 bytes
+    per window, three pieces at a time)."""
+    if piece_bytes is None:
+        piece_bytes = float(os.environ.get("ICV_PIECE_BYTES", 2e9))
+    piece_rows = max(chunksize, int(piece_bytes // max(per_row, 1)) // chunksize * chunksize)
+    packed = 3 * min(piece_rows, max(n_rows, 1)) * n_windows * 12
+    slab_rows = int(max(0.45 * free_bytes / share - packed, 0) // per_row)
+    slab_rows = max(chunksize, slab_rows // chunksize * chunksize)
+    slabs = [(r, min(n_rows, r + slab_rows)) for r in range(0, max(n_rows, 1), slab_rows)] if n_rows else []
+    return piece_rows, slabs
+
+
+def _resident_piece_rows(n_obs, n_vars, n_windows, free_bytes, chunksize, gene_values):
+    """Rows per piece of a matrix resident in HBM: whole chunks whose result buffers (4 + 12 bytes per window, worst
+    case) fit next to the matrix."""
+    per_row = 16 * n_windows + 64 + (8 * (n_vars + n_windows) if gene_values else 0)
+    if gene_values:
+        free_bytes = max(free_bytes - 8 * n_vars * n_obs, free_bytes // 8)  # the float64 gene matrix of ALL rows stays
+    return max(chunksize, int(0.4 * free_bytes // per_row) // chunksize * chunksize)
+
+
+def _wait_for(event, errors):
+    while not event.wait(0.05):
+        if errors:
+            raise threading.BrokenBarrierError
+
+
 class _Shard:
     """The rows [g0, g1) of the matrix on one GPU: plan, slabs, upload streams, kernels, CSR drain."""
 
@@ -134,7 +305,142 @@ class _Shard:
         self.tm = {}
         self.result = None      # (indptr, indices, data) of the shard's X_cnv
         self.gene_pieces = []
-        self.accs = None        # host, per group: reference-order accumulators after this shard's rows
+        self.chained = threading.Event()  # the accumulators of the rows up to this shard's last are on the host
+        self.accs = None        # host: what the reference pass accumulated over this shard's rows (float64 sums) or up
+        #                         to its last row (per group: reference-order accumulators)
+        self.piece_rows, self.slabs = 0, []
+        self.streams = {}       # slab index -> its SlabStream (one slab resident)
+        self.drain = None
+        self.h2d_seconds = 0.0
+
+    def _retire(self, k):
+        ss = self.streams.pop(k)
+        ss.close()
+        self.h2d_seconds += ss.h2d_seconds
+        if getattr(ss, "pack_stats", None):
+            for kk, vv in ss.pack_stats.items():
+                self.tm["pack_" + kk] = vv if kk == "threads" else self.tm.get("pack_" + kk, 0.0) + vv
+
+    def _slab_stream(self, call, i):
+        """Start (or return) the upload of slab i; the previous slab is released first (one slab resident)."""
+        if i not in self.streams:
+            for k in list(self.streams):
+                self._retire(k)
+            r0, r1 = self.slabs[i]
+            # (the parent's arrays are read in place: no host copy of the shard or the slab)
+            torch = _engine._torch()
+            self.streams[i] = _engine.SlabStream(
+                call.X, torch.float32 if call.compute == np.float32 else torch.float64, self.piece_rows,
+                self.g0 + r0, self.g0 + r1,
+                host_pack_threads=max(2, _engine._default_pack_threads() // len(call.shards)))
+            self.tm["sparse_upload"] = bool(self.streams[i].sparse_upload)
+        return self.streams[i]
+
+    def _reference_pass(self, call):
+        """The R x G means over cells, every shard adding its rows.  ``mean_order="float64"``: float64 column sums, all
+        shards at once, the host adds the shards' sums.  Else the reference-order chains: shard k continues the
+        accumulators of shard k - 1 (its own upload starts before it waits for them); the last shard holds the sums."""
+        torch = _engine._torch()
+        t0 = _time.perf_counter()
+        (groups, counts, cats), n_vars = call.means_of, call.X.shape[1]
+        n_groups = len(counts)
+        f64 = call.mean_order == "float64"
+        if f64:
+            accs = torch.zeros((n_groups, n_vars), dtype=torch.float64, device="cuda")
+        else:
+            if self.slabs:
+                self._slab_stream(call, 0)  # the upload starts now, whatever this shard has to wait for
+            accs = [None] * n_groups
+            if self.index > 0:  # continue the chains of the rows before this shard
+                _wait_for(call.shards[self.index - 1].chained, call.errors)
+                accs = [torch.from_numpy(a).cuda() for a in call.shards[self.index - 1].accs]
+        for i, (s0, _) in enumerate(self.slabs):
+            ss = self._slab_stream(call, i)
+            for r0, r1 in ss.pieces():
+                rg = None if groups is None else groups[self.g0 + s0 + r0: self.g0 + s0 + r1]
+                if f64:
+                    _engine.column_sums(ss.dm, rg, n_groups, accs, r0, r1)
+                    continue
+                for gi in range(n_groups):
+                    rows = None if rg is None else np.nonzero(rg == gi)[0]
+                    accs[gi] = _engine.column_chain(ss.dm, accs[gi], rows, counts[gi], r0, r1)
+            ss = None
+        if f64:
+            self.accs = accs.cpu().numpy()
+        else:
+            self.accs = [(a.cpu().numpy() if a is not None else np.zeros(n_vars, dtype=call.mean_dtype)) for a in accs]
+            self.chained.set()
+        if call.barrier is not None:
+            call.barrier.wait()  # every shard's accumulators are on the host
+        if self.index == 0 and f64:
+            call.ref_box["ref"] = _means_from_sums([sh.accs for sh in call.shards], counts, cats, call.mean_dtype)
+        elif self.index == 0:
+            call.ref_box["ref"] = _means_from_chains(call.shards[-1].accs, counts, cats, sp.issparse(call.X))
+        if call.barrier is not None:
+            call.barrier.wait()
+        self.tm["reference_pass"] = _time.perf_counter() - t0
+        return call.ref_box["ref"]
+
+    def _smooth(self, call, plan, ref_lo, ref_hi):
+        """X_cnv of the shard's rows, piece by piece behind the uploads; the drain packs and copies back finished pieces
+        behind the kernels (only the row offsets and the packed entries are read back)."""
+        t0 = _time.perf_counter()
+        self.drain = _engine.CsrDrain(self.g1 - self.g0, plan.n_windows)
+        for i in range(len(self.slabs)):
+            ss = self._slab_stream(call, i)  # a single slab that a reference pass has already brought in is not uploaded again
+            for r0, r1 in ss.pieces():
+                gv = _piece_step(call, plan, ss.dm, ref_lo, ref_hi, call.flags, r0, r1, self.drain.submit)
+                if gv is not None:
+                    self.gene_pieces.append(gv.cpu().numpy())
+                    del gv
+            ss = None
+        for k in list(self.streams):
+            self._retire(k)
+        self.tm["stream_and_kernels"] = _time.perf_counter() - t0
+        tp = _time.perf_counter()
+        self.result = self.drain.finish(arrays=len(call.shards) > 1)
+        self.tm["h2d"] = self.h2d_seconds
+        self.tm["csr_pack_d2h"] = self.drain.busy_seconds        # mostly hidden behind the uploads and kernels
+        self.tm["csr_pack_d2h_tail"] = _time.perf_counter() - tp  # what was left after the last kernel was launched
+
+    def run(self, call):
+        """Everything one GPU does, on the calling thread (its own thread when there are several shards)."""
+        t_sh = _time.perf_counter()
+        X, n_rows = call.X, self.g1 - self.g0
+        ent, plan = call.plan0 if self.index == 0 else _checkout_plan(*call.plan_args, self.device)
+        per_row = _host_row_bytes(X.shape[1], plan.n_windows, np.dtype(call.compute).itemsize, call.calculate_gene_values,
+                                  X.nnz / max(X.shape[0], 1) if sp.issparse(X) else None)
+        self.piece_rows, self.slabs = _host_sizing(n_rows, per_row, _engine.free_hbm_bytes(), self.share,
+                                                   call.chunksize, plan.n_windows)
+        try:
+            ref = call.given if call.given is not None else self._reference_pass(call)
+            ref_lo, ref_hi = _ref_lo_hi(ref, call.compute)
+            self._smooth(call, plan, ref_lo, ref_hi)
+            # (kernel: _lib.ICV_KERNEL_*, which smoothing kernel the last piece took)
+            self.tm.update(rows=n_rows, device=self.device, kernel=plan.last_kernel(),
+                           total=_time.perf_counter() - t_sh)
+        finally:
+            # error or not: stop the helper threads, release their device buffers (ADVICE r2: a failed call used to
+            # leave the drain thread blocked on its queue with the GPU tensors pinned)
+            for k in list(self.streams):
+                self.streams.pop(k).close(cancel=True)
+            if self.drain is not None:
+                self.drain.close()
+            if plan is not call.plan0[1]:
+                _checkin_plan(ent, plan)
+
+    def thread_main(self, call):
+        torch = _engine._torch()
+        try:
+            with torch.cuda.device(self.device):
+                # a stream of its own: shards that share a GPU overlap, and nothing queues behind the caller's work
+                with torch.cuda.stream(torch.cuda.Stream(self.device)):
+                    self.run(call)
+                    torch.cuda.current_stream().synchronize()
+        except BaseException as e:  # noqa: BLE001 -- re-raised on the calling thread
+            call.errors.append((self.index, e))
+            if call.barrier is not None:
+                call.barrier.abort()
 
 
 _PLAN_CACHE = {}  # key -> _PlanEntry, most recently used last
@@ -264,96 +570,59 @@ def _is_real_anndata(adata):
     return mod == "anndata" or mod.startswith("anndata.")
 
 
-def _repeat_rows(rows, cats):
-    """Per-category rows in the order the categories were listed (the same label listed twice: its row repeats)."""
-    if cats is None:
-        return rows
-    labels = cats.tolist()
-    if len(set(labels)) == len(labels):
-        return rows
-    first = {c: i for i, c in reversed(list(enumerate(labels)))}
-    return [rows[first[c]] for c in labels]
+def _resident_profile(torch, dm, obs, call):
+    """The R x G profile of a resident matrix as a device tensor of its dtype: the given one, or means over cells
+    formed where the matrix lies."""
+    n_obs, n_vars = dm.shape
+    np_dtype = np.float32 if dm.dtype == torch.float32 else np.float64
+    given, groups, counts, cats = _reference_request(call.reference, call.reference_key, call.reference_cat, obs, n_obs,
+                                                     n_vars)
+    if given is not None:
+        if np.result_type(np_dtype, given.dtype) != np_dtype:
+            raise ValueError("a device-resident matrix needs a reference of its own (or a narrower) dtype: "
+                             "numpy would promote the subtraction (pass the matrix as float64)")
+        return torch.from_numpy(np.ascontiguousarray(given.astype(np_dtype))).cuda()
+    if call.mean_order == "float64":
+        # opt-in: float64 column sums (one concurrent pass, correctly rounded means -- not numpy's order)
+        sums = _engine.column_sums(dm, groups, len(counts))
+        cnt = torch.as_tensor(np.asarray(counts, dtype=np.float64)).cuda()
+        rows = list((sums / cnt[:, None]).to(dm.dtype))
+    else:
+        rows = []
+        for gi, n_g in enumerate(counts):
+            sel = None if groups is None else np.nonzero(groups == gi)[0]
+            acc = _engine.column_chain(dm, None, sel, int(n_g))
+            rows.append(_engine.chain_mean(acc, int(n_g), dm.format == _lib.ICV_CSR))
+    return torch.stack(_repeat_rows(rows, cats))
 
 
-def _infercnv_resident(var, obs, dm, *, reference_key, reference_cat, reference, lfc_clip, window_size, step,
-                       dynamic_threshold, exclude_chromosomes, chunksize, calculate_gene_values, mean_order, tm):
+def _infercnv_resident(var, obs, dm, call, tm):
     """The call on a matrix that is resident in HBM (no host copies, no synchronisation): reference means as chains on
     the device, one smoothing launch per piece, threshold + CSR pack; returns ``(chr_pos, PackedCsr, gene values |
     None)`` with everything still on the device."""
+    call = call._replace(chunksize=_check_chunksize(call.chunksize))
     torch = _engine._torch()
     t_start = _time.perf_counter()
     dev = dm._keep[0].device.index
     n_obs, n_vars = dm.shape
     with torch.cuda.device(dev):
-        ent, plan = _checkout_plan(var["chromosome"].to_numpy(), var["start"].to_numpy(), window_size, step,
-                                   exclude_chromosomes, dev)
+        ent, plan = _checkout_plan(var["chromosome"].to_numpy(), var["start"].to_numpy(), call.window_size, call.step,
+                                   call.exclude_chromosomes, dev)
         try:
-            if plan.n_without_position:
-                log.warning(f"Skipped {plan.n_without_position} genes because they don't have a genomic position annotated. ")
-            is_csr = dm.format == _lib.ICV_CSR
-            np_dtype = np.float32 if dm.dtype == torch.float32 else np.float64
-            flags = 0
-            if reference is not None:
-                given = np.asarray(reference)
-                if given.ndim == 1:
-                    given = given[np.newaxis, :]
-                if given.shape[1] != n_vars:
-                    raise ValueError("Reference must match the number of genes in AnnData. ")
-                if np.result_type(np_dtype, given.dtype) != np_dtype:
-                    raise ValueError("a device-resident matrix needs a reference of its own (or a narrower) dtype: "
-                                     "numpy would promote the subtraction (pass the matrix as float64)")
-                ref = torch.from_numpy(np.ascontiguousarray(given.astype(np_dtype))).cuda()
-            else:
-                groups = cats = None
-                if reference_key is None or reference_cat is None:
-                    log.warning("Using mean of all cells as reference. For better results, provide either "
-                                "`reference`, or both `reference_key` and `reference_cat`. ")
-                    counts = [n_obs]
-                else:
-                    groups, counts, cats = _reference_groups(obs, reference_key, reference_cat)
-                if mean_order == "float64":
-                    # opt-in: float64 column sums (one concurrent pass, correctly rounded means -- not numpy's order)
-                    sums = _engine.column_sums(dm, groups, len(counts))
-                    cnt = torch.as_tensor(np.asarray(counts, dtype=np.float64)).cuda()
-                    rows = list((sums / cnt[:, None]).to(dm.dtype))
-                else:
-                    rows = []
-                    for gi, n_g in enumerate(counts):
-                        sel = None if groups is None else np.nonzero(groups == gi)[0]
-                        acc = _engine.column_chain(dm, None, sel, int(n_g))
-                        rows.append(_engine.chain_mean(acc, int(n_g), is_csr))
-                ref = torch.stack(_repeat_rows(rows, cats))
-            if ref.shape[0] == 1:
-                ref_lo, ref_hi = ref[0].contiguous(), None
-            else:
-                ref_lo, ref_hi = ref.min(dim=0).values.contiguous(), ref.max(dim=0).values.contiguous()
-            # pieces of whole chunks whose result buffers (4 + 12 bytes per window, worst case) fit next to the matrix
-            free_b = _engine.free_hbm_bytes()
-            per_row = 16 * plan.n_windows + 64 + (8 * (n_vars + plan.n_windows) if calculate_gene_values else 0)
-            if calculate_gene_values:
-                free_b = max(free_b - 8 * n_vars * n_obs, free_b // 8)  # the float64 gene matrix of ALL rows stays
-            piece = max(chunksize, int(0.4 * free_b // per_row) // chunksize * chunksize)
+            _warn_skipped(plan)
+            ref_lo, ref_hi = _ref_lo_hi(_resident_profile(torch, dm, obs, call))
+            piece = _resident_piece_rows(n_obs, n_vars, plan.n_windows, _engine.free_hbm_bytes(), call.chunksize,
+                                         call.calculate_gene_values)
             parts = []
-            genes = torch.empty((n_obs, n_vars), dtype=torch.float64, device="cuda") if calculate_gene_values else None
+            genes = torch.empty((n_obs, n_vars), dtype=torch.float64, device="cuda") if call.calculate_gene_values else None
             for r0 in range(0, max(n_obs, 1), piece):
                 r1 = min(n_obs, r0 + piece)
-                # (calculate_gene_values: the smoothing launch also writes its float64 windows -- one pass, as the
-                # reference's _infercnv_chunk returns both from one pass, :438-457)
-                res = _engine.run_hot_path(plan, dm, ref_lo, ref_hi, lfc_clip=lfc_clip,
-                                           dynamic_threshold=dynamic_threshold, chunksize=chunksize, flags=flags,
-                                           row0=r0, row1=r1, apply=False, windows=calculate_gene_values)
-                parts.append(_engine.threshold_csr(plan, dm, ref_lo, ref_hi, res, lfc_clip=lfc_clip,
-                                                   chunksize=chunksize, flags=flags, row0=r0, row1=r1))
-                if calculate_gene_values and r1 > r0:
-                    # (pieces are whole chunks: the piece's thresholds are the thresholds of its rows' chunks)
-                    _engine.gene_values_from_windows(plan, res.windows, thr=res.thr, chunksize=chunksize,
-                                                     out=genes[r0:r1])
-                del res
+                # (no kernel flags: the matrix is float32 / float64 and its profile never wider than it)
+                _piece_step(call, plan, dm, ref_lo, ref_hi, 0, r0, r1, parts.append,
+                            None if genes is None else genes[r0:r1])
             x_cnv = parts[0] if len(parts) == 1 else _engine.concat_packed(parts)
-            tm["kernel"] = plan.last_kernel()
-            tm["devices"] = [dev]
-            tm["pieces"] = len(parts)
-            tm["total"] = _time.perf_counter() - t_start  # host time only: nothing has been waited for
+            # (total: host time only, nothing has been waited for)
+            tm.update(kernel=plan.last_kernel(), devices=[dev], pieces=len(parts), total=_time.perf_counter() - t_start)
             chr_pos = dict(plan.chr_pos)
         finally:
             _checkin_plan(ent, plan)
@@ -406,6 +675,8 @@ def infercnv_device(
         adata.obsm["X_cnv"] = x_cnv.to_scipy()          # the reference's host matrix
         adata.uns["cnv"] = {"chr_pos": chr_pos}
     """
+    call = _Call(reference_key, reference_cat, reference, lfc_clip, window_size, step, dynamic_threshold,
+                 exclude_chromosomes, chunksize, calculate_gene_values, mean_order)
     _check_var(var, var.index)
     _check_mean_order(mean_order)
     _lib.load()
@@ -417,14 +688,7 @@ def infercnv_device(
         raise ValueError("X must have one column per row of `var`")
     if reference is None and reference_key is not None and reference_cat is not None and obs is None:
         raise ValueError("reference_key needs `obs`")
-    chunksize = int(chunksize)
-    if chunksize < 1:
-        raise ValueError("chunksize must be >= 1")
-    return _infercnv_resident(
-        var, obs, dm, reference_key=reference_key, reference_cat=reference_cat, reference=reference,
-        lfc_clip=lfc_clip, window_size=window_size, step=step, dynamic_threshold=dynamic_threshold,
-        exclude_chromosomes=exclude_chromosomes, chunksize=chunksize, calculate_gene_values=calculate_gene_values,
-        mean_order=mean_order, tm=_timings if _timings is not None else {})
+    return _infercnv_resident(var, obs, dm, call, _timings if _timings is not None else {})
 
 
 def infercnv(
@@ -509,37 +773,34 @@ def infercnv(
     """
     tm = _timings if _timings is not None else {}
     t_start = _time.perf_counter()
+    call = _Call(reference_key, reference_cat, reference, lfc_clip, window_size, step, dynamic_threshold,
+                 exclude_chromosomes, chunksize, calculate_gene_values, mean_order)
     _check_var(adata.var, adata.var_names)
     _check_mean_order(mean_order)
     _lib.load()  # fail loudly before doing any work if the HIP extension is missing
 
-    X0 = adata.X if layer is None else adata.layers[layer]
-    dm0 = _resident_matrix(X0, sys.modules.get("torch"))
-    if dm0 is not None:
-        chunksize = int(chunksize)
-        if chunksize < 1:
-            raise ValueError("chunksize must be >= 1")
-        chr_pos, x_cnv, per_gene = _infercnv_resident(
-            adata.var, adata.obs, dm0, reference_key=reference_key, reference_cat=reference_cat, reference=reference,
-            lfc_clip=lfc_clip, window_size=window_size, step=step, dynamic_threshold=dynamic_threshold,
-            exclude_chromosomes=exclude_chromosomes, chunksize=chunksize,
-            calculate_gene_values=calculate_gene_values, mean_order=mean_order, tm=tm)
-        if not inplace:
-            return chr_pos, x_cnv, per_gene
-        if _is_real_anndata(adata):
+    X = adata.X if layer is None else adata.layers[layer]
+    dm = _resident_matrix(X, sys.modules.get("torch"))
+    if dm is not None:
+        chr_pos, x_cnv, per_gene = _infercnv_resident(adata.var, adata.obs, dm, call, tm)
+        if inplace and _is_real_anndata(adata):
             # anndata validates what goes into obsm / layers and takes neither a PackedCsr nor a device tensor: a real
             # AnnData gets the reference's host objects (tl.infercnv_device keeps the result on the GPU)
             x_cnv = x_cnv.to_scipy()
             per_gene = per_gene.cpu().numpy() if per_gene is not None else None
-        adata.obsm[f"X_{key_added}"] = x_cnv
-        adata.uns[key_added] = {"chr_pos": chr_pos}
-        if calculate_gene_values:
-            adata.layers[f"gene_values_{key_added}"] = per_gene
-        return None
+    else:
+        chr_pos, x_cnv, per_gene = _infercnv_host(adata.var, adata.obs, X, call, n_jobs, devices, tm, t_start)
+    if not inplace:
+        return chr_pos, x_cnv, per_gene
+    adata.obsm[f"X_{key_added}"] = x_cnv
+    adata.uns[key_added] = {"chr_pos": chr_pos}
+    if calculate_gene_values:
+        adata.layers[f"gene_values_{key_added}"] = per_gene
 
-    var_chrom, var_start = adata.var["chromosome"].to_numpy(), adata.var["start"].to_numpy()
 
-    X = adata.X if layer is None else adata.layers[layer]
+def _host_matrix(X, call):
+    """``adata.X`` in host memory as the shards read it -- an ndarray or a canonical CSR matrix -- and the two layouts
+    whose reference-order means need whole columns: ``(X, X_csc | None, X_fortran | None)``."""
     if isinstance(X, np.matrix):
         X = np.asarray(X)
     X_csc = X if (sp.issparse(X) and X.format == "csc") else None  # scipy reduces CSC columns in another order
@@ -548,7 +809,7 @@ def infercnv(
     # (a single-column matrix is a 1-D contiguous reduction for numpy: the same pairwise order)
     X_fortran = X if (isinstance(X, np.ndarray) and X.ndim == 2 and X.shape[0] > 1 and
                       (abs(X.strides[0]) < abs(X.strides[1]) or X.shape[1] == 1)) else None
-    if sp.issparse(X) and X.format not in ("csr", "csc") and reference is None and mean_order == "reference":
+    if sp.issparse(X) and X.format not in ("csr", "csc") and call.reference is None and call.mean_order == "reference":
         log.warning(f"tl.infercnv: a {X.format.upper()} matrix is converted to CSR; scipy's own summation order for this "
                     "format is not reproduced, so the reference means (and entries of X_cnv next to the noise "
                     "threshold) may differ from infercnvpy's in the last bit.  Convert with .tocsr() for exact parity.")
@@ -557,47 +818,59 @@ def infercnv(
         if not X.has_canonical_format:  # the kernels expect unique, sorted column indices per row
             X = X.copy()
             X.sum_duplicates()
-    n_obs, n_vars = X.shape
-    chunksize = int(chunksize)
-    if chunksize < 1:
-        raise ValueError("chunksize must be >= 1")
+    return X, X_csc, X_fortran
 
-    torch = _engine._torch()
 
-    # ---- compute dtype: what numpy's promotion gives the reference (:423, :428) ----------------
-    x_is_int = X.dtype.kind in "iub"
-    given = None
-    if reference is not None:
-        given = np.asarray(reference)
-    mean_dtype = np.float32 if X.dtype == np.float32 else np.float64
-    ref_dtype = given.dtype if given is not None else mean_dtype
-    if x_is_int or X.dtype == np.float64:
-        compute = np.float64
-    elif X.dtype == np.float32 or X.dtype == np.float16:
-        compute = np.float32 if np.result_type(np.float32, ref_dtype) == np.float32 else np.float64
-    else:
-        raise ValueError(f"unsupported matrix dtype {X.dtype}")
-    tdtype = torch.float32 if compute == np.float32 else torch.float64
-    esz = 4 if compute == np.float32 else 8
-
-    # ---- the reference profile: given, or per-group column means formed from the shards' sums (:359-408) --------
-    need_means = reference is None
-    groups = counts = cats = None
-    n_groups = 1
-    if need_means:
-        if reference_key is None or reference_cat is None:
-            log.warning("Using mean of all cells as reference. For better results, provide either "
-                        "`reference`, or both `reference_key` and `reference_cat`. ")
-            counts = float(n_obs)
+def _whole_column_means(X_csc, X_fortran, call, groups, counts, cats, mean_dtype, device, tm):
+    """The reference-order means that row shards cannot form, on the first GPU before the shards start: R x G array,
+    or None where the shards' chains are the reference's order."""
+    if call.mean_order == "float64" or (X_csc is None and (X_fortran is None or groups is not None)):
+        return None
+    t0 = _time.perf_counter()
+    with _engine._torch().cuda.device(device):
+        if X_csc is not None:
+            # CSC input: np.add.reduceat per column over ALL rows of the group -- not separable by row shards; the CSC
+            # arrays go to the GPU in column blocks (values + row indices, 8 bytes per stored entry)
+            means = _engine.csc_column_means(X_csc, groups, len(counts), [int(c) for c in counts], np_dtype=mean_dtype)
+            given = _means_from_chains(list(means), counts, cats, True)
         else:
-            groups, counts, cats = _reference_groups(adata.obs, reference_key, reference_cat)
-            n_groups = len(cats)
-    else:
-        given = np.asarray(given)
-        if given.ndim == 1:
-            given = given[np.newaxis, :]
-        if given.shape[1] != n_vars:
-            raise ValueError("Reference must match the number of genes in AnnData. ")
+            # F-ordered input, all-cell mean: whole columns are needed (per-category means go through X[rows, :],
+            # which numpy returns C-ordered: the shards' chains)
+            given = _engine.fortran_column_means(X_fortran, np_dtype=mean_dtype)[np.newaxis, :]
+    tm["reference_pass"] = _time.perf_counter() - t0
+    return given
+
+
+def _run_shards(call):
+    """One thread (and stream) per shard; a single shard runs on the caller's thread and current stream."""
+    shards = call.shards
+    if len(shards) == 1:
+        with _engine._torch().cuda.device(shards[0].device):
+            shards[0].run(call)
+        return
+    threads = [threading.Thread(target=s.thread_main, args=(call,), daemon=True) for s in shards]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    if call.errors:
+        real = [e for _, e in sorted(call.errors, key=lambda x: x[0]) if not isinstance(e, threading.BrokenBarrierError)]
+        raise (real[0] if real else call.errors[0][1])
+
+
+def _infercnv_host(var, obs, X, call, n_jobs, devices, tm, t_start):
+    """The call on a matrix in host memory: ``(chr_pos, scipy CSR X_cnv, gene values | None)``."""
+    plan_args = (var["chromosome"].to_numpy(), var["start"].to_numpy(), call.window_size, call.step,
+                 call.exclude_chromosomes)
+    X, X_csc, X_fortran = _host_matrix(X, call)
+    n_obs, n_vars = X.shape
+    chunksize = _check_chunksize(call.chunksize)
+    torch = _engine._torch()
+    _check_matrix_dtype(X.dtype)  # (an unsupported matrix is refused before the reference is looked at)
+    # ---- the reference profile: given, or per-group column means formed by the shards (:359-408) -----------------
+    given, groups, counts, cats = _reference_request(call.reference, call.reference_key, call.reference_cat, obs, n_obs,
+                                                     n_vars)
+    mean_dtype = np.float32 if X.dtype == np.float32 else np.float64
 
     # ---- row shards: contiguous, chunk-aligned, one per listed GPU (reference: chunks to a process pool) ---------
     from ..dist import shard_bounds
@@ -606,232 +879,26 @@ def infercnv(
     devs = _resolve_devices(n_jobs, devices, n_chunks, torch, n_obs)
     bounds = [b for b in shard_bounds(n_obs, len(devs), chunksize) if b[1] > b[0]] or [(0, n_obs)]
     devs = devs[: len(bounds)]
-    shards = [_Shard(i, d, devs.count(d), g0, g1) for i, (d, (g0, g1)) in enumerate(zip(devs, bounds))]
+    shards = tuple(_Shard(i, d, devs.count(d), g0, g1) for i, (d, (g0, g1)) in enumerate(zip(devs, bounds)))
     multi = len(shards) > 1
     tm["devices"] = list(devs)
 
-    f64_means = need_means and mean_order == "float64"
-    if need_means and X_csc is not None and not f64_means:
-        # CSC input: np.add.reduceat per column over ALL rows of the group -- not separable by row shards; the CSC
-        # arrays go to the first GPU in column blocks (values + row indices, 8 bytes per stored entry)
-        t0 = _time.perf_counter()
-        with torch.cuda.device(devs[0]):
-            cnt = [int(n_obs)] if cats is None else [int(c) for c in counts]
-            means = _engine.csc_column_means(X_csc, groups, n_groups, cnt, np_dtype=mean_dtype)
-        given = _means_from_chains(list(means), counts, cats, True)
-        need_means = False
-        tm["reference_pass"] = _time.perf_counter() - t0
-
-    if need_means and X_fortran is not None and groups is None and not f64_means:
-        # F-ordered input, all-cell mean: whole columns are needed -- formed on the first GPU before the shards start
-        # (per-category means go through X[rows, :], which numpy returns C-ordered: the chains below)
-        t0 = _time.perf_counter()
-        with torch.cuda.device(devs[0]):
-            given = _engine.fortran_column_means(X_fortran, np_dtype=mean_dtype)[np.newaxis, :]
-        need_means = False
-        tm["reference_pass"] = _time.perf_counter() - t0
-
-    barrier = threading.Barrier(len(shards)) if multi else None
-    chained = [threading.Event() for _ in shards]  # shard k's reference-order accumulators are on the host
-    ref_box = {}
-    errors = []
-
-    def wait_for(ev):
-        while not ev.wait(0.05):
-            if errors:
-                raise threading.BrokenBarrierError
-
-    def per_row_bytes(plan):
-        if sp.issparse(X):
-            per_row = max(1.0, X.nnz / max(n_obs, 1)) * (esz + 4) + 8 + 4 * plan.n_windows + 64
-        else:
-            per_row = n_vars * esz + 4 * plan.n_windows + 64
-        per_row += 8 * plan.n_windows  # float64 window scratch of the chromosome-group fallback (rows that exceed LDS)
-        if calculate_gene_values:  # float64 gene matrix + float64 windows + covered-gene means
-            per_row += 8 * (2 * n_vars + plan.n_windows) + 4 * plan.n_windows
-        return per_row
-
-    def run_shard(s: _Shard):
-        """Everything one GPU does, on the calling thread (its own thread when there are several shards)."""
-        t_sh = _time.perf_counter()
-        ent, plan = (ent0, plan0) if s.index == 0 else _checkout_plan(var_chrom, var_start, window_size, step,
-                                                                      exclude_chromosomes, s.device)
-        n_rows = s.g1 - s.g0
-        # pieces of a slab: a few chunks each (~2 GB of input), copied by a helper thread while earlier ones compute
-        per_row = per_row_bytes(plan)
-        piece_bytes = float(os.environ.get("ICV_PIECE_BYTES", 2e9))  # (developer knob: pipeline granularity)
-        piece_rows = max(chunksize, int(piece_bytes // max(per_row, 1)) // chunksize * chunksize)
-        # row slabs (multiples of chunksize) sized to fit this shard's share of the GPU's free HBM, next to the packed
-        # results of the pieces on their way back (worst case 12 bytes per window, three pieces at a time)
-        free_b = _engine.free_hbm_bytes()
-        packed = 3 * min(piece_rows, max(n_rows, 1)) * plan.n_windows * 12
-        slab_rows = int(max(0.45 * free_b / s.share - packed, 0) // per_row)
-        slab_rows = max(chunksize, slab_rows // chunksize * chunksize)
-        slabs = [(r, min(n_rows, r + slab_rows)) for r in range(0, max(n_rows, 1), slab_rows)] if n_rows else []
-        t_h2d = [0.0]
-        streams = {}
-        drain = None
-
-        def retire(k):
-            ss = streams.pop(k)
-            ss.close()
-            t_h2d[0] += ss.h2d_seconds
-            if getattr(ss, "pack_stats", None):
-                for kk, vv in ss.pack_stats.items():
-                    s.tm["pack_" + kk] = vv if kk == "threads" else s.tm.get("pack_" + kk, 0.0) + vv
-
-        def slab_stream(i):
-            """Start (or return) the upload of slab i; the previous slab is released first (one slab resident)."""
-            if i not in streams:
-                for k in list(streams):
-                    retire(k)
-                r0, r1 = slabs[i]
-                # (the parent's arrays are read in place: no host copy of the shard or the slab)
-                streams[i] = _engine.SlabStream(X, tdtype, piece_rows, s.g0 + r0, s.g0 + r1,
-                                                host_pack_threads=max(2, _engine._default_pack_threads() // len(shards)))
-                s.tm["sparse_upload"] = bool(streams[i].sparse_upload)
-            return streams[i]
-
-        try:
-            if f64_means:
-                # opt-in: float64 column sums of this shard's rows, all shards at once; the host adds the shards' sums
-                t0 = _time.perf_counter()
-                sums = torch.zeros((n_groups, n_vars), dtype=torch.float64, device="cuda")
-                for i, (s0, _) in enumerate(slabs):
-                    ss = slab_stream(i)
-                    for r0, r1 in ss.pieces():
-                        rg = None if groups is None else groups[s.g0 + s0 + r0: s.g0 + s0 + r1]
-                        _engine.column_sums(ss.dm, rg, n_groups, sums, r0, r1)
-                    ss = None
-                s.accs = sums.cpu().numpy()
-                if multi:
-                    barrier.wait()
-                    if s.index == 0:
-                        ref_box["ref"] = _means_from_sums([sh.accs for sh in shards], counts, cats, mean_dtype)
-                    barrier.wait()
-                    ref = ref_box["ref"]
-                else:
-                    ref = _means_from_sums([s.accs], counts, cats, mean_dtype)
-                s.tm["reference_pass"] = _time.perf_counter() - t0
-            elif need_means:
-                t0 = _time.perf_counter()
-                if slabs:
-                    slab_stream(0)  # the upload starts now, whatever this shard has to wait for
-                accs = [None] * n_groups
-                if s.index > 0:  # continue the chains of the rows before this shard
-                    wait_for(chained[s.index - 1])
-                    accs = [torch.from_numpy(a).cuda() for a in shards[s.index - 1].accs]
-                for i, (s0, _) in enumerate(slabs):
-                    ss = slab_stream(i)
-                    for r0, r1 in ss.pieces():
-                        for gi in range(n_groups):
-                            rows, n_g = None, counts
-                            if groups is not None:
-                                rows = np.nonzero(groups[s.g0 + s0 + r0: s.g0 + s0 + r1] == gi)[0]
-                                n_g = counts[gi]
-                            accs[gi] = _engine.column_chain(ss.dm, accs[gi], rows, n_g, r0, r1)
-                    ss = None
-                s.accs = [(a.cpu().numpy() if a is not None else np.zeros(n_vars, dtype=mean_dtype)) for a in accs]
-                chained[s.index].set()
-                if multi:
-                    barrier.wait()  # every shard's accumulators are on the host
-                    if s.index == 0:
-                        ref_box["ref"] = _means_from_chains(shards[-1].accs, counts, cats, sp.issparse(X))
-                    barrier.wait()
-                    ref = ref_box["ref"]
-                else:
-                    ref = _means_from_chains(s.accs, counts, cats, sp.issparse(X))
-                s.tm["reference_pass"] = _time.perf_counter() - t0
-            else:
-                ref = given
-            flags = 0
-            if ref.shape[0] == 1:
-                ref_lo = torch.from_numpy(np.ascontiguousarray(ref[0].astype(compute))).cuda()
-                ref_hi = None
-            else:
-                ref_lo = torch.from_numpy(np.ascontiguousarray(np.min(ref, axis=0).astype(compute))).cuda()
-                ref_hi = torch.from_numpy(np.ascontiguousarray(np.max(ref, axis=0).astype(compute))).cuda()
-                if x_is_int:
-                    flags |= _lib.ICV_FLAG_TRUNC_TO_INT
-                elif X.dtype in (np.float32, np.float16) and compute == np.float64:
-                    flags |= _lib.ICV_FLAG_ROUND_F32
-
-            t0 = _time.perf_counter()
-            drain = _engine.CsrDrain(n_rows, plan.n_windows)  # packs and copies back finished pieces behind the kernels
-            for i in range(len(slabs)):
-                ss = slab_stream(i)  # a single slab that a reference pass has already brought in is not uploaded again
-                for r0, r1 in ss.pieces():
-                    # (calculate_gene_values: the smoothing launch also writes its float64 windows; the gene layer of
-                    # the piece is formed from them in one kernel -- pieces are whole chunks, so the piece's thresholds
-                    # are those of its rows)
-                    res = _engine.run_hot_path(plan, ss.dm, ref_lo, ref_hi, lfc_clip=lfc_clip,
-                                               dynamic_threshold=dynamic_threshold, chunksize=chunksize, flags=flags,
-                                               row0=r0, row1=r1, apply=False, windows=calculate_gene_values)
-                    # step 5b + csr_matrix(x_res) on the device (keep-mask, row offsets, fill); only the row offsets
-                    # and the packed entries are read back by the drain
-                    drain.submit(_engine.threshold_csr(plan, ss.dm, ref_lo, ref_hi, res, lfc_clip=lfc_clip,
-                                                       chunksize=chunksize, flags=flags, row0=r0, row1=r1))
-                    if calculate_gene_values and r1 > r0:
-                        gv = _engine.gene_values_from_windows(plan, res.windows, thr=res.thr, chunksize=chunksize,
-                                                              n_vars=n_vars)
-                        s.gene_pieces.append(gv.cpu().numpy())
-                        del gv
-                    del res
-                ss = None
-            for k in list(streams):
-                retire(k)
-            s.tm["stream_and_kernels"] = _time.perf_counter() - t0
-            tp = _time.perf_counter()
-            s.result = drain.finish(arrays=multi)
-            s.tm["h2d"] = t_h2d[0]
-            s.tm["csr_pack_d2h"] = drain.busy_seconds        # mostly hidden behind the uploads and kernels
-            s.tm["csr_pack_d2h_tail"] = _time.perf_counter() - tp  # what was left after the last kernel was launched
-            s.tm["rows"] = n_rows
-            s.tm["device"] = s.device
-            s.tm["kernel"] = plan.last_kernel()  # _lib.ICV_KERNEL_*: which smoothing kernel the last piece took
-            s.tm["total"] = _time.perf_counter() - t_sh
-        finally:
-            # error or not: stop the helper threads, release their device buffers (ADVICE r2: a failed call used to
-            # leave the drain thread blocked on its queue with the GPU tensors pinned)
-            for k in list(streams):
-                streams.pop(k).close(cancel=True)
-            if drain is not None:
-                drain.close()
-            if plan is not plan0:
-                _checkin_plan(ent, plan)
-
-    def shard_thread(s: _Shard):
-        try:
-            with torch.cuda.device(s.device):
-                # a stream of its own: shards that share a GPU overlap, and nothing queues behind the caller's work
-                with torch.cuda.stream(torch.cuda.Stream(s.device)):
-                    run_shard(s)
-                    torch.cuda.current_stream().synchronize()
-        except BaseException as e:  # noqa: BLE001 -- re-raised on the calling thread
-            errors.append((s.index, e))
-            if barrier is not None:
-                barrier.abort()
+    if given is None:
+        given = _whole_column_means(X_csc, X_fortran, call, groups, counts, cats, mean_dtype, devs[0], tm)
+    compute, flags = _compute_dtype(X.dtype, None if given is None else given.dtype,
+                                    len(counts) if given is None else given.shape[0])
 
     # the plans come from the cache the resident path uses (one per concurrent user and device, handed back at the end):
     # planning the gene order costs ~6 ms of host time at 20 000 genes -- 4 % of a 200 000-cell call -- the first time only
     t0 = _time.perf_counter()
-    ent0, plan0 = _checkout_plan(var_chrom, var_start, window_size, step, exclude_chromosomes, shards[0].device)
+    ent0, plan0 = _checkout_plan(*plan_args, shards[0].device)
     tm["plan"] = _time.perf_counter() - t0
     try:
-        if plan0.n_without_position:
-            log.warning(f"Skipped {plan0.n_without_position} genes because they don't have a genomic position annotated. ")
-        if multi:
-            threads = [threading.Thread(target=shard_thread, args=(s,), daemon=True) for s in shards]
-            for th in threads:
-                th.start()
-            for th in threads:
-                th.join()
-            if errors:
-                real = [e for _, e in sorted(errors, key=lambda x: x[0]) if not isinstance(e, threading.BrokenBarrierError)]
-                raise (real[0] if real else errors[0][1])
-        else:
-            with torch.cuda.device(shards[0].device):
-                run_shard(shards[0])
+        _warn_skipped(plan0)
+        _run_shards(call._replace(
+            chunksize=chunksize, X=X, compute=compute, mean_dtype=mean_dtype, flags=flags, given=given,
+            means_of=(groups, counts, cats), plan_args=plan_args, plan0=(ent0, plan0), shards=shards,
+            barrier=threading.Barrier(len(shards)) if multi else None, ref_box={}, errors=[]))
         chr_pos = dict(plan0.chr_pos)
         n_windows = plan0.n_windows
     finally:
@@ -853,18 +920,11 @@ def infercnv(
     tm["kernel"] = shards[0].tm.get("kernel", 0)
 
     per_gene_mtx = None
-    if calculate_gene_values:
+    if call.calculate_gene_values:
         pieces = [p for s in shards for p in s.gene_pieces]
         per_gene_mtx = np.vstack(pieces) if pieces else np.zeros((0, n_vars))
     tm["total"] = _time.perf_counter() - t_start
-
-    if inplace:
-        adata.obsm[f"X_{key_added}"] = res_mat
-        adata.uns[key_added] = {"chr_pos": chr_pos}
-        if calculate_gene_values:
-            adata.layers[f"gene_values_{key_added}"] = per_gene_mtx
-    else:
-        return chr_pos, res_mat, per_gene_mtx
+    return chr_pos, res_mat, per_gene_mtx
 
 
 def _concat_csr(parts, n_rows, n_cols):
