@@ -836,6 +836,41 @@ int icv_copy_states_viterbi(const icv_matrix *m, const int32_t *chr_start, int32
                             int32_t n_levels, int32_t neutral, double h, double stay, double sw, int8_t *states,
                             int8_t *sign, int32_t *nonneutral, void *stream);
 
+/* ---- tl.cnv_copy_posteriors and tl.cnv_copy_states_filter: posteriors of the model of tl.cnv_copy_states ---
+ * icv_copy_posterior_chains: forward-backward along every chromosome of every row of m under the K-state model of
+ * icv_copy_states_viterbi (m, chr_start, levels, n_levels = K, neutral and h as there); ps = 1 - p and
+ * pw = p / (K - 1) are the host's doubles for a p in (0, 1), pw a normal float64.  The rules are those of
+ * icv_posterior_chains with K states: b(s) = exp_(e_s - max e); pred(s) = (..((al(0) A(0,s)) + (al(1) A(1,s))) + ..) over
+ * r ascending, u = pred b, c = (..(u(0) + u(1)) + ..), al = u / c; be_t(r) = (..((A(r,0) g(0)) + (A(r,1) g(1))) + ..) / c_{t+1}
+ * with g = b_{t+1} be_{t+1}; the posterior is (al_t be_t) / (..(w(0) + w(1)) + ..).  Float64, no fused multiply-add, every
+ * division correctly rounded: a pure function of the arguments, and with the levels (-a, 0, a) the bytes of
+ * icv_posterior_chains for the amplitude a.  neutral_out (device float64, n_rows x n_cols row-major, no padding) receives
+ * P(neutral); planes_out is null or receives all K planes (n_levels x n_rows x n_cols, plane s = P(state s)).  A window
+ * that no chromosome covers gets 1.0 in the neutral plane and 0.0 in the others.  One wavefront per row, 8 (K + 1) bytes of
+ * LDS per window: 1 <= n_cols <= ICV_COPY_POSTERIOR_MAX_WINDOWS(K).  ICV_ERR_INVALID, with the rule in icv_last_error and
+ * before anything is launched or any pointer but levels is read, for a null m, chr_start, levels or neutral_out, n_cols
+ * outside that range, n_chr outside [1, n_cols], every model that icv_copy_states_viterbi refuses, an h that is not finite
+ * and > 0, a ps outside (0, 1), a pw that is not a normal float64 in (0, 1), and an incomplete matrix.  No rows: ICV_OK,
+ * nothing is launched.  No synchronisation.
+ * icv_copy_states_filter: icv_states_filter for calls that are levels.  states (device int8, values in [-7, 7]) and
+ * p_neutral (device float64), both n_rows x n_cols row-major without padding.  A run is a maximal stretch of ONE level
+ * other than 0 inside one chromosome (+1 +1 +2 +2 is two runs).  With q_t = int64(rint(p_neutral[i,t] 2^40)), a run [s, e)
+ * is reset to 0 in filtered (device int8) iff double(sum of its q_t) / (double(e - s) 2^40) > max_p_normal (in [0, 1]);
+ * every other window is copied.  sign (device int8) receives filtered clipped to -1 / 0 / +1, the format of
+ * icv_states_viterbi.  nonneutral[i] / removed[i] (device int32) = the windows of filtered's row i that are not 0 / the
+ * runs of row i that were reset.  *bad (device int32) is set to 0 and then to 1 where a call is outside [-7, 7] or a
+ * posterior is not a number in [0, 1].  With calls in {-1, 0, +1} filtered, nonneutral, removed and bad are those of
+ * icv_states_filter.  n_cols <= ICV_FILTER_MAX_WINDOWS (ICV_ERR_UNSUPPORTED beyond); ICV_ERR_INVALID for a null pointer,
+ * n_rows < 0, n_cols < 1, n_chr outside [1, n_cols] or a max_p_normal outside [0, 1].  No synchronisation. */
+#define ICV_COPY_POSTERIOR_LDS_BYTES 163840
+#define ICV_COPY_POSTERIOR_MAX_WINDOWS(k) (ICV_COPY_POSTERIOR_LDS_BYTES / (8 * ((k) + 1)))
+int icv_copy_posterior_chains(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, const double *levels,
+                              int32_t n_levels, int32_t neutral, double h, double ps, double pw, double *neutral_out,
+                              double *planes_out_or_null, void *stream);
+int icv_copy_states_filter(const int8_t *states, const double *p_neutral, int64_t n_rows, int32_t n_cols,
+                           const int32_t *chr_start, int32_t n_chr, double max_p_normal, int8_t *filtered, int8_t *sign,
+                           int32_t *nonneutral, int32_t *removed, int32_t *bad, void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

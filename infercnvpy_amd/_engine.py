@@ -1920,6 +1920,43 @@ def states_filter(states, p_neutral, chr_start, max_p_normal):
     return filtered, count, removed, bad
 
 
+# ---- tl.cnv_copy_posteriors / tl.cnv_copy_states_filter: the K-state forward-backward chains and filter ----
+def copy_posterior_chains(dm: DeviceMatrix, chr_start, *, levels, neutral, h, ps, pw, all_states=False):
+    """(neutral, planes): device float64 ``n x W`` P(neutral) and, with ``all_states``, device float64 ``K x n x W`` with
+    plane s = P(state s) (else None), by DESIGN.md 4.23 rules 2-6.  ``levels``: the K state means (host floats,
+    ``levels[neutral] == 0``); ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The launch
+    is enqueued on the current stream; nothing is read back."""
+    n, w = dm.shape
+    mu = (C.c_double * len(levels))(*(float(v) for v in levels))
+    return _hmm_call(_lib.load().icv_copy_posterior_chains, dm, chr_start, (mu, len(levels), int(neutral), h, ps, pw),
+                     lambda torch: (torch.empty((n, w), dtype=torch.float64, device="cuda"),
+                                    torch.empty((len(levels), n, w), dtype=torch.float64, device="cuda")
+                                    if all_states else None))
+
+
+def copy_states_filter(states, p_neutral, chr_start, max_p_normal):
+    """(filtered int8 n x W, sign int8 n x W, nonneutral int32 n, removed int32 n, bad int32 flag), device tensors: the
+    levels of ``states`` (device int8, in [-7, 7]) with every run of one level whose mean ``p_neutral`` (device float64)
+    is above ``max_p_normal`` reset to 0, and the same clipped to -1 / 0 / +1 (the filter's rules 1-3).
+    Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
+    assert p_neutral.is_cuda and p_neutral.dtype == torch.float64 and p_neutral.is_contiguous()
+    assert p_neutral.shape == states.shape and p_neutral.device == states.device
+    n, w = int(states.shape[0]), int(states.shape[1])
+    with torch.cuda.device(states.device):
+        cs, n_chr = _chr_start_upload(torch, chr_start)
+        filtered = torch.empty((n, w), dtype=torch.int8, device="cuda")
+        sign = torch.empty((n, w), dtype=torch.int8, device="cuda")
+        count, removed = _empty(torch, n, torch.int32), _empty(torch, n, torch.int32)
+        bad = torch.empty(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.icv_copy_states_filter(_ptr(states), _ptr(p_neutral), n, w, _ptr(cs), n_chr,
+                                              float(max_p_normal), _ptr(filtered), _ptr(sign), _ptr(count),
+                                              _ptr(removed), _ptr(bad), _stream_ptr(torch)))
+    return filtered, sign, count, removed, bad
+
+
 # ---- tl.cnv_segments: runs of the int8 call matrix, group votes and consensus on the device (icv_segments_*, icv_state_*) --
 def dense_input(x):
     """A dense array (the int8 calls, the float64 posteriors) as a contiguous CUDA tensor: a CUDA tensor is read where it

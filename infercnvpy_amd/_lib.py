@@ -27,6 +27,14 @@ ICV_POSTERIOR_MAX_WINDOWS = 4096  # windows icv_posterior_chains keeps in LDS pe
 ICV_CHANGEPOINT_MAX_CHR_WINDOWS = 4096  # windows of one chromosome icv_changepoint_levels keeps in LDS (include/infercnv_hip.h)
 ICV_RANK_MAX_CELLS = 1 << 21  # cells icv_rank_sums ranks against each other: N^3 in an int64 (include/infercnv_hip.h)
 ICV_FILTER_MAX_WINDOWS = 1 << 22  # windows per row of icv_states_filter: a run's int64 sum (include/infercnv_hip.h)
+ICV_COPY_POSTERIOR_LDS_BYTES = 163840  # LDS of one cell of icv_copy_posterior_chains (include/infercnv_hip.h)
+
+
+def ICV_COPY_POSTERIOR_MAX_WINDOWS(k):
+    """Windows icv_copy_posterior_chains keeps in LDS per cell with k states (the macro of include/infercnv_hip.h)."""
+    return ICV_COPY_POSTERIOR_LDS_BYTES // (8 * (k + 1))
+
+
 (ICV_KERNEL_NONE, ICV_KERNEL_GENERIC, ICV_KERNEL_WS, ICV_KERNEL_WS_CSR, ICV_KERNEL_X16, ICV_KERNEL_SD,
  ICV_KERNEL_SPLIT) = range(7)
 
@@ -59,6 +67,7 @@ EXPORTS = (
     "icv_rank_count", "icv_rank_scatter", "icv_rank_sort", "icv_rank_sums", "icv_rank_finish",
     "icv_neighbor_pool_sizes", "icv_neighbor_pool",
     "icv_copy_states_viterbi",
+    "icv_copy_posterior_chains", "icv_copy_states_filter",
 )
 
 
@@ -220,6 +229,8 @@ def load():
     lib.icv_neighbor_pool_sizes.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.icv_neighbor_pool.argtypes = [P(Matrix), vp, vp, i64, i32, vp, vp, i64, vp, vp]
     lib.icv_copy_states_viterbi.argtypes = [P(Matrix), vp, i32, P(dbl), i32, i32, dbl, dbl, dbl, vp, vp, vp, vp]
+    lib.icv_copy_posterior_chains.argtypes = [P(Matrix), vp, i32, P(dbl), i32, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.icv_copy_states_filter.argtypes = [vp, vp, i64, i32, vp, i32, dbl, vp, vp, vp, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -46,6 +46,7 @@
 #include "icv_tsne.hpp"
 #include "icv_states.hpp"
 #include "icv_copy_states.hpp"
+#include "icv_copy_posterior.hpp"
 #include "icv_segments.hpp"
 #include "icv_hmmfit.hpp"
 #include "icv_posterior.hpp"
@@ -3872,18 +3873,19 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
 // ---- the chain kernels of the HMM functions (csrc/icv_hmm.hpp): what their entry points share --------------------------------
 namespace {
 
-// The argument checks of icv_states_viterbi, icv_posterior_chains, icv_posterior_stats and icv_copy_states_viterbi, in the
-// order they are reported.
+// The argument checks of icv_states_viterbi, icv_posterior_chains, icv_posterior_stats, icv_copy_states_viterbi and
+// icv_copy_posterior_chains, in the order they are reported.
 // who: the entry point without icv_; outputs_ok: its own pointers; cap, lds_per_window: its window cap and the LDS bytes a
-// window takes; params_ok, params_rule: its verdict on the model's scalars and the words for it.
+// window takes (cap_note: what the two depend on, for the message); params_ok, params_rule: its verdict on the model's
+// scalars and the words for it.
 int hmm_check(const std::string& who, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, bool outputs_ok, int cap,
-              int lds_per_window, bool params_ok, const char* params_rule) {
+              int lds_per_window, bool params_ok, const char* params_rule, const std::string& cap_note = "") {
     if (!matrix_header_ok(m) || !chr_start || !outputs_ok || n_chr < 1)
         return fail(ICV_ERR_INVALID, "bad " + who + " arguments");
     if (m->n_cols < 1 || m->n_cols > cap)
         return fail(ICV_ERR_INVALID, who + ": n_cols = " + std::to_string(m->n_cols) + " must lie in [1, " +
                                          std::to_string(cap) + "] (" + std::to_string(lds_per_window) +
-                                         " bytes of LDS per window)");
+                                         " bytes of LDS per window" + cap_note + ")");
     if (n_chr > m->n_cols) return fail(ICV_ERR_INVALID, who + ": more chromosomes than windows");
     if (!params_ok) return fail(ICV_ERR_INVALID, who + ": " + params_rule);
     if (!matrix_complete(m) || (m->format == ICV_DENSE && m->ld < m->n_cols))
@@ -4497,6 +4499,75 @@ int icv_copy_states_viterbi(const icv_matrix* m, const int32_t* chr_start, int32
         case 7: return cs_launch<7>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
         default: return cs_launch<8>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
     }
+}
+
+}  // extern "C"
+
+// ---- tl.cnv_copy_posteriors and tl.cnv_copy_states_filter ---------------------------------------------------
+static_assert(icv::kCpLdsBytes == ICV_COPY_POSTERIOR_LDS_BYTES && icv::kCpLdsBytes <= icv::kLdsLimit,
+              "the header's LDS budget is the kernel's and one cell fits a CU's LDS");
+static_assert(icv::cp_max_windows(2) == ICV_COPY_POSTERIOR_MAX_WINDOWS(2) &&
+                  icv::cp_max_windows(icv::kCsMaxStates) == ICV_COPY_POSTERIOR_MAX_WINDOWS(icv::kCsMaxStates),
+              "the header's window cap is the kernel's");
+
+namespace {
+
+template <int K>
+int cp_launch(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const icv::CpParams& P, double* neutral,
+              double* planes, void* stream) {
+    return hmm_launch([](auto t, auto csr) { return icv::k_copy_posterior_chains<decltype(t), decltype(csr)::value, K>; }, m,
+                      chr_start, n_chr, icv::cp_lds_bytes(m->n_cols, K), stream, P, neutral, planes);
+}
+
+}  // namespace
+
+extern "C" {
+
+int icv_copy_posterior_chains(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const double* levels,
+                              int32_t n_levels, int32_t neutral, double h, double ps, double pw, double* neutral_out,
+                              double* planes_out_or_null, void* stream) {
+    // the model check of icv_copy_states_viterbi (its stay and sw have no part here), then this entry's own scalars
+    const char* fault = levels ? cs_params_fault(levels, n_levels, neutral, h, 0.0, 0.0) : nullptr;
+    if (levels && !fault && !(ps > 0.0 && ps < 1.0 && std::isnormal(pw) && pw > 0.0 && pw < 1.0))
+        fault = "ps = 1 - p and pw = p / (n_levels - 1) for a p in (0, 1): ps in (0, 1), pw a normal float64 in (0, 1)";
+    const int k = std::min(std::max(n_levels, 2), icv::kCsMaxStates);  // (an n_levels outside [2, 8] is the model's fault)
+    ICV_TRY(hmm_check("copy_posterior_chains", m, chr_start, n_chr, levels && neutral_out, icv::cp_max_windows(k),
+                      8 * (k + 1), fault == nullptr, fault ? fault : "", " with K = " + std::to_string(k) + " states"));
+    icv::CpParams P{};
+    for (int32_t s = 0; s < n_levels; ++s) P.mu[s] = levels[s];
+    P.mu[neutral] = 0.0;  // (a -0.0 is used as 0.0)
+    P.h = h, P.ps = ps, P.pw = pw, P.z = neutral;
+    switch (n_levels) {
+        case 2: return cp_launch<2>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
+        case 3: return cp_launch<3>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
+        case 4: return cp_launch<4>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
+        case 5: return cp_launch<5>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
+        case 6: return cp_launch<6>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
+        case 7: return cp_launch<7>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
+        default: return cp_launch<8>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
+    }
+}
+
+int icv_copy_states_filter(const int8_t* states, const double* p_neutral, int64_t n_rows, int32_t n_cols,
+                           const int32_t* chr_start, int32_t n_chr, double max_p_normal, int8_t* filtered, int8_t* sign,
+                           int32_t* nonneutral, int32_t* removed, int32_t* bad, void* stream) {
+    if (seg_bad_shape(states, n_rows, n_cols, chr_start, n_chr) || !p_neutral || !filtered || !sign || !nonneutral ||
+        !removed || !bad || !(max_p_normal >= 0.0 && max_p_normal <= 1.0))
+        return fail(ICV_ERR_INVALID, "bad copy_states_filter arguments");
+    if (n_cols > ICV_FILTER_MAX_WINDOWS)
+        return fail(ICV_ERR_UNSUPPORTED, "copy_states_filter: n_cols = " + std::to_string(n_cols) + " is above " +
+                                             std::to_string(ICV_FILTER_MAX_WINDOWS) + " (the int64 sum of a run)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return ICV_OK;
+    const int64_t blocks = (n_rows + icv::kFiRowsPerBlock - 1) / icv::kFiRowsPerBlock;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "copy_states_filter: too many rows for one call");
+    AsyncBuf mask;
+    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
+    hipLaunchKernelGGL(icv::k_copy_states_filter, dim3((unsigned)blocks), dim3(64 * icv::kFiRowsPerBlock), 0, st, states,
+                       p_neutral, n_rows, n_cols, mask.as<uint32_t>(), max_p_normal, filtered, sign, nonneutral, removed, bad);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
 }
 
 }  // extern "C"
