@@ -871,6 +871,29 @@ int icv_copy_states_filter(const int8_t *states, const double *p_neutral, int64_
                            const int32_t *chr_start, int32_t n_chr, double max_p_normal, int8_t *filtered, int8_t *sign,
                            int32_t *nonneutral, int32_t *removed, int32_t *bad, void *stream);
 
+/* ---- tl.cnv_copy_states_fit: the E-step of the Baum-Welch fit of the model of tl.cnv_copy_states ------------
+ * icv_copy_posterior_stats: forward-backward exactly as icv_copy_posterior_chains (the same arguments, rules and bits of
+ * b, al_t, c_t, be_t, z_t and gamma_t), reduced per row to stats[i] = (N_0 .. N_{K-1}, M_0 .. M_{K-1}, S) (device float64,
+ * n_rows x (2K + 1) row-major).  Per chromosome of T >= 1 windows the 2K + 1 sums start at 0.0 and take their terms for
+ * t = T-1 down to 0: N_s += gamma_t(s); M_s += gamma_t(s) x_t (the product rounded before the add); for t <= T-2,
+ * S += (st / c_{t+1}) / z_t with m(s) = (al_t(s) ps) g(s), g = b_{t+1} be_{t+1} and st = (..(m(0) + m(1)) + ..) + m(K-1).
+ * The row's sums start at 0.0 and add the chromosome sums in ascending chromosome order; a chromosome without windows
+ * and a window that no chromosome covers add nothing.  Float64, no fused multiply-add, no atomics: a pure function of the
+ * arguments, and with the levels (-a, 0, a) S is the bytes of column 2 of icv_posterior_stats for the amplitude a.  One
+ * wavefront per row; its LDS holds the row, K planes and 2K + 1 sums per chromosome:
+ * ICV_COPY_POSTERIOR_STATS_LDS(n_cols, K, n_chr) <= ICV_COPY_POSTERIOR_LDS_BYTES, that is
+ * 1 <= n_cols <= ICV_COPY_POSTERIOR_STATS_MAX_WINDOWS(K, n_chr).  ICV_ERR_INVALID, with the rule in icv_last_error, before
+ * anything is launched or any pointer but levels is read and in the order of icv_copy_posterior_chains, for a null m,
+ * chr_start, levels or stats, n_cols outside that range, n_chr outside [1, n_cols], every model and scalar that
+ * icv_copy_posterior_chains refuses, and an incomplete matrix.  No rows: ICV_OK, nothing is launched.  No
+ * synchronisation. */
+#define ICV_COPY_POSTERIOR_STATS_LDS(n_cols, k, n_chr) (8 * (((k) + 1) * (n_cols) + (2 * (k) + 1) * (n_chr)))
+#define ICV_COPY_POSTERIOR_STATS_MAX_WINDOWS(k, n_chr) \
+    ((ICV_COPY_POSTERIOR_LDS_BYTES - 8 * (2 * (k) + 1) * (n_chr)) / (8 * ((k) + 1)))
+int icv_copy_posterior_stats(const icv_matrix *m, const int32_t *chr_start, int32_t n_chr, const double *levels,
+                             int32_t n_levels, int32_t neutral, double h, double ps, double pw, double *stats,
+                             void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

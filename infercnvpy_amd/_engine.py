@@ -1934,6 +1934,17 @@ def copy_posterior_chains(dm: DeviceMatrix, chr_start, *, levels, neutral, h, ps
                                     if all_states else None))
 
 
+def copy_posterior_stats(dm: DeviceMatrix, chr_start, *, levels, neutral, h, ps, pw):
+    """Device float64 ``n x (2K + 1)``: per cell the sums ``(N_0 .. N_{K-1}, M_0 .. M_{K-1}, S)`` of DESIGN.md 4.24, the
+    E-step of ``tl.cnv_copy_states_fit``.  ``levels``: the K state means (host floats, ``levels[neutral] == 0``);
+    ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The launch is enqueued on the current
+    stream; nothing is read back."""
+    k = len(levels)
+    mu = (C.c_double * k)(*(float(v) for v in levels))
+    return _hmm_call(_lib.load().icv_copy_posterior_stats, dm, chr_start, (mu, k, int(neutral), h, ps, pw), lambda torch: (
+        torch.empty((dm.shape[0], 2 * k + 1), dtype=torch.float64, device="cuda"),))[0]
+
+
 def copy_states_filter(states, p_neutral, chr_start, max_p_normal):
     """(filtered int8 n x W, sign int8 n x W, nonneutral int32 n, removed int32 n, bad int32 flag), device tensors: the
     levels of ``states`` (device int8, in [-7, 7]) with every run of one level whose mean ``p_neutral`` (device float64)

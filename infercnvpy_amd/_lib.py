@@ -35,6 +35,18 @@ def ICV_COPY_POSTERIOR_MAX_WINDOWS(k):
     return ICV_COPY_POSTERIOR_LDS_BYTES // (8 * (k + 1))
 
 
+def ICV_COPY_POSTERIOR_STATS_LDS(n_cols, k, n_chr):
+    """LDS bytes of one cell of icv_copy_posterior_stats: the row, k planes and 2k + 1 sums per chromosome (the macro of
+    include/infercnv_hip.h); at most ICV_COPY_POSTERIOR_LDS_BYTES."""
+    return 8 * ((k + 1) * n_cols + (2 * k + 1) * n_chr)
+
+
+def ICV_COPY_POSTERIOR_STATS_MAX_WINDOWS(k, n_chr):
+    """Windows icv_copy_posterior_stats takes with k states and n_chr chromosomes (the macro of include/infercnv_hip.h);
+    0 where the chromosomes' sums alone take the LDS."""
+    return max(ICV_COPY_POSTERIOR_LDS_BYTES - 8 * (2 * k + 1) * n_chr, 0) // (8 * (k + 1))
+
+
 (ICV_KERNEL_NONE, ICV_KERNEL_GENERIC, ICV_KERNEL_WS, ICV_KERNEL_WS_CSR, ICV_KERNEL_X16, ICV_KERNEL_SD,
  ICV_KERNEL_SPLIT) = range(7)
 
@@ -68,6 +80,7 @@ EXPORTS = (
     "icv_neighbor_pool_sizes", "icv_neighbor_pool",
     "icv_copy_states_viterbi",
     "icv_copy_posterior_chains", "icv_copy_states_filter",
+    "icv_copy_posterior_stats",
 )
 
 
@@ -231,6 +244,7 @@ def load():
     lib.icv_copy_states_viterbi.argtypes = [P(Matrix), vp, i32, P(dbl), i32, i32, dbl, dbl, dbl, vp, vp, vp, vp]
     lib.icv_copy_posterior_chains.argtypes = [P(Matrix), vp, i32, P(dbl), i32, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.icv_copy_states_filter.argtypes = [vp, vp, i64, i32, vp, i32, dbl, vp, vp, vp, vp, vp, vp]
+    lib.icv_copy_posterior_stats.argtypes = [P(Matrix), vp, i32, P(dbl), i32, i32, dbl, dbl, dbl, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

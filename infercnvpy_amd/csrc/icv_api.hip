@@ -47,6 +47,7 @@
 #include "icv_states.hpp"
 #include "icv_copy_states.hpp"
 #include "icv_copy_posterior.hpp"
+#include "icv_copy_hmmfit.hpp"
 #include "icv_segments.hpp"
 #include "icv_hmmfit.hpp"
 #include "icv_posterior.hpp"
@@ -3873,11 +3874,12 @@ int icv_tsne_iterations(const int64_t* indptr, const int32_t* indices, const flo
 // ---- the chain kernels of the HMM functions (csrc/icv_hmm.hpp): what their entry points share --------------------------------
 namespace {
 
-// The argument checks of icv_states_viterbi, icv_posterior_chains, icv_posterior_stats, icv_copy_states_viterbi and
-// icv_copy_posterior_chains, in the order they are reported.
+// The argument checks of icv_states_viterbi, icv_posterior_chains, icv_posterior_stats, icv_copy_states_viterbi,
+// icv_copy_posterior_chains and icv_copy_posterior_stats, in the order they are reported.
 // who: the entry point without icv_; outputs_ok: its own pointers; cap, lds_per_window: its window cap and the LDS bytes a
-// window takes (cap_note: what the two depend on, for the message); params_ok, params_rule: its verdict on the model's
-// scalars and the words for it.
+// window takes (cap_note: what the two depend on, for the message; a cap of 0, where what does not depend on the windows
+// fills the LDS alone, refuses every n_cols); params_ok, params_rule: its verdict on the model's scalars and the words
+// for it.
 int hmm_check(const std::string& who, const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, bool outputs_ok, int cap,
               int lds_per_window, bool params_ok, const char* params_rule, const std::string& cap_note = "") {
     if (!matrix_header_ok(m) || !chr_start || !outputs_ok || n_chr < 1)
@@ -4509,14 +4511,42 @@ static_assert(icv::kCpLdsBytes == ICV_COPY_POSTERIOR_LDS_BYTES && icv::kCpLdsByt
 static_assert(icv::cp_max_windows(2) == ICV_COPY_POSTERIOR_MAX_WINDOWS(2) &&
                   icv::cp_max_windows(icv::kCsMaxStates) == ICV_COPY_POSTERIOR_MAX_WINDOWS(icv::kCsMaxStates),
               "the header's window cap is the kernel's");
+static_assert(ICV_COPY_POSTERIOR_STATS_MAX_WINDOWS(6, 1) == 2923 && ICV_COPY_POSTERIOR_STATS_LDS(2923, 6, 1) <= icv::kCpLdsBytes &&
+                  ICV_COPY_POSTERIOR_STATS_LDS(2924, 6, 1) > icv::kCpLdsBytes,
+              "the header's cap of icv_copy_posterior_stats is the largest n_cols whose LDS fits");
 
 namespace {
+
+// what is wrong with the model of icv_copy_posterior_chains and icv_copy_posterior_stats, in the order it is reported: the
+// model check of icv_copy_states_viterbi (its stay and sw have no part here), then these entries' own scalars
+const char* cp_params_fault(const double* levels, int32_t n_levels, int32_t neutral, double h, double ps, double pw) {
+    const char* fault = cs_params_fault(levels, n_levels, neutral, h, 0.0, 0.0);
+    if (!fault && !(ps > 0.0 && ps < 1.0 && std::isnormal(pw) && pw > 0.0 && pw < 1.0))
+        fault = "ps = 1 - p and pw = p / (n_levels - 1) for a p in (0, 1): ps in (0, 1), pw a normal float64 in (0, 1)";
+    return fault;
+}
+
+// levels, neutral, h, ps and pw as the kernels take them
+icv::CpParams cp_params(const double* levels, int32_t n_levels, int32_t neutral, double h, double ps, double pw) {
+    icv::CpParams P{};
+    for (int32_t s = 0; s < n_levels; ++s) P.mu[s] = levels[s];
+    P.mu[neutral] = 0.0;  // (a -0.0 is used as 0.0)
+    P.h = h, P.ps = ps, P.pw = pw, P.z = neutral;
+    return P;
+}
 
 template <int K>
 int cp_launch(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const icv::CpParams& P, double* neutral,
               double* planes, void* stream) {
     return hmm_launch([](auto t, auto csr) { return icv::k_copy_posterior_chains<decltype(t), decltype(csr)::value, K>; }, m,
                       chr_start, n_chr, icv::cp_lds_bytes(m->n_cols, K), stream, P, neutral, planes);
+}
+
+template <int K>
+int cps_launch(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const icv::CpParams& P, double* stats,
+               void* stream) {
+    return hmm_launch([](auto t, auto csr) { return icv::k_copy_posterior_stats<decltype(t), decltype(csr)::value, K>; }, m,
+                      chr_start, n_chr, (size_t)icv::cps_lds_bytes(m->n_cols, K, n_chr), stream, P, stats);
 }
 
 }  // namespace
@@ -4526,17 +4556,11 @@ extern "C" {
 int icv_copy_posterior_chains(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const double* levels,
                               int32_t n_levels, int32_t neutral, double h, double ps, double pw, double* neutral_out,
                               double* planes_out_or_null, void* stream) {
-    // the model check of icv_copy_states_viterbi (its stay and sw have no part here), then this entry's own scalars
-    const char* fault = levels ? cs_params_fault(levels, n_levels, neutral, h, 0.0, 0.0) : nullptr;
-    if (levels && !fault && !(ps > 0.0 && ps < 1.0 && std::isnormal(pw) && pw > 0.0 && pw < 1.0))
-        fault = "ps = 1 - p and pw = p / (n_levels - 1) for a p in (0, 1): ps in (0, 1), pw a normal float64 in (0, 1)";
+    const char* fault = levels ? cp_params_fault(levels, n_levels, neutral, h, ps, pw) : nullptr;
     const int k = std::min(std::max(n_levels, 2), icv::kCsMaxStates);  // (an n_levels outside [2, 8] is the model's fault)
     ICV_TRY(hmm_check("copy_posterior_chains", m, chr_start, n_chr, levels && neutral_out, icv::cp_max_windows(k),
                       8 * (k + 1), fault == nullptr, fault ? fault : "", " with K = " + std::to_string(k) + " states"));
-    icv::CpParams P{};
-    for (int32_t s = 0; s < n_levels; ++s) P.mu[s] = levels[s];
-    P.mu[neutral] = 0.0;  // (a -0.0 is used as 0.0)
-    P.h = h, P.ps = ps, P.pw = pw, P.z = neutral;
+    const icv::CpParams P = cp_params(levels, n_levels, neutral, h, ps, pw);
     switch (n_levels) {
         case 2: return cp_launch<2>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
         case 3: return cp_launch<3>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
@@ -4545,6 +4569,29 @@ int icv_copy_posterior_chains(const icv_matrix* m, const int32_t* chr_start, int
         case 6: return cp_launch<6>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
         case 7: return cp_launch<7>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
         default: return cp_launch<8>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
+    }
+}
+
+// ---- tl.cnv_copy_states_fit: the E-step of the Baum-Welch fit of the K-state model
+int icv_copy_posterior_stats(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const double* levels,
+                             int32_t n_levels, int32_t neutral, double h, double ps, double pw, double* stats,
+                             void* stream) {
+    const char* fault = levels ? cp_params_fault(levels, n_levels, neutral, h, ps, pw) : nullptr;
+    const int k = std::min(std::max(n_levels, 2), icv::kCsMaxStates);  // (an n_levels outside [2, 8] is the model's fault)
+    ICV_TRY(hmm_check("copy_posterior_stats", m, chr_start, n_chr, levels && stats, icv::cps_max_windows(k, n_chr),
+                      8 * (k + 1), fault == nullptr, fault ? fault : "",
+                      " with K = " + std::to_string(k) + " states, beside " + std::to_string(8 * (2 * k + 1)) +
+                          " bytes for each of the " + std::to_string(n_chr) + " chromosomes, of " +
+                          std::to_string(icv::kCpLdsBytes) + " bytes"));
+    const icv::CpParams P = cp_params(levels, n_levels, neutral, h, ps, pw);
+    switch (n_levels) {
+        case 2: return cps_launch<2>(m, chr_start, n_chr, P, stats, stream);
+        case 3: return cps_launch<3>(m, chr_start, n_chr, P, stats, stream);
+        case 4: return cps_launch<4>(m, chr_start, n_chr, P, stats, stream);
+        case 5: return cps_launch<5>(m, chr_start, n_chr, P, stats, stream);
+        case 6: return cps_launch<6>(m, chr_start, n_chr, P, stats, stream);
+        case 7: return cps_launch<7>(m, chr_start, n_chr, P, stats, stream);
+        default: return cps_launch<8>(m, chr_start, n_chr, P, stats, stream);
     }
 }
 

@@ -34,7 +34,8 @@ def cnv_copy_posteriors(adata, use_rep="cnv", key_added="cnv_copy_posterior", in
     Forward-backward on the hidden Markov chain of :func:`infercnvpy_amd.tl.cnv_copy_states`: K states with Gaussian
     emissions of means ``levels`` and standard deviation ``sigma``, probability ``switch_prob`` of leaving a state between
     two windows (each of the other K - 1 states gets an equal share), one chain per chromosome and cell.  Requires running
-    :func:`infercnvpy_amd.tl.infercnv` first.
+    :func:`infercnvpy_amd.tl.infercnv` first.  :func:`infercnvpy_amd.tl.cnv_copy_states_fit` fits the model to the matrix;
+    called with its ``params``, ``tl.cnv_copy_states`` leaves them where this function picks them up.
 
     Parameters
     ----------

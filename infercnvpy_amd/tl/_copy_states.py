@@ -50,6 +50,7 @@ def cnv_copy_states(adata, use_rep="cnv", key_added="cnv_copy_states", inplace=T
     A K-state hidden Markov chain with Gaussian emissions of means ``levels`` and standard deviation ``sigma`` runs along
     each chromosome of each cell; the most likely path (Viterbi) is the call, reported as the state's distance from the
     neutral one.  Chains never cross a chromosome boundary.  Requires running :func:`infercnvpy_amd.tl.infercnv` first.
+    :func:`infercnvpy_amd.tl.cnv_copy_states_fit` fits ``levels`` and ``sigma`` to the matrix in place of the defaults.
 
     Parameters
     ----------

@@ -39,25 +39,25 @@ def _m_step(gs, ds, ks, qs, n_total, n_steps, a, sigma, p, fit):
     return (a, sigma, p) if ok else None
 
 
-def _fit_options(fit, max_iter, tol):
+def _fit_options(fit, max_iter, tol, who="tl.cnv_states_fit"):
     """(the fitted names in the order of _NAMES, tol as a float) of the checked ``fit``, ``max_iter`` and ``tol``."""
     if isinstance(fit, str):
         fit = (fit,)
     try:
         names = list(fit)
     except TypeError:
-        raise ValueError(f"tl.cnv_states_fit: fit={fit!r} must be a sequence of parameter names") from None
+        raise ValueError(f"{who}: fit={fit!r} must be a sequence of parameter names") from None
     unknown = [k for k in names if k not in _NAMES]
     if unknown or not names:
-        raise ValueError(f"tl.cnv_states_fit: fit={fit!r} must be a non-empty subset of {_NAMES}")
+        raise ValueError(f"{who}: fit={fit!r} must be a non-empty subset of {_NAMES}")
     if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
-        raise ValueError(f"tl.cnv_states_fit: max_iter={max_iter!r} must be an int >= 1")
+        raise ValueError(f"{who}: max_iter={max_iter!r} must be an int >= 1")
     try:
         tol_f = float(tol)
     except (TypeError, ValueError):
-        raise ValueError(f"tl.cnv_states_fit: tol={tol!r} must be a number") from None
+        raise ValueError(f"{who}: tol={tol!r} must be a number") from None
     if isinstance(tol, bool) or not (math.isfinite(tol_f) and tol_f >= 0.0):
-        raise ValueError(f"tl.cnv_states_fit: tol={tol!r} must be finite and >= 0")
+        raise ValueError(f"{who}: tol={tol!r} must be finite and >= 0")
     return [k for k in _NAMES if k in names], tol_f
 
 

@@ -157,7 +157,7 @@ class Model(NamedTuple):
 
 
 def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch_prob, log_switch, sum_of_squares,
-            zero_model=False, then=None):
+            zero_model=False, then=None, default_sigma=None):
     """The common opening of the three functions: arguments checked, matrix on the device, model resolved.
 
     who
@@ -178,6 +178,9 @@ def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch
     then
         Called after the model's arguments are checked and before anything touches the device: the caller's checks of
         its remaining arguments.  What it returns is ``Model.rest``.
+    default_sigma
+        None, or ``default_sigma(dm, bounds, rms)``: the caller's own default for a ``sigma`` of None, given the root
+        mean square that is the default otherwise.
 
     Raises in this order: keys, shape, cap, ``chr_pos``, ``amplitude``, ``sigma``, ``switch_prob``, ``then()``, and
     only then what needs the device (non-finite values, overflows)."""
@@ -234,6 +237,8 @@ def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch
             qs = math.inf
         if sig is None:
             sig = math.sqrt(qs / (float(n) * float(w)))
+            if default_sigma is not None and math.isfinite(sig):
+                sig = default_sigma(dm, bounds, sig)
         if not (math.isfinite(qs) and math.isfinite(sig)):
             raise ValueError(f"{who}: the sum of squares of {key} overflows float64" if sum_of_squares else
                              f"{who}: the default sigma of {key} overflows float64; pass sigma")
