@@ -1839,14 +1839,20 @@ def states_viterbi(dm: DeviceMatrix, chr_start, *, amplitude, h, stay, sw):
         torch.empty((n, w), dtype=torch.int8, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")))
 
 
+def _levels_arg(levels, neutral):
+    """(the K state means as a ctypes array, K, neutral): what the three icv_copy_* chain entries take for the model's
+    levels.  ``levels``: host floats, ``levels[neutral] == 0``."""
+    k = len(levels)
+    return (C.c_double * k)(*(float(v) for v in levels)), k, int(neutral)
+
+
 def copy_states_viterbi(dm: DeviceMatrix, chr_start, *, levels, neutral, h, stay, sw):
     """(states, sign, nonneutral): device int8 ``n x W`` of ``state - neutral``, the same clipped to -1 / 0 / +1, and
     device int32 counts of the windows that are not 0 (DESIGN.md 4.22 rules 2-5).  ``levels``: the K state means (host
     floats, ``levels[neutral] == 0``); ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The
     launch is enqueued on the current stream; nothing is read back."""
     n, w = dm.shape
-    mu = (C.c_double * len(levels))(*(float(v) for v in levels))
-    return _hmm_call(_lib.load().icv_copy_states_viterbi, dm, chr_start, (mu, len(levels), int(neutral), h, stay, sw),
+    return _hmm_call(_lib.load().icv_copy_states_viterbi, dm, chr_start, (*_levels_arg(levels, neutral), h, stay, sw),
                      lambda torch: (torch.empty((n, w), dtype=torch.int8, device="cuda"),
                                     torch.empty((n, w), dtype=torch.int8, device="cuda"),
                                     torch.empty(n, dtype=torch.int32, device="cuda")))
@@ -1899,25 +1905,30 @@ def posterior_stats(dm: DeviceMatrix, chr_start, *, amplitude, h, ps, pw):
         torch.empty((dm.shape[0], 3), dtype=torch.float64, device="cuda"),))[0]
 
 
-def states_filter(states, p_neutral, chr_start, max_p_normal):
-    """(filtered int8 n x W, nonneutral int32 n, removed int32 n, bad int32 flag), device tensors: the calls of
-    ``states`` (device int8) with every run whose mean ``p_neutral`` (device float64) is above ``max_p_normal`` reset to
-    0 (DESIGN.md 4.15, the filter's rules 1-3).  Nothing is read back."""
+def _filter_call(entry, states, p_neutral, chr_start, thr, with_sign):
+    """What :func:`states_filter` and :func:`copy_states_filter` share: ``entry(states, p_neutral, n, W, chr_start, C, thr,
+    filtered, [sign,] nonneutral, removed, bad, stream)`` on the current stream.  Returns (filtered int8 n x W, [sign int8
+    n x W,] nonneutral int32 n, removed int32 n, bad int32 flag), device tensors; nothing is read back."""
     torch = _torch()
-    lib = _lib.load()
     assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
     assert p_neutral.is_cuda and p_neutral.dtype == torch.float64 and p_neutral.is_contiguous()
     assert p_neutral.shape == states.shape and p_neutral.device == states.device
     n, w = int(states.shape[0]), int(states.shape[1])
     with torch.cuda.device(states.device):
         cs, n_chr = _chr_start_upload(torch, chr_start)
-        filtered = torch.empty((n, w), dtype=torch.int8, device="cuda")
+        planes = tuple(torch.empty((n, w), dtype=torch.int8, device="cuda") for _ in range(2 if with_sign else 1))
         count, removed = _empty(torch, n, torch.int32), _empty(torch, n, torch.int32)
         bad = torch.empty(1, dtype=torch.int32, device="cuda")
-        _lib.check(lib.icv_states_filter(_ptr(states), _ptr(p_neutral), n, w, _ptr(cs), n_chr,
-                                         float(max_p_normal), _ptr(filtered), _ptr(count), _ptr(removed), _ptr(bad),
-                                         _stream_ptr(torch)))
-    return filtered, count, removed, bad
+        _lib.check(entry(_ptr(states), _ptr(p_neutral), n, w, _ptr(cs), n_chr, float(thr), *(_ptr(t) for t in planes),
+                         _ptr(count), _ptr(removed), _ptr(bad), _stream_ptr(torch)))
+    return (*planes, count, removed, bad)
+
+
+def states_filter(states, p_neutral, chr_start, max_p_normal):
+    """(filtered int8 n x W, nonneutral int32 n, removed int32 n, bad int32 flag), device tensors: the calls of
+    ``states`` (device int8) with every run whose mean ``p_neutral`` (device float64) is above ``max_p_normal`` reset to
+    0 (DESIGN.md 4.15, the filter's rules 1-3).  Nothing is read back."""
+    return _filter_call(_lib.load().icv_states_filter, states, p_neutral, chr_start, max_p_normal, False)
 
 
 # ---- tl.cnv_copy_posteriors / tl.cnv_copy_states_filter: the K-state forward-backward chains and filter (DESIGN.md 4.23) ----
@@ -1927,8 +1938,7 @@ def copy_posterior_chains(dm: DeviceMatrix, chr_start, *, levels, neutral, h, ps
     ``levels[neutral] == 0``); ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The launch
     is enqueued on the current stream; nothing is read back."""
     n, w = dm.shape
-    mu = (C.c_double * len(levels))(*(float(v) for v in levels))
-    return _hmm_call(_lib.load().icv_copy_posterior_chains, dm, chr_start, (mu, len(levels), int(neutral), h, ps, pw),
+    return _hmm_call(_lib.load().icv_copy_posterior_chains, dm, chr_start, (*_levels_arg(levels, neutral), h, ps, pw),
                      lambda torch: (torch.empty((n, w), dtype=torch.float64, device="cuda"),
                                     torch.empty((len(levels), n, w), dtype=torch.float64, device="cuda")
                                     if all_states else None))
@@ -1939,10 +1949,8 @@ def copy_posterior_stats(dm: DeviceMatrix, chr_start, *, levels, neutral, h, ps,
     E-step of ``tl.cnv_copy_states_fit``.  ``levels``: the K state means (host floats, ``levels[neutral] == 0``);
     ``chr_start``: host int32 array of C + 1 ascending window numbers from 0 to W.  The launch is enqueued on the current
     stream; nothing is read back."""
-    k = len(levels)
-    mu = (C.c_double * k)(*(float(v) for v in levels))
-    return _hmm_call(_lib.load().icv_copy_posterior_stats, dm, chr_start, (mu, k, int(neutral), h, ps, pw), lambda torch: (
-        torch.empty((dm.shape[0], 2 * k + 1), dtype=torch.float64, device="cuda"),))[0]
+    return _hmm_call(_lib.load().icv_copy_posterior_stats, dm, chr_start, (*_levels_arg(levels, neutral), h, ps, pw),
+                     lambda torch: (torch.empty((dm.shape[0], 2 * len(levels) + 1), dtype=torch.float64, device="cuda"),))[0]
 
 
 def copy_states_filter(states, p_neutral, chr_start, max_p_normal):
@@ -1950,22 +1958,7 @@ def copy_states_filter(states, p_neutral, chr_start, max_p_normal):
     levels of ``states`` (device int8, in [-7, 7]) with every run of one level whose mean ``p_neutral`` (device float64)
     is above ``max_p_normal`` reset to 0, and the same clipped to -1 / 0 / +1 (the filter's rules 1-3).
     Nothing is read back."""
-    torch = _torch()
-    lib = _lib.load()
-    assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
-    assert p_neutral.is_cuda and p_neutral.dtype == torch.float64 and p_neutral.is_contiguous()
-    assert p_neutral.shape == states.shape and p_neutral.device == states.device
-    n, w = int(states.shape[0]), int(states.shape[1])
-    with torch.cuda.device(states.device):
-        cs, n_chr = _chr_start_upload(torch, chr_start)
-        filtered = torch.empty((n, w), dtype=torch.int8, device="cuda")
-        sign = torch.empty((n, w), dtype=torch.int8, device="cuda")
-        count, removed = _empty(torch, n, torch.int32), _empty(torch, n, torch.int32)
-        bad = torch.empty(1, dtype=torch.int32, device="cuda")
-        _lib.check(lib.icv_copy_states_filter(_ptr(states), _ptr(p_neutral), n, w, _ptr(cs), n_chr,
-                                              float(max_p_normal), _ptr(filtered), _ptr(sign), _ptr(count),
-                                              _ptr(removed), _ptr(bad), _stream_ptr(torch)))
-    return filtered, sign, count, removed, bad
+    return _filter_call(_lib.load().icv_copy_states_filter, states, p_neutral, chr_start, max_p_normal, True)
 
 
 # ---- tl.cnv_segments: runs of the int8 call matrix, group votes and consensus on the device (icv_segments_*, icv_state_*) --

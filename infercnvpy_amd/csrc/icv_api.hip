@@ -3989,6 +3989,32 @@ bool seg_bad_shape(const void* states, int64_t n_rows, int32_t n_cols, const int
 
 constexpr int64_t kSegMaxBlocks = 0x7fffffffLL;
 
+// what icv_states_filter and icv_copy_states_filter do after their own pointer checks; who: the entry point without icv_;
+// sign: the second plane of icv_copy_states_filter (k_copy_states_filter), null for icv_states_filter (k_states_filter)
+int filter_launch(const char* who, const int8_t* states, const double* p_neutral, int64_t n_rows, int32_t n_cols,
+                  const int32_t* chr_start, int32_t n_chr, double max_p_normal, int8_t* filtered, int8_t* sign,
+                  int32_t* nonneutral, int32_t* removed, int32_t* bad, void* stream) {
+    if (n_cols > ICV_FILTER_MAX_WINDOWS)
+        return fail(ICV_ERR_UNSUPPORTED, std::string(who) + ": n_cols = " + std::to_string(n_cols) + " is above " +
+                                             std::to_string(ICV_FILTER_MAX_WINDOWS) + " (the int64 sum of a run)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return ICV_OK;
+    const int64_t blocks = (n_rows + icv::kFiRowsPerBlock - 1) / icv::kFiRowsPerBlock;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, std::string(who) + ": too many rows for one call");
+    AsyncBuf mask;
+    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
+    const dim3 grid((unsigned)blocks), block(64 * icv::kFiRowsPerBlock);
+    if (sign)
+        hipLaunchKernelGGL(icv::k_copy_states_filter, grid, block, 0, st, states, p_neutral, n_rows, n_cols,
+                           mask.as<uint32_t>(), max_p_normal, filtered, sign, nonneutral, removed, bad);
+    else
+        hipLaunchKernelGGL(icv::k_states_filter, grid, block, 0, st, states, p_neutral, n_rows, n_cols,
+                           mask.as<uint32_t>(), max_p_normal, filtered, nonneutral, removed, bad);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
 // k_seg_rows<fill> over all rows with the chromosome mask of the call; who: the entry point without icv_
 int seg_rows_launch(bool fill, const char* who, const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start,
                     int32_t n_chr, hipStream_t st, int64_t* counts, int32_t* bad, const int64_t* offsets, int64_t n_segments,
@@ -4096,20 +4122,8 @@ int icv_states_filter(const int8_t* states, const double* p_neutral, int64_t n_r
     if (seg_bad_shape(states, n_rows, n_cols, chr_start, n_chr) || !p_neutral || !filtered || !nonneutral || !removed ||
         !bad || !(max_p_normal >= 0.0 && max_p_normal <= 1.0))
         return fail(ICV_ERR_INVALID, "bad states_filter arguments");
-    if (n_cols > ICV_FILTER_MAX_WINDOWS)
-        return fail(ICV_ERR_UNSUPPORTED, "states_filter: n_cols = " + std::to_string(n_cols) + " is above " +
-                                             std::to_string(ICV_FILTER_MAX_WINDOWS) + " (the int64 sum of a run)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
-    if (n_rows == 0) return ICV_OK;
-    const int64_t blocks = (n_rows + icv::kFiRowsPerBlock - 1) / icv::kFiRowsPerBlock;
-    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "states_filter: too many rows for one call");
-    AsyncBuf mask;
-    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
-    hipLaunchKernelGGL(icv::k_states_filter, dim3((unsigned)blocks), dim3(64 * icv::kFiRowsPerBlock), 0, st, states,
-                       p_neutral, n_rows, n_cols, mask.as<uint32_t>(), max_p_normal, filtered, nonneutral, removed, bad);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return filter_launch("states_filter", states, p_neutral, n_rows, n_cols, chr_start, n_chr, max_p_normal, filtered, nullptr,
+                         nonneutral, removed, bad, stream);
 }
 
 
@@ -4451,9 +4465,18 @@ int icv_neighbor_pool(const icv_matrix* m, const int64_t* g_indptr, const int32_
 
 }  // extern "C"
 
-// ---- tl.cnv_copy_states: the K-state Viterbi chain -----------------------------------------------------------
+// ---- the K-state model: tl.cnv_copy_states, tl.cnv_copy_posteriors, tl.cnv_copy_states_filter, tl.cnv_copy_states_fit
+//  ------------------------------------------------------------------------------------------------
 static_assert(icv::kCsMaxWindows == ICV_COPY_STATES_MAX_WINDOWS, "the header's window cap is the kernel's");
 static_assert((size_t)icv::kCsMaxWindows * icv::kCsLdsPerWindow <= (size_t)icv::kLdsLimit, "one cell fits a CU's LDS");
+static_assert(icv::kCpLdsBytes == ICV_COPY_POSTERIOR_LDS_BYTES && icv::kCpLdsBytes <= icv::kLdsLimit,
+              "the header's LDS budget is the kernel's and one cell fits a CU's LDS");
+static_assert(icv::cp_max_windows(2) == ICV_COPY_POSTERIOR_MAX_WINDOWS(2) &&
+                  icv::cp_max_windows(icv::kCsMaxStates) == ICV_COPY_POSTERIOR_MAX_WINDOWS(icv::kCsMaxStates),
+              "the header's window cap is the kernel's");
+static_assert(ICV_COPY_POSTERIOR_STATS_MAX_WINDOWS(6, 1) == 2923 && ICV_COPY_POSTERIOR_STATS_LDS(2923, 6, 1) <= icv::kCpLdsBytes &&
+                  ICV_COPY_POSTERIOR_STATS_LDS(2924, 6, 1) > icv::kCpLdsBytes,
+              "the header's cap of icv_copy_posterior_stats is the largest n_cols whose LDS fits");
 
 namespace {
 
@@ -4471,11 +4494,40 @@ const char* cs_params_fault(const double* levels, int32_t n_levels, int32_t neut
     return nullptr;
 }
 
-template <int K>
-int cs_launch(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const icv::CsParams& P, int8_t* states,
-              int8_t* sign, int32_t* nonneutral, void* stream) {
-    return hmm_launch([](auto t, auto csr) { return icv::k_copy_states_viterbi<decltype(t), decltype(csr)::value, K>; }, m,
-                      chr_start, n_chr, icv::cs_lds_bytes(m->n_cols), stream, P, states, sign, nonneutral);
+// what is wrong with the model of icv_copy_posterior_chains and icv_copy_posterior_stats, in the order it is reported: the
+// model check of icv_copy_states_viterbi (its stay and sw have no part here), then these entries' own scalars
+const char* cp_params_fault(const double* levels, int32_t n_levels, int32_t neutral, double h, double ps, double pw) {
+    const char* fault = cs_params_fault(levels, n_levels, neutral, h, 0.0, 0.0);
+    if (!fault && !(ps > 0.0 && ps < 1.0 && std::isnormal(pw) && pw > 0.0 && pw < 1.0))
+        fault = "ps = 1 - p and pw = p / (n_levels - 1) for a p in (0, 1): ps in (0, 1), pw a normal float64 in (0, 1)";
+    return fault;
+}
+
+// the checked model as the kernels take it; stay, sw: log(1 - p), log(p / (K - 1)) for Viterbi, ps, pw for forward-backward
+icv::CsParams cs_params(const double* levels, int32_t n_levels, int32_t neutral, double h, double stay, double sw) {
+    icv::CsParams P{};
+    for (int32_t k = 0; k < n_levels; ++k) P.mu[k] = levels[k];
+    P.mu[neutral] = 0.0;  // (a -0.0 is used as 0.0)
+    P.h = h, P.stay = stay, P.sw = sw, P.z = neutral;
+    return P;
+}
+
+// the K of a window cap and its message: an n_levels outside [2, 8] is the model's fault, which is reported after the cap
+int cs_cap_states(int32_t n_levels) { return std::min(std::max(n_levels, 2), icv::kCsMaxStates); }
+
+// One instantiation by the number of states (2 .. 8, checked by the caller): f, a generic lambda, gets
+// std::integral_constant<int, K>.
+template <typename F>
+int by_states(int32_t n_levels, F&& f) {
+    switch (n_levels) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        default: return f(std::integral_constant<int, 8>{});
+    }
 }
 
 }  // namespace
@@ -4488,111 +4540,46 @@ int icv_copy_states_viterbi(const icv_matrix* m, const int32_t* chr_start, int32
     const char* fault = levels ? cs_params_fault(levels, n_levels, neutral, h, stay, sw) : nullptr;
     ICV_TRY(hmm_check("copy_states_viterbi", m, chr_start, n_chr, levels && states && sign && nonneutral,
                       ICV_COPY_STATES_MAX_WINDOWS, icv::kCsLdsPerWindow, fault == nullptr, fault ? fault : ""));
-    icv::CsParams P{};
-    for (int32_t k = 0; k < n_levels; ++k) P.mu[k] = levels[k];
-    P.mu[neutral] = 0.0;  // (a -0.0 is used as 0.0)
-    P.h = h, P.stay = stay, P.sw = sw, P.z = neutral;
-    switch (n_levels) {
-        case 2: return cs_launch<2>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
-        case 3: return cs_launch<3>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
-        case 4: return cs_launch<4>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
-        case 5: return cs_launch<5>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
-        case 6: return cs_launch<6>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
-        case 7: return cs_launch<7>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
-        default: return cs_launch<8>(m, chr_start, n_chr, P, states, sign, nonneutral, stream);
-    }
+    const icv::CsParams P = cs_params(levels, n_levels, neutral, h, stay, sw);
+    return by_states(n_levels, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        return hmm_launch([](auto t, auto csr) { return icv::k_copy_states_viterbi<decltype(t), decltype(csr)::value, K>; }, m,
+                          chr_start, n_chr, icv::cs_lds_bytes(m->n_cols), stream, P, states, sign, nonneutral);
+    });
 }
-
-}  // extern "C"
-
-// ---- tl.cnv_copy_posteriors and tl.cnv_copy_states_filter ---------------------------------------------------
-static_assert(icv::kCpLdsBytes == ICV_COPY_POSTERIOR_LDS_BYTES && icv::kCpLdsBytes <= icv::kLdsLimit,
-              "the header's LDS budget is the kernel's and one cell fits a CU's LDS");
-static_assert(icv::cp_max_windows(2) == ICV_COPY_POSTERIOR_MAX_WINDOWS(2) &&
-                  icv::cp_max_windows(icv::kCsMaxStates) == ICV_COPY_POSTERIOR_MAX_WINDOWS(icv::kCsMaxStates),
-              "the header's window cap is the kernel's");
-static_assert(ICV_COPY_POSTERIOR_STATS_MAX_WINDOWS(6, 1) == 2923 && ICV_COPY_POSTERIOR_STATS_LDS(2923, 6, 1) <= icv::kCpLdsBytes &&
-                  ICV_COPY_POSTERIOR_STATS_LDS(2924, 6, 1) > icv::kCpLdsBytes,
-              "the header's cap of icv_copy_posterior_stats is the largest n_cols whose LDS fits");
-
-namespace {
-
-// what is wrong with the model of icv_copy_posterior_chains and icv_copy_posterior_stats, in the order it is reported: the
-// model check of icv_copy_states_viterbi (its stay and sw have no part here), then these entries' own scalars
-const char* cp_params_fault(const double* levels, int32_t n_levels, int32_t neutral, double h, double ps, double pw) {
-    const char* fault = cs_params_fault(levels, n_levels, neutral, h, 0.0, 0.0);
-    if (!fault && !(ps > 0.0 && ps < 1.0 && std::isnormal(pw) && pw > 0.0 && pw < 1.0))
-        fault = "ps = 1 - p and pw = p / (n_levels - 1) for a p in (0, 1): ps in (0, 1), pw a normal float64 in (0, 1)";
-    return fault;
-}
-
-// levels, neutral, h, ps and pw as the kernels take them
-icv::CpParams cp_params(const double* levels, int32_t n_levels, int32_t neutral, double h, double ps, double pw) {
-    icv::CpParams P{};
-    for (int32_t s = 0; s < n_levels; ++s) P.mu[s] = levels[s];
-    P.mu[neutral] = 0.0;  // (a -0.0 is used as 0.0)
-    P.h = h, P.ps = ps, P.pw = pw, P.z = neutral;
-    return P;
-}
-
-template <int K>
-int cp_launch(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const icv::CpParams& P, double* neutral,
-              double* planes, void* stream) {
-    return hmm_launch([](auto t, auto csr) { return icv::k_copy_posterior_chains<decltype(t), decltype(csr)::value, K>; }, m,
-                      chr_start, n_chr, icv::cp_lds_bytes(m->n_cols, K), stream, P, neutral, planes);
-}
-
-template <int K>
-int cps_launch(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const icv::CpParams& P, double* stats,
-               void* stream) {
-    return hmm_launch([](auto t, auto csr) { return icv::k_copy_posterior_stats<decltype(t), decltype(csr)::value, K>; }, m,
-                      chr_start, n_chr, (size_t)icv::cps_lds_bytes(m->n_cols, K, n_chr), stream, P, stats);
-}
-
-}  // namespace
-
-extern "C" {
 
 int icv_copy_posterior_chains(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const double* levels,
                               int32_t n_levels, int32_t neutral, double h, double ps, double pw, double* neutral_out,
                               double* planes_out_or_null, void* stream) {
     const char* fault = levels ? cp_params_fault(levels, n_levels, neutral, h, ps, pw) : nullptr;
-    const int k = std::min(std::max(n_levels, 2), icv::kCsMaxStates);  // (an n_levels outside [2, 8] is the model's fault)
-    ICV_TRY(hmm_check("copy_posterior_chains", m, chr_start, n_chr, levels && neutral_out, icv::cp_max_windows(k),
-                      8 * (k + 1), fault == nullptr, fault ? fault : "", " with K = " + std::to_string(k) + " states"));
-    const icv::CpParams P = cp_params(levels, n_levels, neutral, h, ps, pw);
-    switch (n_levels) {
-        case 2: return cp_launch<2>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
-        case 3: return cp_launch<3>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
-        case 4: return cp_launch<4>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
-        case 5: return cp_launch<5>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
-        case 6: return cp_launch<6>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
-        case 7: return cp_launch<7>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
-        default: return cp_launch<8>(m, chr_start, n_chr, P, neutral_out, planes_out_or_null, stream);
-    }
+    const int kc = cs_cap_states(n_levels);
+    ICV_TRY(hmm_check("copy_posterior_chains", m, chr_start, n_chr, levels && neutral_out, icv::cp_max_windows(kc),
+                      8 * (kc + 1), fault == nullptr, fault ? fault : "", " with K = " + std::to_string(kc) + " states"));
+    const icv::CsParams P = cs_params(levels, n_levels, neutral, h, ps, pw);
+    return by_states(n_levels, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        return hmm_launch([](auto t, auto csr) { return icv::k_copy_posterior_chains<decltype(t), decltype(csr)::value, K>; }, m,
+                          chr_start, n_chr, icv::cp_lds_bytes(m->n_cols, K), stream, P, neutral_out, planes_out_or_null);
+    });
 }
 
-// ---- tl.cnv_copy_states_fit: the E-step of the Baum-Welch fit of the K-state model
+// the E-step of the Baum-Welch fit of the K-state model
 int icv_copy_posterior_stats(const icv_matrix* m, const int32_t* chr_start, int32_t n_chr, const double* levels,
                              int32_t n_levels, int32_t neutral, double h, double ps, double pw, double* stats,
                              void* stream) {
     const char* fault = levels ? cp_params_fault(levels, n_levels, neutral, h, ps, pw) : nullptr;
-    const int k = std::min(std::max(n_levels, 2), icv::kCsMaxStates);  // (an n_levels outside [2, 8] is the model's fault)
-    ICV_TRY(hmm_check("copy_posterior_stats", m, chr_start, n_chr, levels && stats, icv::cps_max_windows(k, n_chr),
-                      8 * (k + 1), fault == nullptr, fault ? fault : "",
-                      " with K = " + std::to_string(k) + " states, beside " + std::to_string(8 * (2 * k + 1)) +
+    const int kc = cs_cap_states(n_levels);
+    ICV_TRY(hmm_check("copy_posterior_stats", m, chr_start, n_chr, levels && stats, icv::cps_max_windows(kc, n_chr),
+                      8 * (kc + 1), fault == nullptr, fault ? fault : "",
+                      " with K = " + std::to_string(kc) + " states, beside " + std::to_string(8 * (2 * kc + 1)) +
                           " bytes for each of the " + std::to_string(n_chr) + " chromosomes, of " +
                           std::to_string(icv::kCpLdsBytes) + " bytes"));
-    const icv::CpParams P = cp_params(levels, n_levels, neutral, h, ps, pw);
-    switch (n_levels) {
-        case 2: return cps_launch<2>(m, chr_start, n_chr, P, stats, stream);
-        case 3: return cps_launch<3>(m, chr_start, n_chr, P, stats, stream);
-        case 4: return cps_launch<4>(m, chr_start, n_chr, P, stats, stream);
-        case 5: return cps_launch<5>(m, chr_start, n_chr, P, stats, stream);
-        case 6: return cps_launch<6>(m, chr_start, n_chr, P, stats, stream);
-        case 7: return cps_launch<7>(m, chr_start, n_chr, P, stats, stream);
-        default: return cps_launch<8>(m, chr_start, n_chr, P, stats, stream);
-    }
+    const icv::CsParams P = cs_params(levels, n_levels, neutral, h, ps, pw);
+    return by_states(n_levels, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        return hmm_launch([](auto t, auto csr) { return icv::k_copy_posterior_stats<decltype(t), decltype(csr)::value, K>; }, m,
+                          chr_start, n_chr, (size_t)icv::cps_lds_bytes(m->n_cols, K, n_chr), stream, P, stats);
+    });
 }
 
 int icv_copy_states_filter(const int8_t* states, const double* p_neutral, int64_t n_rows, int32_t n_cols,
@@ -4601,20 +4588,8 @@ int icv_copy_states_filter(const int8_t* states, const double* p_neutral, int64_
     if (seg_bad_shape(states, n_rows, n_cols, chr_start, n_chr) || !p_neutral || !filtered || !sign || !nonneutral ||
         !removed || !bad || !(max_p_normal >= 0.0 && max_p_normal <= 1.0))
         return fail(ICV_ERR_INVALID, "bad copy_states_filter arguments");
-    if (n_cols > ICV_FILTER_MAX_WINDOWS)
-        return fail(ICV_ERR_UNSUPPORTED, "copy_states_filter: n_cols = " + std::to_string(n_cols) + " is above " +
-                                             std::to_string(ICV_FILTER_MAX_WINDOWS) + " (the int64 sum of a run)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
-    if (n_rows == 0) return ICV_OK;
-    const int64_t blocks = (n_rows + icv::kFiRowsPerBlock - 1) / icv::kFiRowsPerBlock;
-    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "copy_states_filter: too many rows for one call");
-    AsyncBuf mask;
-    ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
-    hipLaunchKernelGGL(icv::k_copy_states_filter, dim3((unsigned)blocks), dim3(64 * icv::kFiRowsPerBlock), 0, st, states,
-                       p_neutral, n_rows, n_cols, mask.as<uint32_t>(), max_p_normal, filtered, sign, nonneutral, removed, bad);
-    HIP_TRY(hipGetLastError());
-    return ICV_OK;
+    return filter_launch("copy_states_filter", states, p_neutral, n_rows, n_cols, chr_start, n_chr, max_p_normal, filtered, sign,
+                         nonneutral, removed, bad, stream);
 }
 
 }  // extern "C"

@@ -18,8 +18,10 @@
 // Geometry: that of k_copy_posterior_chains: one wavefront per cell, the row through hmm_load_row, lane c running the
 // chromosomes c, c + 64, ..., K a template parameter with everything per state in registers.  The forward pass is the one
 // of cp_forward_backward (al_t into K planes of W doubles); the backward pass is written out here, because it keeps
-// gamma_t in registers and stores no plane: giving cp_forward_backward a per-step sink would have to leave the code of
-// the 28 instantiations of k_copy_posterior_chains byte for byte as it is, and the sibling does so by not touching it.
+// gamma_t in registers and stores no plane.  One chain for both kernels was built twice and put back (DESIGN.md 4.24,
+// "One chain, measured"): a per-step sink as hmm_forward_backward has one, and __forceinline__ helpers for the forward
+// pass and the recurrence step.  Either changes the compiled code of all 56 instantiations (a helper for the forward pass
+// alone does), and each left one kernel slower than the run-to-run spread of the code as it is.
 // st / c_{t+1} is formed in the step that reads al_t from LDS, where g and c_{t+1} are live, and carried as one double to
 // the next step, where z_t is known.
 //
@@ -34,7 +36,7 @@
 
 #include <cstdint>
 
-#include "icv_copy_posterior.hpp"  // CpParams, cp_emit, cp_pred, cp_sum, kCpLdsBytes
+#include "icv_copy_posterior.hpp"  // CsParams, cp_emit, cp_pred, cp_sum, kCpLdsBytes
 #include "icv_hmm.hpp"             // hmm_load_row, hmm_chr
 
 namespace icv {
@@ -53,7 +55,7 @@ inline int cps_max_windows(int k, int64_t n_chr) {
 // g + s W, where the forward pass leaves al_t.  N, M: K sums each, S: one.
 template <int K>
 __device__ __forceinline__ void cps_chain_stats(const double* x, double* g, int32_t W, int32_t s0, int32_t s1,
-                                                const CpParams& P, double (&N)[K], double (&M)[K], double& S) {
+                                                const CsParams& P, double (&N)[K], double (&M)[K], double& S) {
     double b[K], a[K], p[K], u[K];
     // rule 3, as cp_forward_backward runs it
     cp_emit<K>(x[s0], P, b);
@@ -102,13 +104,13 @@ __device__ __forceinline__ void cps_chain_stats(const double* x, double* g, int3
 #pragma unroll
         for (int s = 0; s < K; ++s) q[s] = b[s] * be[s];
 #pragma unroll
-        for (int s = 0; s < K; ++s) m[s] = (a[s] * P.ps) * q[s];  // a = al_{t-1}, q = rule 4's g at t
+        for (int s = 0; s < K; ++s) m[s] = (a[s] * P.stay) * q[s];  // a = al_{t-1}, q = rule 4's g at t
         stay = cp_sum<K>(m) / cc;
 #pragma unroll
         for (int r = 0; r < K; ++r) {
-            double acc = (r == 0 ? P.ps : P.pw) * q[0];
+            double acc = (r == 0 ? P.stay : P.sw) * q[0];
 #pragma unroll
-            for (int s = 1; s < K; ++s) acc = acc + ((r == s ? P.ps : P.pw) * q[s]);
+            for (int s = 1; s < K; ++s) acc = acc + ((r == s ? P.stay : P.sw) * q[s]);
             be[r] = acc / cc;
         }
     }
@@ -118,7 +120,7 @@ __device__ __forceinline__ void cps_chain_stats(const double* x, double* g, int3
 template <typename T, bool CSR, int K>
 __global__ __launch_bounds__(64) void k_copy_posterior_stats(const T* __restrict__ val, const int64_t* __restrict__ indptr,
                                                              const int32_t* __restrict__ indices, int64_t ld, int32_t W,
-                                                             const int32_t* __restrict__ chr_start, int32_t C, CpParams P,
+                                                             const int32_t* __restrict__ chr_start, int32_t C, CsParams P,
                                                              double* __restrict__ stats) {
     static_assert(K >= 2 && K <= kCsMaxStates, "the model of icv_copy_states_viterbi");
     static_assert(2 * K + 1 <= 64, "one lane per statistic");

@@ -31,15 +31,15 @@
 //   2. a run [s, e) is a maximal stretch of ONE level other than 0 inside one chromosome (+1 +1 +2 +2 is two runs); it has
 //      S = the int64 sum of its q_t and mean = double(S) / (double(e - s) 2^40).
 //   3. the run is reset to 0 iff mean > max_p_normal.
-// Geometry: that of k_states_filter (icv_posterior.hpp), whose body this one repeats with the wider range and the second
-// output plane; sharing the body through a template parameter changed the code of k_states_filter, so it is written out.
+// Geometry and body: those of k_states_filter; both kernels run fi_filter_row (icv_posterior.hpp), here with the wider
+// range and the second output plane.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "icv_copy_states.hpp"  // kCsMaxStates
-#include "icv_posterior.hpp"    // kFiRowsPerBlock, kSegMaskShift
+#include "icv_copy_states.hpp"  // CsParams, kCsMaxStates
+#include "icv_posterior.hpp"    // kFiRowsPerBlock, fi_filter_row
 
 namespace icv {
 
@@ -49,15 +49,9 @@ constexpr int kCfMaxLevel = 7;       // a call of icv_copy_states_viterbi lies i
 
 inline size_t cp_lds_bytes(int32_t n_windows, int k) { return (size_t)n_windows * 8 * (size_t)(k + 1); }
 
-struct CpParams {
-    double mu[kCsMaxStates];  // the first K are used
-    double h, ps, pw;
-    int32_t z;  // the neutral state: mu[z] == 0.0
-};
-
 // rule 2 for the K states
 template <int K>
-__device__ __forceinline__ void cp_emit(double x, const CpParams& P, double (&b)[K]) {
+__device__ __forceinline__ void cp_emit(double x, const CsParams& P, double (&b)[K]) {
     double e[K];
 #pragma unroll
     for (int s = 0; s < K; ++s) {
@@ -72,14 +66,14 @@ __device__ __forceinline__ void cp_emit(double x, const CpParams& P, double (&b)
     for (int s = 0; s < K; ++s) b[s] = ts_exp(e[s] - m);
 }
 
-// pred of rule 3 from al_{t-1}
+// pred of rule 3 from al_{t-1}; P.stay, P.sw: ps, pw of rule 1
 template <int K>
-__device__ __forceinline__ void cp_pred(const double (&a)[K], const CpParams& P, double (&p)[K]) {
+__device__ __forceinline__ void cp_pred(const double (&a)[K], const CsParams& P, double (&p)[K]) {
 #pragma unroll
     for (int s = 0; s < K; ++s) {
-        double acc = a[0] * (s == 0 ? P.ps : P.pw);
+        double acc = a[0] * (s == 0 ? P.stay : P.sw);
 #pragma unroll
-        for (int r = 1; r < K; ++r) acc = acc + (a[r] * (r == s ? P.ps : P.pw));
+        for (int r = 1; r < K; ++r) acc = acc + (a[r] * (r == s ? P.stay : P.sw));
         p[s] = acc;
     }
 }
@@ -97,7 +91,7 @@ __device__ __forceinline__ double cp_sum(const double (&v)[K]) {
 // row; g: K planes of W doubles, plane s at g + s W, where the forward pass leaves al_t and the backward pass gamma_t.
 template <int K>
 __device__ __forceinline__ void cp_forward_backward(const double* x, double* g, int32_t W, int32_t s0, int32_t s1,
-                                                    const CpParams& P) {
+                                                    const CsParams& P) {
     double b[K], a[K], p[K], u[K];
     // rule 3
     cp_emit<K>(x[s0], P, b);
@@ -139,9 +133,9 @@ __device__ __forceinline__ void cp_forward_backward(const double* x, double* g, 
         for (int s = 0; s < K; ++s) q[s] = b[s] * be[s];
 #pragma unroll
         for (int r = 0; r < K; ++r) {
-            double acc = (r == 0 ? P.ps : P.pw) * q[0];
+            double acc = (r == 0 ? P.stay : P.sw) * q[0];
 #pragma unroll
-            for (int s = 1; s < K; ++s) acc = acc + ((r == s ? P.ps : P.pw) * q[s]);
+            for (int s = 1; s < K; ++s) acc = acc + ((r == s ? P.stay : P.sw) * q[s]);
             be[r] = acc / cc;
         }
     }
@@ -151,7 +145,7 @@ __device__ __forceinline__ void cp_forward_backward(const double* x, double* g, 
 template <typename T, bool CSR, int K>
 __global__ __launch_bounds__(64) void k_copy_posterior_chains(const T* __restrict__ val, const int64_t* __restrict__ indptr,
                                                               const int32_t* __restrict__ indices, int64_t ld, int32_t W,
-                                                              const int32_t* __restrict__ chr_start, int32_t C, CpParams P,
+                                                              const int32_t* __restrict__ chr_start, int32_t C, CsParams P,
                                                               double* __restrict__ neutral, double* __restrict__ planes) {
     static_assert(K >= 2 && K <= kCsMaxStates, "the model of icv_copy_states_viterbi");
     extern __shared__ __attribute__((aligned(16))) unsigned char cp_lds[];
@@ -190,111 +184,14 @@ __global__ __launch_bounds__(64) void k_copy_posterior_chains(const T* __restric
 }
 
 // ---- the filter -------------------------------------------------------------------------------------------------------
-// S, P, out, sign: n_rows x W row-major without padding; mask: the chromosome-start bits of k_seg_chr_mask.  out: S with
-// the runs that were reset at 0; sign: out clipped to -1 / 0 / +1; nonneutral[row] = the windows of out's row that are
-// not 0, removed[row] = the runs that were reset.  *bad |= 1 where a call is outside [-7, 7] or a posterior is not a
-// number in [0, 1] (such a posterior counts as 0).  W <= kFiMaxWindows.
+// fi_filter_row (icv_posterior.hpp) on levels in [-7, 7], with the sign plane
 __global__ __launch_bounds__(64 * kFiRowsPerBlock) void k_copy_states_filter(
     const int8_t* __restrict__ S, const double* __restrict__ Pn, int64_t n_rows, int32_t W,
     const uint32_t* __restrict__ mask, double thr, int8_t* __restrict__ out, int8_t* __restrict__ sign,
     int32_t* __restrict__ nonneutral, int32_t* __restrict__ removed, int32_t* __restrict__ bad) {
-    const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * kFiRowsPerBlock + (threadIdx.x >> 6);
     if (row >= n_rows) return;  // (whole wavefronts leave; there is no barrier below)
-    const int8_t* s_row = S + row * (int64_t)W;
-    const double* p_row = Pn + row * (int64_t)W;
-    int8_t* o_row = out + row * (int64_t)W;
-    int8_t* g_row = sign + row * (int64_t)W;
-    auto put = [&](int32_t t, int v) {  // window t of both planes
-        o_row[t] = (int8_t)v;
-        g_row[t] = (int8_t)((v > 0) - (v < 0));
-    };
-
-    int32_t carry_state = 0;   // the call of the window in front of this step
-    int32_t open_start = 0;    // the first window of the run that was open at the end of the step before
-    int64_t open_sum = 0;      // its sum so far
-    int32_t kept = 0, gone = 0;
-    bool invalid = false;
-
-    for (int32_t v0 = 0; v0 < W; v0 += 64) {
-        const int32_t t = v0 + lane;
-        const bool in = t < W;
-        const int s = in ? (int)s_row[t] : 0;
-        const double pv = in ? p_row[t] : 0.0;
-        const bool p_ok = pv >= 0.0 && pv <= 1.0;  // (false for NaN)
-        invalid |= s < -kCfMaxLevel || s > kCfMaxLevel || !p_ok;
-        int prev = __shfl_up(s, 1, 64);
-        if (lane == 0) prev = carry_state;
-        int next = __shfl_down(s, 1, 64);
-        if (lane == 63) next = (t + 1 < W) ? (int)s_row[t + 1] : 0;
-        carry_state = __shfl(s, 63, 64);
-
-        // is window t / t + 1 a chromosome start?  (bit kSegMaskShift + W is never set; the mask has the word)
-        const uint32_t qb = (uint32_t)(in ? t : 0) + kSegMaskShift;
-        const bool cs0 = (mask[qb >> 5] >> (qb & 31)) & 1u;
-        const bool cs1 = (mask[(qb + 1) >> 5] >> ((qb + 1) & 31)) & 1u;
-        const bool sf = s != 0 && (cs0 || prev != s);  // (another level starts another run)
-        const bool ef = s != 0 && (cs1 || next != s);  // (t + 1 == W: next = 0)
-
-        const int64_t q = (s != 0 && p_ok) ? (int64_t)rint(pv * 1099511627776.0) : 0;
-        int64_t incl = q;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t up = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += up;
-        }
-        const int64_t excl = incl - q;
-        const uint64_t smask = __ballot(sf), emask = __ballot(ef);
-
-        // the lane of this window's run start (-1: the run was open when the step began) and of its end (64: it stays open)
-        const uint64_t below = smask & (~0ull >> (63 - lane));
-        const int sl = below ? 63 - __builtin_clzll(below) : -1;
-        const uint64_t above = emask >> lane;
-        const int el = above ? lane + __builtin_ctzll(above) : 64;
-        const int64_t excl_at_start = __shfl(excl, sl < 0 ? 0 : sl, 64);
-
-        // the verdict, formed at the run's last window
-        bool reset = false;
-        if (ef) {
-            const int64_t sum = sl >= 0 ? incl - excl_at_start : open_sum + incl;
-            const int32_t first = sl >= 0 ? v0 + sl : open_start;
-            const int32_t len = t + 1 - first;
-            const double mean = (double)sum / ((double)len * 1099511627776.0);
-            reset = mean > thr;
-            if (reset) ++gone;
-            else kept += len;
-        }
-        const bool my_reset = __shfl((int)reset, el & 63, 64) != 0;
-        if (in) {
-            if (s == 0) put(t, 0);
-            else if (el < 64) put(t, my_reset ? 0 : s);
-        }
-        // the windows of the steps before that belong to a run ending in this step (the run of lane 0, if it was open)
-        const int s_first = __shfl(s, 0, 64);
-        const bool first_open = __shfl((int)(sl < 0 && s != 0 && el < 64), 0, 64) != 0;
-        if (first_open) {
-            const int v = __shfl((int)my_reset, 0, 64) != 0 ? 0 : s_first;
-            for (int32_t k = open_start + lane; k < v0; k += 64) put(k, v);
-        }
-        // the run that stays open: lane 63's, if it has not ended
-        const bool stays = __shfl((int)(s != 0 && el == 64), 63, 64) != 0;
-        if (stays) {
-            const int sl63 = __shfl(sl, 63, 64);
-            const int64_t total = __shfl(incl, 63, 64);
-            if (sl63 >= 0) {
-                open_start = v0 + sl63;
-                open_sum = total - __shfl(excl, sl63, 64);
-            } else {
-                open_sum += total;
-            }
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        kept += __shfl_down(kept, off, 64);
-        gone += __shfl_down(gone, off, 64);
-    }
-    if (lane == 0) nonneutral[row] = kept, removed[row] = gone;
-    if (__ballot(invalid) != 0 && lane == 0) atomicOr(bad, 1);
+    fi_filter_row<kCfMaxLevel, true>(S, Pn, row, W, mask, thr, out, sign, nonneutral, removed, bad);
 }
 
 }  // namespace icv

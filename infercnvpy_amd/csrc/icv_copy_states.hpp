@@ -37,9 +37,12 @@ constexpr int kCsLdsPerWindow = 10;    // the float64 value + the 16-bit back-po
 
 inline size_t cs_lds_bytes(int32_t n_windows) { return ((size_t)n_windows * kCsLdsPerWindow + 15) / 16 * 16; }
 
+// the model of the K-state kernels: k_copy_states_viterbi and the forward-backward kernels of icv_copy_posterior.hpp
 struct CsParams {
     double mu[kCsMaxStates];  // the first K are used
-    double h, stay, sw;
+    double h;
+    double stay, sw;  // a step that stays / leaves for one other state: log(1 - p), log(p / (K - 1)) for Viterbi,
+                      // the probabilities ps = 1 - p, pw = p / (K - 1) for forward-backward
     int32_t z;  // the neutral state: mu[z] == 0.0
 };
 

@@ -85,22 +85,30 @@ __global__ __launch_bounds__(64) void k_posterior_chains(const T* __restrict__ v
 }
 
 // ---- the filter -------------------------------------------------------------------------------------------------------
-// S, P, out: n_rows x W row-major without padding; mask: the chromosome-start bits of k_seg_chr_mask (bit kSegMaskShift + t
-// is window t; seg_mask_words(W) words).  nonneutral[row] = the windows of out's row that are not 0, removed[row] = the
-// runs that were reset.  *bad |= 1 where a state is not -1 / 0 / +1 or a posterior is not a number in [0, 1] (such a
-// posterior counts as 0).  W <= kFiMaxWindows.
-__global__ __launch_bounds__(64 * kFiRowsPerBlock) void k_states_filter(
-    const int8_t* __restrict__ S, const double* __restrict__ Pn, int64_t n_rows, int32_t W,
-    const uint32_t* __restrict__ mask, double thr, int8_t* __restrict__ out, int32_t* __restrict__ nonneutral,
-    int32_t* __restrict__ removed, int32_t* __restrict__ bad) {
+// One row of the filter, for k_states_filter and k_copy_states_filter (icv_copy_posterior.hpp, rules of 4.23): calls in
+// [-MaxLevel, MaxLevel], a run being a maximal stretch of ONE level other than 0 inside one chromosome (with MaxLevel = 1
+// that is rule 1 of 4.14); Sign: the plane `sign` (out clipped to -1 / 0 / +1) is written too, otherwise it is not
+// touched.  S, P, out, sign: n_rows x W row-major without padding; mask: the chromosome-start bits of k_seg_chr_mask (bit
+// kSegMaskShift + t is window t; seg_mask_words(W) words).  nonneutral[row] = the windows of out's row that are not 0,
+// removed[row] = the runs that were reset.  *bad |= 1 where a call is outside the range or a posterior is not a number
+// in [0, 1] (such a posterior counts as 0).  W <= kFiMaxWindows.  Called by all 64 lanes of a wavefront; no barrier.
+template <int MaxLevel, bool Sign>
+__device__ __forceinline__ void fi_filter_row(const int8_t* __restrict__ S, const double* __restrict__ Pn, int64_t row,
+                                              int32_t W, const uint32_t* __restrict__ mask, double thr,
+                                              int8_t* __restrict__ out, int8_t* __restrict__ sign,
+                                              int32_t* __restrict__ nonneutral, int32_t* __restrict__ removed,
+                                              int32_t* __restrict__ bad) {
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * kFiRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= n_rows) return;  // (whole wavefronts leave; there is no barrier below)
     const int8_t* s_row = S + row * (int64_t)W;
     const double* p_row = Pn + row * (int64_t)W;
     int8_t* o_row = out + row * (int64_t)W;
+    int8_t* g_row = Sign ? sign + row * (int64_t)W : nullptr;
+    auto put = [&](int32_t t, int v) {  // window t of out (and of sign)
+        o_row[t] = (int8_t)v;
+        if constexpr (Sign) g_row[t] = (int8_t)((v > 0) - (v < 0));
+    };
 
-    int32_t carry_state = 0;   // the state of the window in front of this step
+    int32_t carry_state = 0;   // the call of the window in front of this step
     int32_t open_start = 0;    // the first window of the run that was open at the end of the step before
     int64_t open_sum = 0;      // its sum so far
     int32_t kept = 0, gone = 0;
@@ -112,7 +120,7 @@ __global__ __launch_bounds__(64 * kFiRowsPerBlock) void k_states_filter(
         const int s = in ? (int)s_row[t] : 0;
         const double pv = in ? p_row[t] : 0.0;
         const bool p_ok = pv >= 0.0 && pv <= 1.0;  // (false for NaN)
-        invalid |= s < -1 || s > 1 || !p_ok;
+        invalid |= s < -MaxLevel || s > MaxLevel || !p_ok;
         int prev = __shfl_up(s, 1, 64);
         if (lane == 0) prev = carry_state;
         int next = __shfl_down(s, 1, 64);
@@ -123,7 +131,7 @@ __global__ __launch_bounds__(64 * kFiRowsPerBlock) void k_states_filter(
         const uint32_t qb = (uint32_t)(in ? t : 0) + kSegMaskShift;
         const bool cs0 = (mask[qb >> 5] >> (qb & 31)) & 1u;
         const bool cs1 = (mask[(qb + 1) >> 5] >> ((qb + 1) & 31)) & 1u;
-        const bool sf = s != 0 && (cs0 || prev != s);
+        const bool sf = s != 0 && (cs0 || prev != s);  // (another level starts another run)
         const bool ef = s != 0 && (cs1 || next != s);  // (t + 1 == W: next = 0)
 
         const int64_t q = (s != 0 && p_ok) ? (int64_t)rint(pv * 1099511627776.0) : 0;
@@ -156,15 +164,15 @@ __global__ __launch_bounds__(64 * kFiRowsPerBlock) void k_states_filter(
         }
         const bool my_reset = __shfl((int)reset, el & 63, 64) != 0;
         if (in) {
-            if (s == 0) o_row[t] = 0;
-            else if (el < 64) o_row[t] = my_reset ? (int8_t)0 : (int8_t)s;
+            if (s == 0) put(t, 0);
+            else if (el < 64) put(t, my_reset ? 0 : s);
         }
         // the windows of the steps before that belong to a run ending in this step (the run of lane 0, if it was open)
         const int s_first = __shfl(s, 0, 64);
         const bool first_open = __shfl((int)(sl < 0 && s != 0 && el < 64), 0, 64) != 0;
         if (first_open) {
-            const int8_t v = __shfl((int)my_reset, 0, 64) != 0 ? (int8_t)0 : (int8_t)s_first;
-            for (int32_t k = open_start + lane; k < v0; k += 64) o_row[k] = v;
+            const int v = __shfl((int)my_reset, 0, 64) != 0 ? 0 : s_first;
+            for (int32_t k = open_start + lane; k < v0; k += 64) put(k, v);
         }
         // the run that stays open: lane 63's, if it has not ended
         const bool stays = __shfl((int)(s != 0 && el == 64), 63, 64) != 0;
@@ -185,6 +193,16 @@ __global__ __launch_bounds__(64 * kFiRowsPerBlock) void k_states_filter(
     }
     if (lane == 0) nonneutral[row] = kept, removed[row] = gone;
     if (__ballot(invalid) != 0 && lane == 0) atomicOr(bad, 1);
+}
+
+// the calls -1 / 0 / +1 of tl.cnv_states: one wavefront per row, kFiRowsPerBlock rows per workgroup
+__global__ __launch_bounds__(64 * kFiRowsPerBlock) void k_states_filter(
+    const int8_t* __restrict__ S, const double* __restrict__ Pn, int64_t n_rows, int32_t W,
+    const uint32_t* __restrict__ mask, double thr, int8_t* __restrict__ out, int32_t* __restrict__ nonneutral,
+    int32_t* __restrict__ removed, int32_t* __restrict__ bad) {
+    const int64_t row = (int64_t)blockIdx.x * kFiRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= n_rows) return;  // (whole wavefronts leave; there is no barrier below)
+    fi_filter_row<1, false>(S, Pn, row, W, mask, thr, out, nullptr, nonneutral, removed, bad);
 }
 
 }  // namespace icv

@@ -12,15 +12,13 @@ max_iter, tol) and equals ``tests/_copy_fit_oracle.py`` bit for bit.
 from __future__ import annotations
 
 import math
-import sys
 import time
 import warnings
 
 from .. import _engine, _lib
 from ._changepoints import default_sigma
-from ._copy_states import DEFAULT_STEPS, MAX_STATES, MIN_STATES
 from ._fit import _NAMES, _P_MAX, _P_MIN, _as_dict, _fit_options
-from ._hmm import check_emissions, resolve
+from ._hmm import DEFAULT_STEPS, MAX_STATES, MIN_STATES, check_emissions, resolve
 
 _WHO = "tl.cnv_copy_states_fit"
 
@@ -163,9 +161,6 @@ def cnv_copy_states_fit(adata, use_rep="cnv", key_added="cnv_copy_states_fit", i
             raise ValueError(f"{_WHO}: {w} windows in {n_chr} chromosomes; the kernel keeps a cell's windows, the forward "
                              f"variables of K = {k} states and {2 * k + 1} sums per chromosome in {lds} bytes of LDS and "
                              f"takes at most {cap} windows")
-        # rule 1 divides switch_prob by K - 1, resolve() tried it with 2
-        if not float(p_start) / (k - 1) >= sys.float_info.min:
-            raise ValueError(f"{_WHO}: switch_prob={switch_prob!r} is too close to 0 or 1 for float64")
         return _fit_options(fit, max_iter, tol, _WHO)
 
     def start_sigma(dm, bounds, rms):
@@ -178,7 +173,8 @@ def cnv_copy_states_fit(adata, use_rep="cnv", key_added="cnv_copy_states_fit", i
     mo = resolve(adata, use_rep, _WHO, max_windows=_lib.ICV_COPY_POSTERIOR_STATS_MAX_WINDOWS(k, 1),
                  keeps=f"a cell's windows, the forward variables of K = {k} states and {2 * k + 1} sums per chromosome "
                        f"({_lib.ICV_COPY_POSTERIOR_LDS_BYTES} bytes)", amplitude=amplitude, sigma=sigma,
-                 switch_prob=p_start, log_switch=False, sum_of_squares=True, then=options, default_sigma=start_sigma)
+                 switch_prob=p_start, log_switch=False, sum_of_squares=True, then=options, default_sigma=start_sigma,
+                 n_states=k)
     fitted, tol_f = mo.rest
     n, bounds, dm, amp, sig, p, qs, t1 = mo.n, mo.bounds, mo.dm, mo.amp, mo.sig, mo.p, mo.qs, mo.t1
     z = lattice.index(0)

@@ -10,12 +10,11 @@ run of one level from integer sums.  Both equal ``tests/_copy_posterior_oracle.p
 """
 from __future__ import annotations
 
-import sys
 import time
 
 from .. import _engine, _lib
-from ._copy_states import DEFAULT_STEPS, check_levels
-from ._hmm import call_matrix, check_emissions, chromosome_bounds, resolve
+from ._hmm import resolve_levels
+from ._posteriors import _filter_runs
 
 _WHO = "tl.cnv_copy_posteriors"
 
@@ -76,43 +75,20 @@ def cnv_copy_posteriors(adata, use_rep="cnv", key_added="cnv_copy_posterior", in
     magnitude.  The kernel keeps a cell's windows and K planes of forward variables in LDS: at most
     ``ICV_COPY_POSTERIOR_MAX_WINDOWS(K) = 163840 // (8 (K + 1))`` windows (3 413 for K = 6).
     """
-    if levels is not None and amplitude is not None:
-        raise ValueError(f"{_WHO}: levels and amplitude are both given; amplitude only spaces the default levels")
-    mu = z = None
-    zero_model = False
+    zero_levels = None
     if levels is None and amplitude is None and sigma is None and switch_prob is None and states_key in adata.uns:
         stored = adata.uns[states_key]
         if isinstance(stored, dict) and "params" in stored:
             par = stored["params"]
             levels, sigma, switch_prob = par["levels"], par["sigma"], par["switch_prob"]
-            zero_model = sigma == 0  # (what tl.cnv_copy_states leaves for an all-zero matrix: its levels are all 0)
-            if zero_model:
-                mu, z = [float(v) for v in levels], int(par["neutral"])
-    if levels is not None and not zero_model:
-        mu, z = check_levels(levels, _WHO)
-    k = len(DEFAULT_STEPS) if mu is None else len(mu)
-    if switch_prob is None:
-        switch_prob = 1e-3
-
-    def other_states_share():
-        # rule 1 divides switch_prob by K - 1, resolve() tried it with 2
-        if not float(switch_prob) / (k - 1) >= sys.float_info.min:
-            raise ValueError(f"{_WHO}: switch_prob={switch_prob!r} is too close to 0 or 1 for float64")
-
-    cap = _lib.ICV_COPY_POSTERIOR_MAX_WINDOWS(k)
-    # rule 7 with given levels is resolve()'s own check under the amplitude max(|levels[0]|, |levels[-1]|)
-    mo = resolve(adata, use_rep, _WHO, max_windows=cap,
-                 keeps=f"a cell's windows and the forward variables of K = {k} states",
-                 amplitude=amplitude if mu is None else max(abs(mu[0]), abs(mu[-1])), sigma=sigma,
-                 switch_prob=switch_prob, log_switch=False, sum_of_squares=False, zero_model=zero_model,
-                 then=other_states_share)
+            if sigma == 0:  # (what tl.cnv_copy_states leaves for an all-zero matrix: its levels are all 0)
+                zero_levels = [float(v) for v in levels], int(par["neutral"])
+    mo, mu, z, k = resolve_levels(
+        adata, use_rep, _WHO, levels=levels, amplitude=amplitude, sigma=sigma,
+        switch_prob=1e-3 if switch_prob is None else switch_prob, log_switch=False, zero_levels=zero_levels,
+        max_windows=_lib.ICV_COPY_POSTERIOR_MAX_WINDOWS,
+        keeps=lambda k: f"a cell's windows and the forward variables of K = {k} states")
     n, w, bounds, sig, p, on_device = mo.n, mo.w, mo.bounds, mo.sig, mo.p, mo.on_device
-    if mu is None:
-        mu = [float(s) * mo.amp for s in DEFAULT_STEPS]
-        z = DEFAULT_STEPS.index(0)
-        if mo.h is not None:
-            mu, z = check_levels(mu, _WHO)
-            check_emissions(_WHO, f"X_{use_rep}", mo.x, mo.m, max(abs(mu[0]), abs(mu[-1])), mo.h, sig)
     names = plane_names(k, z)
     torch = _engine._torch()
     with torch.cuda.device(mo.dm.device):
@@ -185,42 +161,5 @@ def cnv_copy_states_filter(adata, use_rep="cnv_copy_states", posterior_key="cnv_
     they are CUDA tensors (``inplace=True`` copies the two per-cell vectors back for ``adata.obs``).  A posterior that is
     not a number in [0, 1] or a level outside [-7, 7] raises ``ValueError`` (one flag read back from the device).
     """
-    who = "tl.cnv_copy_states_filter"
-    key, pkey = f"X_{use_rep}", f"X_{posterior_key}_neutral"
-    x, post, n, w = call_matrix(adata, who, key, cnv_key, "`tl.infercnv`?", pkey)
-    if w > _lib.ICV_FILTER_MAX_WINDOWS:
-        raise ValueError(f"{who}: {w} windows; a run's int64 sum takes at most {_lib.ICV_FILTER_MAX_WINDOWS}")
-    bounds = chromosome_bounds(adata.uns[cnv_key]["chr_pos"], w)
-    try:
-        thr = float(max_p_normal)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: max_p_normal={max_p_normal!r} must be a number in [0, 1]") from None
-    if isinstance(max_p_normal, bool) or not 0.0 <= thr <= 1.0:
-        raise ValueError(f"{who}: max_p_normal={max_p_normal!r} must lie in [0, 1]")
-
-    torch = _engine._torch()
-    on_device = isinstance(x, torch.Tensor) or isinstance(post, torch.Tensor)
-    t0 = time.perf_counter()
-    states = _engine.dense_input(x)
-    with torch.cuda.device(states.device):
-        p_dev = _engine.dense_input(post).to(states.device)
-        filtered, sign, count, removed, bad = _engine.copy_states_filter(states, p_dev, bounds, thr)
-        fraction = _engine.states_fraction(count, w)
-        if int(bad.item()):
-            raise ValueError(f"{who}: {pkey} has values that are not numbers in [0, 1], or {key} has levels outside "
-                             "[-7, 7]")
-        info = None
-        if return_info:
-            info = {"n_removed": int(removed.sum().item()), "stage_ms": {"filter": (time.perf_counter() - t0) * 1e3}}
-        if not on_device:
-            filtered, sign = filtered.cpu().numpy(), sign.cpu().numpy()
-            fraction, removed = fraction.cpu().numpy(), removed.cpu().numpy()
-    if inplace:
-        adata.obsm[f"X_{key_added}"] = filtered
-        adata.obsm[f"X_{key_added}_sign"] = sign
-        adata.obs[key_added + "_fraction"] = fraction.cpu().numpy() if on_device else fraction
-        adata.obs[key_added + "_removed"] = removed.cpu().numpy() if on_device else removed
-        adata.uns[key_added] = {"params": {"max_p_normal": thr, "use_rep": use_rep, "posterior_key": posterior_key},
-                                "chr_pos": dict(adata.uns[cnv_key]["chr_pos"])}
-        return (filtered, sign, fraction, removed, info) if return_info else None
-    return (filtered, sign, fraction, removed, info) if return_info else (filtered, sign, fraction, removed)
+    return _filter_runs(adata, "tl.cnv_copy_states_filter", _engine.copy_states_filter, "levels outside [-7, 7]", True,
+                        use_rep, posterior_key, cnv_key, key_added, max_p_normal, inplace, return_info)

@@ -16,31 +16,9 @@ import time
 import numpy as np
 
 from .. import _engine, _lib
-from ._hmm import check_emissions, resolve
+from ._hmm import DEFAULT_STEPS, MAX_STATES, MIN_STATES, check_levels, resolve_levels  # noqa: F401 (re-exported)
 
 _WHO = "tl.cnv_copy_states"
-MIN_STATES, MAX_STATES = 2, 8
-DEFAULT_STEPS = (-2, -1, 0, 1, 2, 3)  # complete loss, one-copy loss, neutral, one-, two-copy and a higher gain
-
-
-def check_levels(levels, who=_WHO):
-    """(list of K floats with the neutral one as ``0.0``, its index z); ``ValueError`` unless ``levels`` are K finite
-    numbers, 2 <= K <= 8, strictly ascending, exactly one of them zero (``-0.0`` counts as a zero)."""
-    try:
-        out = [float(v) for v in levels]
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: levels={levels!r} must be a sequence of numbers") from None
-    if not MIN_STATES <= len(out) <= MAX_STATES:
-        raise ValueError(f"{who}: levels has {len(out)} states; the chain takes {MIN_STATES} to {MAX_STATES}")
-    if not all(math.isfinite(v) for v in out):
-        raise ValueError(f"{who}: levels={out!r} must be finite")
-    if any(b <= a for a, b in zip(out, out[1:])):
-        raise ValueError(f"{who}: levels={out!r} must ascend strictly")
-    zeros = [k for k, v in enumerate(out) if v == 0.0]
-    if len(zeros) != 1:
-        raise ValueError(f"{who}: levels={out!r} must hold exactly one 0.0, the neutral state")
-    out[zeros[0]] = 0.0
-    return out, zeros[0]
 
 
 def cnv_copy_states(adata, use_rep="cnv", key_added="cnv_copy_states", inplace=True, *, levels=None, amplitude=None,
@@ -94,27 +72,10 @@ def cnv_copy_states(adata, use_rep="cnv", key_added="cnv_copy_states", inplace=T
     ``(|x| + max(|levels[0]|, |levels[-1]|))^2 / (2 sigma^2)`` must be finite for the stored value of the largest
     magnitude.
     """
-    if levels is not None and amplitude is not None:
-        raise ValueError(f"{_WHO}: levels and amplitude are both given; amplitude only spaces the default levels")
-    mu, z = (None, None) if levels is None else check_levels(levels)
-    k = len(DEFAULT_STEPS) if mu is None else len(mu)
-
-    def other_states_share():
-        # rule 1 divides switch_prob by K - 1, resolve() tried it with 2
-        if not float(switch_prob) / (k - 1) > 0.0:
-            raise ValueError(f"{_WHO}: switch_prob={switch_prob!r} is too close to 0 or 1 for float64")
-
-    # rule 6 with given levels is resolve()'s own check under the amplitude max(|levels[0]|, |levels[-1]|)
-    mo = resolve(adata, use_rep, _WHO, max_windows=_lib.ICV_COPY_STATES_MAX_WINDOWS, keeps="a cell's windows",
-                 amplitude=amplitude if mu is None else max(abs(mu[0]), abs(mu[-1])), sigma=sigma,
-                 switch_prob=switch_prob, log_switch=True, sum_of_squares=False, then=other_states_share)
+    mo, mu, z, k = resolve_levels(adata, use_rep, _WHO, levels=levels, amplitude=amplitude, sigma=sigma,
+                                  switch_prob=switch_prob, log_switch=True,
+                                  max_windows=lambda k: _lib.ICV_COPY_STATES_MAX_WINDOWS, keeps=lambda k: "a cell's windows")
     n, w, bounds, sig, p, on_device = mo.n, mo.w, mo.bounds, mo.sig, mo.p, mo.on_device
-    if mu is None:
-        mu = [float(s) * mo.amp for s in DEFAULT_STEPS]
-        z = DEFAULT_STEPS.index(0)
-        if mo.h is not None:
-            mu, z = check_levels(mu)
-            check_emissions(_WHO, f"X_{use_rep}", mo.x, mo.m, max(abs(mu[0]), abs(mu[-1])), mo.h, sig)
     torch = _engine._torch()
     with torch.cuda.device(mo.dm.device):
         if mo.h is None:  # an all-zero matrix: nothing to call

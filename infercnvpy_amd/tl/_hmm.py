@@ -1,11 +1,12 @@
-"""The model of the three-state hidden Markov chain, resolved once for ``tl.cnv_states``, ``tl.cnv_posteriors`` and
-``tl.cnv_states_fit``.
+"""The model of the hidden Markov chains, resolved once for ``tl.cnv_states``, ``tl.cnv_posteriors`` and
+``tl.cnv_states_fit`` (three states) and for ``tl.cnv_copy_states``, ``tl.cnv_copy_posteriors`` and
+``tl.cnv_copy_states_fit`` (K states).
 
-The three functions must derive the same ``(amplitude, sigma, switch_prob)`` from the same matrix and the same
+The functions of a family must derive the same ``(amplitude, sigma, switch_prob)`` from the same matrix and the same
 arguments (DESIGN.md 4.13 rules 1 and 6), otherwise the posteriors do not belong to the calls and the fit does not start
 where the calls were made.  :func:`resolve` is that derivation; what differs between the callers is an argument of it.
-The argument checks that the functions downstream of the calls share live here too: :func:`chromosome_bounds`,
-:func:`at_least_one` and :func:`call_matrix`.
+:func:`resolve_levels` adds the ``levels`` of the K-state model.  The argument checks that the functions
+downstream of the calls share live here too: :func:`chromosome_bounds`, :func:`at_least_one` and :func:`call_matrix`.
 """
 from __future__ import annotations
 
@@ -17,6 +18,9 @@ from typing import NamedTuple
 import numpy as np
 
 from .. import _engine
+
+MIN_STATES, MAX_STATES = 2, 8  # of the K-state model
+DEFAULT_STEPS = (-2, -1, 0, 1, 2, 3)  # complete loss, one-copy loss, neutral, one-, two-copy and a higher gain
 
 
 def chromosome_bounds(chr_pos, n_windows, who="tl.cnv_states"):
@@ -157,8 +161,8 @@ class Model(NamedTuple):
 
 
 def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch_prob, log_switch, sum_of_squares,
-            zero_model=False, then=None, default_sigma=None):
-    """The common opening of the three functions: arguments checked, matrix on the device, model resolved.
+            zero_model=False, then=None, default_sigma=None, n_states=3):
+    """The common opening of the chain functions: arguments checked, matrix on the device, model resolved.
 
     who
         The caller's name; it prefixes every message.
@@ -167,9 +171,10 @@ def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch
     amplitude, sigma, switch_prob
         As the caller got them; ``switch_prob`` is not None.
     log_switch
-        True: ``switch_prob`` is too close to 0 or 1 when ``log(1 - p)`` or ``log(p / 2)`` is not finite (the Viterbi
-        chain adds logarithms).  False: when ``p / 2`` is not a normal float64 or ``1 - p`` is not in (0, 1) (the
-        forward-backward chain multiplies probabilities).
+        True: ``switch_prob`` is too close to 0 or 1 when ``log(1 - p)`` or ``log(p / 2)`` is not finite or the share
+        ``p / (n_states - 1)`` of one other state is 0 (the Viterbi chain adds logarithms).  False: when that share (at
+        most ``p / 2``) is not a normal float64 or ``1 - p`` is not in (0, 1) (the forward-backward chain multiplies
+        probabilities).
     sum_of_squares
         True: the per-row sums of squares are always read back and their sum must be finite.  False: only for the
         default ``sigma``; with ``sigma`` given the one pair (non-finite flag, largest magnitude) is all that is read.
@@ -181,6 +186,10 @@ def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch
     default_sigma
         None, or ``default_sigma(dm, bounds, rms)``: the caller's own default for a ``sigma`` of None, given the root
         mean square that is the default otherwise.
+    n_states
+        The K of the model: each of the other K - 1 states gets an equal share of ``switch_prob``.  (The K-state
+        functions used to test that share in ``then()``, which has always run right after the test here: one test in
+        its place reports the same faults in the same order.)
 
     Raises in this order: keys, shape, cap, ``chr_pos``, ``amplitude``, ``sigma``, ``switch_prob``, ``then()``, and
     only then what needs the device (non-finite values, overflows)."""
@@ -209,10 +218,11 @@ def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch
         raise ValueError(f"{who}: switch_prob={switch_prob!r} must be a number") from None
     if isinstance(switch_prob, bool) or not 0.0 < p < 1.0:
         raise ValueError(f"{who}: switch_prob={switch_prob!r} must lie in (0, 1)")
+    share = p / max(2, n_states - 1)
     if log_switch:
-        in_range = math.isfinite(math.log(1.0 - p)) and math.isfinite(math.log(p / 2.0))
+        in_range = math.isfinite(math.log(1.0 - p)) and math.isfinite(math.log(p / 2.0)) and share > 0.0
     else:
-        in_range = p / 2.0 >= sys.float_info.min and 0.0 < 1.0 - p < 1.0
+        in_range = share >= sys.float_info.min and 0.0 < 1.0 - p < 1.0
     if not in_range:
         raise ValueError(f"{who}: switch_prob={switch_prob!r} is too close to 0 or 1 for float64")
     rest = None if then is None else then()
@@ -253,3 +263,56 @@ def resolve(adata, use_rep, who, *, max_windows, keeps, amplitude, sigma, switch
                              "(1 / (2 sigma^2) must be finite and > 0)")
         check_emissions(who, key, x, m, amp, h, sig)
     return Model(x, n, w, bounds, dm, on_device, amp, sig, p, qs, m, h, t0, t1, rest)
+
+
+def check_levels(levels, who="tl.cnv_copy_states"):
+    """(list of K floats with the neutral one as ``0.0``, its index z); ``ValueError`` unless ``levels`` are K finite
+    numbers, 2 <= K <= 8, strictly ascending, exactly one of them zero (``-0.0`` counts as a zero)."""
+    try:
+        out = [float(v) for v in levels]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: levels={levels!r} must be a sequence of numbers") from None
+    if not MIN_STATES <= len(out) <= MAX_STATES:
+        raise ValueError(f"{who}: levels has {len(out)} states; the chain takes {MIN_STATES} to {MAX_STATES}")
+    if not all(math.isfinite(v) for v in out):
+        raise ValueError(f"{who}: levels={out!r} must be finite")
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"{who}: levels={out!r} must ascend strictly")
+    zeros = [k for k, v in enumerate(out) if v == 0.0]
+    if len(zeros) != 1:
+        raise ValueError(f"{who}: levels={out!r} must hold exactly one 0.0, the neutral state")
+    out[zeros[0]] = 0.0
+    return out, zeros[0]
+
+
+def resolve_levels(adata, use_rep, who, *, levels, amplitude, sigma, switch_prob, log_switch, max_windows, keeps,
+                   zero_levels=None):
+    """The common opening of ``tl.cnv_copy_states`` and ``tl.cnv_copy_posteriors``: ``(mo, mu, z, k)`` with ``mo`` the
+    :class:`Model` of :func:`resolve`, ``mu`` the K state means and ``z`` the index of the neutral one.
+
+    ``max_windows(k)`` and ``keeps(k)`` give :func:`resolve` the kernel's cap and its words for K states.
+    ``zero_levels``: the ``(mu, z)`` that ``tl.cnv_copy_states`` stored for an all-zero matrix (its levels are all 0),
+    taken as they are, with ``zero_model`` for :func:`resolve`.
+
+    Raises in this order: ``levels`` together with ``amplitude``, :func:`check_levels`, what :func:`resolve` raises, and
+    for the default levels ``[k * amplitude for k in DEFAULT_STEPS]`` their own :func:`check_levels` and
+    :func:`check_emissions`.  Rule 6 with given levels is the check of :func:`resolve` itself under the amplitude
+    ``max(|levels[0]|, |levels[-1]|)``."""
+    if levels is not None and amplitude is not None:
+        raise ValueError(f"{who}: levels and amplitude are both given; amplitude only spaces the default levels")
+    if zero_levels is not None:
+        mu, z = zero_levels
+    else:
+        mu, z = (None, None) if levels is None else check_levels(levels, who)
+    k = len(DEFAULT_STEPS) if mu is None else len(mu)
+    mo = resolve(adata, use_rep, who, max_windows=max_windows(k), keeps=keeps(k),
+                 amplitude=amplitude if mu is None else max(abs(mu[0]), abs(mu[-1])), sigma=sigma,
+                 switch_prob=switch_prob, log_switch=log_switch, sum_of_squares=False,
+                 zero_model=zero_levels is not None, n_states=k)
+    if mu is None:
+        mu = [float(s) * mo.amp for s in DEFAULT_STEPS]
+        z = DEFAULT_STEPS.index(0)
+        if mo.h is not None:
+            mu, z = check_levels(mu, who)
+            check_emissions(who, f"X_{use_rep}", mo.x, mo.m, max(abs(mu[0]), abs(mu[-1])), mo.h, mo.sig)
+    return mo, mu, z, k

@@ -137,18 +137,27 @@ def cnv_states_filter(adata, use_rep="cnv_states", posterior_key="cnv_posterior"
     are CUDA tensors (``inplace=True`` copies the two per-cell vectors back for ``adata.obs``).  A posterior that is
     not a number in [0, 1] or a call other than -1 / 0 / +1 raises ``ValueError`` (one flag read back from the device).
     """
+    return _filter_runs(adata, "tl.cnv_states_filter", _engine.states_filter, "values other than -1, 0 and +1", False,
+                        use_rep, posterior_key, cnv_key, key_added, max_p_normal, inplace, return_info)
+
+
+def _filter_runs(adata, who, engine_call, bad_calls, with_sign, use_rep, posterior_key, cnv_key, key_added, max_p_normal,
+                 inplace, return_info):
+    """The body of ``tl.cnv_states_filter`` and ``tl.cnv_copy_states_filter``.  ``engine_call``: ``_engine.states_filter``
+    or ``_engine.copy_states_filter``; ``bad_calls``: what the calls hold when the kernel refuses them, for the message;
+    ``with_sign``: there is a second plane, the filtered calls clipped to -1 / 0 / +1, stored with a copy of ``chr_pos``
+    so that ``tl.cnv_segments`` takes it as it is."""
     key, pkey = f"X_{use_rep}", f"X_{posterior_key}_neutral"
-    x, post, n, w = call_matrix(adata, "tl.cnv_states_filter", key, cnv_key, "`tl.infercnv`?", pkey)
+    x, post, n, w = call_matrix(adata, who, key, cnv_key, "`tl.infercnv`?", pkey)
     if w > _lib.ICV_FILTER_MAX_WINDOWS:
-        raise ValueError(f"tl.cnv_states_filter: {w} windows; a run's int64 sum takes at most "
-                         f"{_lib.ICV_FILTER_MAX_WINDOWS}")
+        raise ValueError(f"{who}: {w} windows; a run's int64 sum takes at most {_lib.ICV_FILTER_MAX_WINDOWS}")
     bounds = chromosome_bounds(adata.uns[cnv_key]["chr_pos"], w)
     try:
         thr = float(max_p_normal)
     except (TypeError, ValueError):
-        raise ValueError(f"tl.cnv_states_filter: max_p_normal={max_p_normal!r} must be a number in [0, 1]") from None
+        raise ValueError(f"{who}: max_p_normal={max_p_normal!r} must be a number in [0, 1]") from None
     if isinstance(max_p_normal, bool) or not 0.0 <= thr <= 1.0:
-        raise ValueError(f"tl.cnv_states_filter: max_p_normal={max_p_normal!r} must lie in [0, 1]")
+        raise ValueError(f"{who}: max_p_normal={max_p_normal!r} must lie in [0, 1]")
 
     torch = _engine._torch()
     on_device = isinstance(x, torch.Tensor) or isinstance(post, torch.Tensor)
@@ -156,20 +165,25 @@ def cnv_states_filter(adata, use_rep="cnv_states", posterior_key="cnv_posterior"
     states = _engine.dense_input(x)
     with torch.cuda.device(states.device):
         p_dev = _engine.dense_input(post).to(states.device)
-        filtered, count, removed, bad = _engine.states_filter(states, p_dev, bounds, thr)
+        *planes, count, removed, bad = engine_call(states, p_dev, bounds, thr)
         fraction = _engine.states_fraction(count, w)
         if int(bad.item()):
-            raise ValueError(f"tl.cnv_states_filter: {pkey} has values that are not numbers in [0, 1], or {key} has "
-                             "values other than -1, 0 and +1")
+            raise ValueError(f"{who}: {pkey} has values that are not numbers in [0, 1], or {key} has {bad_calls}")
         info = None
         if return_info:
             info = {"n_removed": int(removed.sum().item()), "stage_ms": {"filter": (time.perf_counter() - t0) * 1e3}}
         if not on_device:
-            filtered, fraction, removed = filtered.cpu().numpy(), fraction.cpu().numpy(), removed.cpu().numpy()
+            planes = [t.cpu().numpy() for t in planes]
+            fraction, removed = fraction.cpu().numpy(), removed.cpu().numpy()
+    result = (*planes, fraction, removed)  # (filtered, [sign,] fraction, removed)
     if inplace:
-        adata.obsm[f"X_{key_added}"] = filtered
+        adata.obsm[f"X_{key_added}"] = planes[0]
+        if with_sign:
+            adata.obsm[f"X_{key_added}_sign"] = planes[1]
         adata.obs[key_added + "_fraction"] = fraction.cpu().numpy() if on_device else fraction
         adata.obs[key_added + "_removed"] = removed.cpu().numpy() if on_device else removed
         adata.uns[key_added] = {"params": {"max_p_normal": thr, "use_rep": use_rep, "posterior_key": posterior_key}}
-        return (filtered, fraction, removed, info) if return_info else None
-    return (filtered, fraction, removed, info) if return_info else (filtered, fraction, removed)
+        if with_sign:
+            adata.uns[key_added]["chr_pos"] = dict(adata.uns[cnv_key]["chr_pos"])
+        return (*result, info) if return_info else None
+    return (*result, info) if return_info else result

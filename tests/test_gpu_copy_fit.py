@@ -144,6 +144,60 @@ def test_stay_mass_is_the_bytes_of_the_three_state_kernel(name):
         assert got[:, 6].tobytes() == fo.stats(x, c["chr_pos"], a, sigma, p)[:, 2].tobytes()
 
 
+def _sums_of_the_planes(planes, x, bounds):
+    """N_s and M_s of DESIGN.md 4.24 from the posteriors gamma (K x n x W): per chromosome from t = T - 1 down to 0, the
+    product gamma x rounded before the add, then the chromosomes in ascending order from 0.0.  Python floats: every
+    operation is one float64 operation."""
+    k, n, _ = planes.shape
+    out = np.zeros((n, 2 * k), dtype=np.float64)
+    for i in range(n):
+        for s in range(k):
+            n_acc, m_acc = 0.0, 0.0
+            for s0, s1 in zip(bounds[:-1], bounds[1:]):
+                n_chr, m_chr = 0.0, 0.0
+                for t in range(int(s1) - 1, int(s0) - 1, -1):
+                    ga = float(planes[s, i, t])
+                    n_chr += ga
+                    m_chr += ga * float(x[i, t])
+                n_acc += n_chr
+                m_acc += m_chr
+            out[i, s], out[i, k + s] = n_acc, m_acc
+    return out
+
+
+@pytest.mark.parametrize("layout", ["chromosome_of_one_window", "seventy_chromosomes"])
+@pytest.mark.parametrize("k", [2, 3, 8])
+def test_statistics_are_the_sums_of_the_planes_the_chains_kernel_writes(k, layout):
+    """icv_copy_posterior_stats and icv_copy_posterior_chains run one chain, each in its own body: N_s and M_s are the
+    sums of the planes the chains kernel writes, bit for bit.  [0, 1, 4, 9]: a chromosome of one window has no inner
+    window and no window t - 1 to read; 70 chromosomes of one or two windows: lanes take a second chromosome.  S stays
+    with the oracle tests above."""
+    from infercnvpy_amd import _engine
+
+    if layout == "chromosome_of_one_window":
+        bounds = np.array([0, 1, 4, 9], dtype=np.int32)
+    else:
+        bounds = np.concatenate([[0], np.cumsum([1 + c % 2 for c in range(70)])]).astype(np.int32)
+    n, w = 5, int(bounds[-1])
+    rng = np.random.default_rng(100 * k + w)
+    dense32 = (rng.normal(0.0, 0.3, (n, w)) * (rng.random((n, w)) < 0.6)).astype(np.float32)
+    dense32[3] = 0.0  # a row without a stored entry
+    z = k // 2
+    mu = [(s - z) * 0.3 for s in range(k)]
+    h, ps, pw = cpo.scalars(0.2, 0.01, k)
+    for name, x in (("dense_float32", dense32), ("dense_float64", dense32.astype(np.float64)),
+                    ("csr_float32", sp.csr_matrix(dense32)), ("csr_float64", sp.csr_matrix(dense32.astype(np.float64)))):
+        dm = _engine.matrix_input(x, "test")
+        _, planes = _engine.copy_posterior_chains(dm, bounds, levels=mu, neutral=z, h=h, ps=ps, pw=pw, all_states=True)
+        stats = _engine.copy_posterior_stats(dm, bounds, levels=mu, neutral=z, h=h, ps=ps, pw=pw).cpu().numpy()
+        want = _sums_of_the_planes(planes.cpu().numpy(), dense32.astype(np.float64), bounds)
+        assert np.isfinite(want).all() and stats.shape == (n, 2 * k + 1), name
+        differ = int((stats[:, :2 * k].view(np.uint64) != want.view(np.uint64)).sum())
+        print(f"{layout}, K = {k}, {name}: {differ} of {want.size} sums differ from the sums of the planes")
+        assert np.ascontiguousarray(stats[:, :2 * k]).tobytes() == want.tobytes(), name
+        assert np.array_equal(stats[3, k:2 * k], np.zeros(k)) and stats[3, :k].sum() == pytest.approx(w), name
+
+
 def test_every_kind_of_input_gives_the_same_bytes():
     import torch
 
