@@ -297,10 +297,66 @@ def cap_case(k):
     return c
 
 
+CUTOFF5_KWARGS = {"levels": (-1.0, -0.5, 0.0, 0.5, 1.0), "sigma": 0.25, "switch_prob": 1e-3}  # h = 8: exact emissions
+CUTOFF5_VALUES = (44.6875, 44.75, 44.8125)  # e_neutral - e_top = -707, -708 (ts_exp's last non-zero argument) and -709
+CUTOFF5_GAPS = (-707.0, -708.0, -709.0)
+
+
+def exp_cutoff5():
+    """``_posterior_oracle.exp_cutoff`` for five levels, the neutral one in the middle: rule 2's ``m`` is the largest of
+    five emissions.  At x = +v the top state has b = 1.0, the state below it b = exp_(1 - 8 v) (about 1e-153), the neutral
+    state b = exp_ of CUTOFF5_GAPS and the two loss states lie far beyond the cutoff (exactly 0.0): a window holds
+    several exact zeros and one smallest b that is not 0.  The layout is that of ``exp_cutoff``: rows 0-5 hold one value
+    (+ and - of each) at the CUTOFF_PROBES windows among windows on that sign's outermost level, rows 6-11 the same among
+    windows that are not stored, then extremes of both signs side by side, and noise.  Every value is a float32 number.
+    dict(x, chr_pos, kwargs, probes=[(row, window, |value|)])."""
+    import scipy.sparse as sp
+
+    mu, z = co.check_levels(CUTOFF5_KWARGS["levels"])
+    h = scalars(CUTOFF5_KWARGS["sigma"], CUTOFF5_KWARGS["switch_prob"], len(mu))[0]
+    assert h == 8.0 and z == 2
+    for v, gap in zip(CUTOFF5_VALUES, CUTOFF5_GAPS):
+        for sign in (1.0, -1.0):
+            e = co.emissions(sign * v, mu, h)
+            top = e[-1] if sign > 0 else e[0]
+            assert top == max(e) and e[z] - top == gap and all(fractions.Fraction(-w / h).denominator <= 256 for w in e)
+    top = mu[-1]
+    w = sum(po.CUTOFF_LENGTHS)
+    lo, mid, hi = CUTOFF5_VALUES
+    rows, probes = [], []
+    for background in (top, 0.0):
+        for v in CUTOFF5_VALUES:
+            for sign in (1.0, -1.0):
+                row = np.full(w, sign * background)
+                row[list(po.CUTOFF_PROBES)] = sign * v
+                if background:
+                    probes.extend((len(rows), t, v) for t in po.CUTOFF_PROBES)
+                rows.append(row)
+    row = np.zeros(w)
+    row[0:6] = [hi, -hi, mid, -mid, lo, -lo]  # the chain meets states it gave probability 0
+    row[10:14] = [mid, mid, hi, hi]
+    row[18:23] = [-lo, 0.5, -mid, -0.5, -hi]
+    rows.append(row)
+    rng = np.random.default_rng(43)
+    for v in CUTOFF5_VALUES:
+        row = rng.normal(0.0, 0.5, size=w).astype(np.float32).astype(np.float64)
+        row[rng.random(w) < 0.4] = 0.0
+        row[rng.integers(0, w, size=3)] = [v, -v, v]
+        rows.append(row)
+    dense = np.vstack(rows)
+    assert np.array_equal(dense, dense.astype(np.float32).astype(np.float64))
+    return {"x": sp.csr_matrix(dense), "chr_pos": so.chr_pos_of(po.CUTOFF_LENGTHS), "kwargs": dict(CUTOFF5_KWARGS),
+            "probes": probes}
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
     """The named case with its expected output, computed once: dict(x, chr_pos, kwargs, planes, params)."""
-    if name.startswith("every_k_"):
+    if name == "exp_cutoff5":
+        c = exp_cutoff5()
+    elif name == "unequal_levels":
+        c = co.unequal_levels()
+    elif name.startswith("every_k_"):
         k, z, p = name[len("every_k_"):].split("_")
         c = co.every_k(int(k), int(z), float(p))
     elif name.startswith("planted_levels_"):

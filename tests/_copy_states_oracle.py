@@ -17,7 +17,8 @@ windows and the K states:
 6. Overflow: with ``m`` the largest ``|v|`` over the stored values and ``t = m + max(|levels[0]|, |levels[K-1]|)``, a
    ``(t t) h`` that is not finite is a ``ValueError``.
 
-Rule 3 is the K^2 form here, whatever the kernel does.  ``bounds=`` takes the kernel's own ``chr_start`` array in place
+Rule 3 is the K^2 form here, whatever the kernel does; ``viterbi_chain_two_best`` restates the kernel's O(K) form and
+its named mistakes, to show on the CPU which cases tell them from the contract.  ``bounds=`` takes the kernel's own ``chr_start`` array in place
 of ``chr_pos``, as in ``_states_oracle``.
 """
 import fractions
@@ -170,6 +171,61 @@ def viterbi_chain(xs, mu, z, h, stay, sw, variant=None):
     return path
 
 
+TWO_BEST_BUGS = ("no_demotion", "no_second", "first_for_all")
+
+
+def viterbi_chain_two_best(xs, mu, z, h, stay, sw, bug=None):
+    """rules 3-4 with rule 3 in the kernel's O(K) form (csrc/icv_copy_states.hpp): every state shares the candidates
+    ``w_r = d(r) + sw``; ``a1`` / ``m1`` are the first r with the largest w_r and that value, ``a2`` / ``m2`` the same among
+    the r != a1, both kept in one pass over ascending r in which only a strictly larger value replaces.  State s compares
+    ``d(s) + stay`` with ``m1``, state a1 with ``m2``; a window's back-pointers are the set of states that stayed, a1 and
+    a2.  Without ``bug`` the list of states is that of ``viterbi_chain``.
+
+    ``bug`` plants one mistake in the bookkeeping of the second best (never the contract): ``"no_demotion"`` leaves
+    m2 / a2 as they are when a new best is found, ``"no_second"`` never lets a later r become the second best,
+    ``"first_for_all"`` compares state a1 with m1 like every other state (the backtrack still takes a2 for it).  None of them can show while
+    ``stay >= sw``, that is ``switch_prob <= (K - 1) / K``: ``m2 <= m1 = d(a1) + sw <= d(a1) + stay``, so state a1 stays
+    whatever m2 and a2 hold."""
+    assert bug is None or bug in TWO_BEST_BUGS
+    k = len(mu)
+    d = emissions(xs[0], mu, h)
+    back = []
+    for x in xs[1:]:
+        e = emissions(x, mu, h)
+        m1, m2, a1, a2 = d[0] + sw, d[1] + sw, 0, 1
+        if m2 > m1:
+            m1, m2, a1, a2 = m2, m1, 1, 0
+        for r in range(2, k):
+            w = d[r] + sw
+            if w > m1:
+                if bug != "no_demotion":
+                    m2, a2 = m1, a1
+                m1, a1 = w, r
+            elif w > m2 and bug != "no_second":
+                m2, a2 = w, r
+        nd, stayed = [], []
+        for s in range(k):
+            keep = d[s] + stay
+            other = m2 if a1 == s and bug != "first_for_all" else m1
+            left = other > keep
+            nd.append((other if left else keep) + e[s])
+            stayed.append(not left)
+        d = nd
+        back.append((stayed, a1, a2))
+    order = end_order(k, z)
+    s = order[0]
+    for c in order[1:]:
+        if d[c] > d[s]:
+            s = c
+    path = [s]
+    for stayed, a1, a2 in reversed(back):
+        if not stayed[s]:
+            s = a2 if s == a1 else a1
+        path.append(s)
+    path.reverse()
+    return path
+
+
 def path_score(xs, path, mu, h, stay, sw):
     """The log-score of one path, summed in the order of rule 3: ((previous + T) + e)."""
     sc = emissions(xs[0], mu, h)[path[0]]
@@ -279,6 +335,81 @@ def every_k(k, z, switch_prob):
             "kwargs": dict(EVERY_K_KWARGS, levels=every_k_levels(k, z), switch_prob=switch_prob)}
 
 
+HIGH_SWITCH = 0.999  # above (K - 1) / K for every K <= 8: sw > stay, and the best other state can beat staying in a1
+
+
+def high_switch_positions(k):
+    """The neutral positions of the HIGH_SWITCH cases: the first, the middle and the last state."""
+    return sorted({0, k // 2, k - 1})
+
+
+def chains_of(c):
+    """[(row, first window, the chromosome's values as a list)] of a case: every chain the kernel runs."""
+    dense = c["x"].toarray()
+    edges = so.bounds(c["chr_pos"], dense.shape[1])
+    return [(i, s0, dense[i, s0:s1].tolist()) for i in range(dense.shape[0]) for s0, s1 in zip(edges[:-1], edges[1:])]
+
+
+def contract_chains(c):
+    """[(the chromosome's values, the states ``viterbi_chain`` gives them)] over ``chains_of(c)``."""
+    kw = c["kwargs"]
+    mu, z = check_levels(kw["levels"])
+    h, stay, sw = scalars(kw["sigma"], kw["switch_prob"], len(mu))
+    return [(xs, viterbi_chain(xs, mu, z, h, stay, sw)) for _, _, xs in chains_of(c)]
+
+
+def two_best_differences(c, bug=None, contract=None):
+    """The number of the case's chains on which ``viterbi_chain_two_best(bug=)`` does not give the states of
+    ``viterbi_chain``; ``contract`` takes a ``contract_chains(c)`` computed before."""
+    kw = c["kwargs"]
+    mu, z = check_levels(kw["levels"])
+    h, stay, sw = scalars(kw["sigma"], kw["switch_prob"], len(mu))
+    contract = contract_chains(c) if contract is None else contract
+    return sum(viterbi_chain_two_best(xs, mu, z, h, stay, sw, bug) != want for xs, want in contract)
+
+
+END_RULE_STATES = 8
+
+
+def end_rule(z):
+    """Rule 4 by hand, K = 8 with the neutral state at z: one row of seven one-window chromosomes, window s holding the
+    value half-way between the levels s and s + 1 of ``every_k_levels(8, z)``.  With sigma = 0.25 (h = 8) the two
+    emissions are exactly -0.5 and every other one is lower, so rule 4's order alone decides: the state nearer to z is
+    tried first and a tie does not replace it, and z wins against both its neighbours.  ``want`` is written down from
+    that, without the oracle.  dict(x, chr_pos, kwargs, want=int8 1 x 7)."""
+    k = END_RULE_STATES
+    mu = every_k_levels(k, z)
+    x = np.array([[mu[s] + 0.25 for s in range(k - 1)]])
+    want = np.array([[(s + 1 if s + 1 <= z else s) - z for s in range(k - 1)]], dtype=np.int8)
+    return {"x": so.canonical(x), "chr_pos": so.chr_pos_of([1] * (k - 1)),
+            "kwargs": dict(EVERY_K_KWARGS, levels=mu, switch_prob=1e-3), "want": want}
+
+
+UNEQUAL_KWARGS = {"levels": (-0.7, -0.15, 0.0, 0.4, 0.45, 1.3, 2.0), "sigma": 0.17, "switch_prob": 0.01}
+UNEQUAL_LENGTHS = (37, 1, 64, 29)  # W = 131: no multiple of 4 or 64
+
+
+def unequal_levels():
+    """Seven levels that are no multiples of one step, two of them 0.05 apart, under a sigma with nothing dyadic: every
+    operation of rules 2-3 rounds, and no symmetry of the lattice hides a state taken for its neighbour.  14 rows of
+    N(0, 0.17) plus one level per stretch of 4 .. 12 windows, drawn from all seven; a third of the values is not stored.
+    dict(x, chr_pos, kwargs)."""
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(77)
+    w = sum(UNEQUAL_LENGTHS)
+    mu = np.asarray(UNEQUAL_KWARGS["levels"])
+    dense = rng.normal(0.0, UNEQUAL_KWARGS["sigma"], size=(14, w))
+    for i in range(dense.shape[0]):
+        t = 0
+        while t < w:
+            n = int(rng.integers(4, 13))
+            dense[i, t:t + n] += mu[rng.integers(0, len(mu))]
+            t += n
+    dense[rng.random(dense.shape) < 1.0 / 3.0] = 0.0
+    return {"x": sp.csr_matrix(dense), "chr_pos": so.chr_pos_of(UNEQUAL_LENGTHS), "kwargs": dict(UNEQUAL_KWARGS)}
+
+
 ROUNDING_LENGTHS = (2, 3, 6)
 ROUNDING_CHAINS = 400  # per length
 ROUNDING_ROWS = 4
@@ -381,6 +512,10 @@ def case(name):
     elif name.startswith("every_k_"):
         k, z, p = name[len("every_k_"):].split("_")
         c = every_k(int(k), int(z), float(p))
+    elif name.startswith("end_rule_"):
+        c = end_rule(int(name[len("end_rule_"):]))
+    elif name == "unequal_levels":
+        c = unequal_levels()
     else:
         c = shapes()[name]
         c["kwargs"] = dict(SHAPE_KWARGS)

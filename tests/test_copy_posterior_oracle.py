@@ -112,6 +112,38 @@ def test_uncovered_windows_zero_matrix_and_default_levels():
         cpo.cnv_copy_posteriors(x, pos, levels=(-0.2, 0.0, 0.2, 0.4), sigma=okw["sigma"])
 
 
+def test_five_level_cutoff_case_sits_on_the_cutoff_of_the_written_exponential():
+    """What the K = 5 case adds to the three-level ``exp_cutoff``: in one window two states lie beyond the cutoff (b
+    exactly 0.0), one lies on or next to it and one is about 1e-153."""
+    from _tsne_oracle import exp_
+
+    assert float(exp_(np.float64(-708.0))) > 0.0 and float(exp_(np.nextafter(np.float64(-708.0), -np.inf))) == 0.0
+    c = cpo.case("exp_cutoff5")
+    mu, z = co.check_levels(c["kwargs"]["levels"])
+    h = cpo.scalars(c["kwargs"]["sigma"], c["kwargs"]["switch_prob"], 5)[0]
+    assert h == 8.0 and z == 2 and c["planes"].shape == (5,) + c["x"].shape
+    for v, gap in zip(cpo.CUTOFF5_VALUES, cpo.CUTOFF5_GAPS):
+        assert np.float32(v) == v
+        for sign in (1.0, -1.0):
+            e = co.emissions(sign * v, mu, h)
+            assert e[z] - max(e) == gap and max(e) == (e[4] if sign > 0 else e[0])
+            b = [float(u[0]) for u in cpo.emissions(np.array([sign * v]), mu, h)]
+            b = b if sign > 0 else b[::-1]
+            assert b[0] == b[1] == 0.0 and (b[2] > 0.0) == (gap >= -708.0) and 0.0 < b[3] < 1e-150 and b[4] == 1.0
+    planes = c["planes"]
+    assert np.isfinite(planes).all() and (planes >= 0.0).all() and (planes <= 1.0).all()
+    zeros = [int(((p == 0.0).any(axis=1) & (p != 0.0).any(axis=1)).sum()) for p in planes]
+    print(f"rows of each plane with an exact 0.0 next to a non-zero posterior: {zeros}")
+    assert all(n >= 1 for n in zeros)
+    seen = {v: [] for v in cpo.CUTOFF5_VALUES}
+    for row, t, v in c["probes"]:
+        seen[v].append(float(planes[z, row, t]))
+    print({v: (min(p), max(p)) for v, p in seen.items()})
+    assert all(len(p) == 2 * len(po.CUTOFF_PROBES) for p in seen.values())
+    assert all(0.0 < p < 1e-300 for p in seen[44.6875]) and all(0.0 < p < 1e-300 for p in seen[44.75])
+    assert all(p == 0.0 for p in seen[44.8125])  # the -708 and the -709 probes differ in the neutral plane
+
+
 # ---- the chain on the planted case -------------------------------------------------------------------------------------------
 def test_chain_constants_on_the_planted_case():
     c = cpo.chain_case()

@@ -2,6 +2,7 @@
 exhaustive enumeration and on the planted multi-level case; the header, the library and the argument validation of the
 C ABI and of the public function -- none of it needs a GPU."""
 import ctypes
+import functools
 import itertools
 import os
 import re
@@ -109,6 +110,110 @@ def test_every_k_cases_reach_every_level():
         c = co.case(f"every_k_{k}_{z}_{p}")
         assert set(np.unique(c["states"])) == set(range(-z, k - z)), (k, z, p)
         assert not c["states"][-1].any() and np.diff(c["x"].indptr)[-1] == 0
+
+
+# ---- rule 3 in the kernel's O(K) form, and what tells a wrong second best from the contract ---------------------------------------
+ALL_K = range(co.MIN_STATES, co.MAX_STATES + 1)
+SWITCHES = co.EVERY_K_SWITCH + (co.HIGH_SWITCH,)
+TWO_BEST_FLOOR = 5  # chains of a HIGH_SWITCH case that every planted bug changes, at least
+
+
+@functools.lru_cache(maxsize=None)
+def _two_best_case(k, z, p):
+    """(every_k(k, z, p), its chains under the contract), computed once for the tests below."""
+    c = co.every_k(k, z, p)
+    return c, co.contract_chains(c)
+
+
+def _high_switch_cases(p):
+    return [(k, z) + _two_best_case(k, z, p) for k in ALL_K for z in co.high_switch_positions(k)]
+
+
+@pytest.mark.parametrize("p", SWITCHES)
+def test_two_best_form_of_rule_3_gives_the_chains_of_the_contract(p):
+    assert co.HIGH_SWITCH > (co.MAX_STATES - 1) / co.MAX_STATES > max(co.EVERY_K_SWITCH)
+    for k, z, c, contract in _high_switch_cases(p):
+        h, stay, sw = co.scalars(c["kwargs"]["sigma"], p, k)
+        assert (sw > stay) == (p == co.HIGH_SWITCH), (k, p)
+        assert len(contract) == len(co.chains_of(c)) >= 180 and co.two_best_differences(c, None, contract) == 0, (k, z, p)
+
+
+@pytest.mark.parametrize("bug", co.TWO_BEST_BUGS)
+def test_a_wrong_second_best_is_invisible_while_staying_costs_less_than_leaving(bug):
+    """Why the cases at switch_prob 1e-3 and 0.3 cannot see a2 / m2: with stay >= sw state a1 never leaves, and no chain
+    of any of them changes under any of the three bugs."""
+    for p in co.EVERY_K_SWITCH:
+        for k, z, c, contract in _high_switch_cases(p):
+            assert co.two_best_differences(c, bug, contract) == 0, (bug, k, z, p)
+
+
+@pytest.mark.parametrize("bug", co.TWO_BEST_BUGS)
+def test_a_wrong_second_best_changes_chains_at_the_high_switch_probability(bug):
+    """Chains (of 186 - 222 per case) whose calls a bug changes at switch_prob = 0.999, measured with this restatement, the
+    smallest over K and z in {0, K // 2, K - 1}: no_demotion 8 (K = 3, z = 1 and K = 8, z = 0), no_second 10 (K = 7,
+    z = 6), first_for_all 42 (K = 2, z = 0).  At K = 2 the loop over r >= 2 is empty: only first_for_all exists there."""
+    counts = {}
+    for k, z, c, contract in _high_switch_cases(co.HIGH_SWITCH):
+        if k == 2 and bug != "first_for_all":
+            assert co.two_best_differences(c, bug, contract) == 0
+            continue
+        counts[(k, z)] = co.two_best_differences(c, bug, contract)
+    print(f"{bug}: chains changed per (K, z): {counts}")
+    assert len(counts) == (20 if bug == "first_for_all" else 18)
+    assert min(counts.values()) >= TWO_BEST_FLOOR, counts
+
+
+def test_high_switch_cases_are_the_matrices_of_0_3_with_other_calls():
+    for k in ALL_K:
+        for z in co.high_switch_positions(k):
+            high, low = co.case(f"every_k_{k}_{z}_{co.HIGH_SWITCH}"), co.case(f"every_k_{k}_{z}_0.3")
+            assert (high["x"] != low["x"]).nnz == 0 and high["params"]["switch_prob"] == co.HIGH_SWITCH
+            assert int((high["states"] != low["states"]).sum()) >= 100, (k, z)
+
+
+def test_three_level_ties_at_switch_0_9_see_a_wrong_second_best():
+    """The three-state case of tests/test_gpu_copy_states.py above (K - 1) / K = 2 / 3.  Chains of 270 that change,
+    measured: no_demotion 5, no_second 30, first_for_all 71."""
+    c = so.ties()
+    a, sigma, p = c["kwargs"]["amplitude"], c["kwargs"]["sigma"], 0.9
+    h, stay, sw = co.scalars(sigma, p, 3)
+    assert sw > stay and co.scalars(sigma, 0.3, 3)[2] < co.scalars(sigma, 0.3, 3)[1]
+    three, fraction, _ = so.cnv_states(c["x"], c["chr_pos"], amplitude=a, sigma=sigma, switch_prob=p)
+    states, sign, copy_fraction, _ = co.cnv_copy_states(c["x"], c["chr_pos"], levels=(-a, 0.0, a), sigma=sigma, switch_prob=p)
+    assert states.tobytes() == three.tobytes() == sign.tobytes() and copy_fraction.tobytes() == fraction.tobytes()
+    c["kwargs"] = {"levels": (-a, 0.0, a), "sigma": sigma, "switch_prob": p}
+    counts = {bug: co.two_best_differences(c, bug) for bug in (None,) + co.TWO_BEST_BUGS}
+    print(f"ties at switch_prob = 0.9: chains of {len(co.chains_of(c))} changed: {counts}")
+    assert counts.pop(None) == 0 and min(counts.values()) >= TWO_BEST_FLOOR
+
+
+# ---- rule 4 by hand, and levels off every lattice ------------------------------------------------------------------------------
+@pytest.mark.parametrize("z", range(co.END_RULE_STATES))
+def test_end_rule_hand_table_is_what_the_oracle_calls(z):
+    c = co.case(f"end_rule_{z}")
+    mu, zz = co.check_levels(c["kwargs"]["levels"])
+    h = co.scalars(c["kwargs"]["sigma"], c["kwargs"]["switch_prob"], len(mu))[0]
+    assert zz == z and h == 8.0 and c["x"].shape == (1, 7) and len(c["chr_pos"]) == 7
+    for s, x in enumerate(c["x"].toarray()[0].tolist()):
+        e = co.emissions(x, mu, h)
+        assert e[s] == e[s + 1] == -0.5 and sorted(e)[-3] < -0.5  # the two nearest states tie exactly
+    want = c["want"][0].tolist()
+    assert want == [s + 1 - z for s in range(z)] + [s - z for s in range(z, 7)]  # below z the upper state, above the lower
+    assert want.count(0) == (1 if z in (0, 7) else 2)  # z wins against both neighbours
+    assert c["states"].tobytes() == c["want"].tobytes() and c["sign"].tobytes() == np.sign(c["want"]).tobytes()
+    assert c["fraction"].tolist() == [(7 - want.count(0)) / 7.0]
+
+
+def test_unequal_levels_case_calls_at_least_five_levels():
+    c = co.case("unequal_levels")
+    mu = c["kwargs"]["levels"]
+    steps = np.diff(mu)
+    assert len(mu) == 7 and len({round(float(v), 9) for v in steps}) == len(steps)  # no two steps alike
+    w = c["x"].shape[1]
+    assert c["x"].shape[0] == 14 and w % 4 and w % 64 and 0.5 < c["x"].nnz / (14 * w) < 0.8
+    called, counts = np.unique(c["states"], return_counts=True)
+    print(f"unequal_levels: calls {dict(zip(called.tolist(), counts.tolist()))}")
+    assert len(called) >= 5 and counts.min() >= 20 and (c["states"] != c["sign"]).any()
 
 
 def test_default_levels_zero_matrix_and_bounds():

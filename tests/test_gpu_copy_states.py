@@ -41,14 +41,27 @@ def _check_case(name):
     return c
 
 
-THREE_STATE_CASES = ["ties", "rounding_ties", "planted777", "full_and_empty"] + [f"output_split_{w}" for w in so.SPLIT_WIDTHS]
+TIES_HIGH_SWITCH = "ties_switch_0.9"  # above (K - 1) / K = 2 / 3: leaving costs less than staying, a2 / m2 decide
+THREE_STATE_CASES = (["ties", "rounding_ties", "planted777", "full_and_empty"]
+                     + [f"output_split_{w}" for w in so.SPLIT_WIDTHS] + [TIES_HIGH_SWITCH])
+
+
+def _three_state_case(name):
+    """``_states_oracle.case(name)``; TIES_HIGH_SWITCH is its ``ties`` matrix called at switch_prob = 0.9."""
+    if name != TIES_HIGH_SWITCH:
+        return so.case(name)
+    c = so.ties()
+    c["kwargs"]["switch_prob"] = 0.9
+    c["states"], c["fraction"], c["params"] = so.cnv_states(c["x"], c["chr_pos"], **c["kwargs"])
+    assert c["params"]["switch_prob"] == 0.9 and (c["states"] != so.case("ties")["states"]).mean() > 0.25
+    return c
 
 
 @pytest.mark.parametrize("name", THREE_STATE_CASES)
 def test_three_levels_give_the_bytes_of_cnv_states(name):
     import infercnvpy_amd as cnv
 
-    c = so.case(name)
+    c = _three_state_case(name)
     a, sigma, p = c["params"]["amplitude"], c["params"]["sigma"], c["params"]["switch_prob"]
     three, three_fraction = cnv.tl.cnv_states(_adata(c["x"], c["chr_pos"]), inplace=False, amplitude=a, sigma=sigma,
                                               switch_prob=p)
