@@ -121,9 +121,15 @@ enum {
     ICV_KERNEL_WS_CSR = 3,  /* k_csr_prepare + k_smooth_ws: CSR float32, row rebuilt in LDS               */
     ICV_KERNEL_X16 = 4,     /* k_smooth_x16: dense float32, window 100 or 250 / step 10                   */
     ICV_KERNEL_SD = 5,      /* k_smooth_sd: CSR float32, block form, stored entries only (prefix sums)    */
-    ICV_KERNEL_SPLIT = 6    /* chromosome groups (row larger than LDS) + median on float64 windows in HBM */
+    ICV_KERNEL_SPLIT = 6,   /* chromosome groups (row larger than LDS) + median on float64 windows in HBM */
+    ICV_KERNEL_X16_FINITE = 7 /* k_smooth_x16<FINITE>: the same kernel without NaN handling (icv_infercnv_run_finite) */
 };
+/* A call that passed `finite_words` launched k_smooth_x16 in both forms and the device chose between them:
+ * icv_plan_last_kernel then reads the form that applied back from the device (it waits for that call) and reports
+ * ICV_KERNEL_X16_FINITE or ICV_KERNEL_X16.  icv_plan_last_route never waits: the route the host picked, ICV_KERNEL_X16
+ * for either form. */
 int icv_plan_last_kernel(icv_plan_t plan, int32_t *h_kind);
+int icv_plan_last_route(icv_plan_t plan, int32_t *h_kind);
 /* How many cells the last smoothing launch on this plan handed back to k_smooth (more than 64 windows in the bins of
  * the two middle ranks; k_smooth_se: also cells with a stored NaN): the device-side counter of that launch, copied to
  * the host.  0 where the last launch was of a kernel that hands nothing back (ICV_KERNEL_GENERIC, _SPLIT) or nothing
@@ -183,6 +189,14 @@ int icv_colchain(const icv_matrix *m, const int32_t *rows, int64_t n_sel, double
 int icv_colsum_pairwise(const void *xt, int32_t dtype, int64_t n_rows, int32_t n_cols, int64_t ld, void *sums,
                         void *stream);
 int icv_colchain_mean(const void *acc, int32_t dtype, int32_t n_cols, int64_t count, void *mean, void *stream);
+/* icv_colchain_mean that also says whether every mean it wrote is finite: `finite_words` (device, ICV_FINITE_WORDS
+ * uint32, 16-byte aligned, no need to clear them) receives one word per workgroup, non-zero where a mean is NaN or
+ * infinite.  A chain that met a NaN stays NaN, one that met an infinity stays infinite or turns NaN: where `acc` holds
+ * the chains over ALL rows of a matrix, all-zero words certify that every element of that matrix is finite
+ * (icv_infercnv_run_finite). */
+#define ICV_FINITE_WORDS 16
+int icv_colchain_mean_finite(const void *acc, int32_t dtype, int32_t n_cols, int64_t count, void *mean,
+                             uint32_t *finite_words, void *stream);
 int icv_colmean_csc(const void *values, int32_t dtype, const int64_t *colptr, const int32_t *row_idx, int32_t n_cols,
                     const int32_t *row_group, int32_t group, double scale, void *mean, void *stream);
 
@@ -288,6 +302,18 @@ int icv_infercnv_run_windows(icv_plan_t plan, const icv_matrix *m, const void *r
                              double lfc_clip, double dynamic_threshold, int64_t chunksize, int64_t row_phase,
                              int32_t flags, float *out, int64_t ldo, double *cell_median, double *cell_stats,
                              double *thr, icv_profile *h_profile, double *win_out, int64_t ldw, void *stream);
+/* icv_infercnv_run_windows for a caller that formed `ref_lo` with icv_colchain_mean_finite over ALL rows `m` holds
+ * (or is a part of): `finite_words` are that call's words (NULL: icv_infercnv_run_windows).  Where the input takes
+ * k_smooth_x16, the kernel is launched twice back to back -- without its per-gene NaN handling, and as it is -- and
+ * each launch reads the words first: all zero, the first one runs and the second returns at once, else the other way
+ * round.  No host synchronisation; results are those of icv_infercnv_run_windows bit for bit.  Every other route
+ * ignores the words.  Words from means over a SUBSET of the rows, or a profile from elsewhere, prove nothing: pass
+ * NULL. */
+int icv_infercnv_run_finite(icv_plan_t plan, const icv_matrix *m, const void *ref_lo, const void *ref_hi,
+                            double lfc_clip, double dynamic_threshold, int64_t chunksize, int64_t row_phase,
+                            int32_t flags, float *out, int64_t ldo, double *cell_median, double *cell_stats,
+                            double *thr, icv_profile *h_profile, double *win_out, int64_t ldw,
+                            const uint32_t *finite_words, void *stream);
 int icv_gene_values_from_windows(icv_plan_t plan, const double *win, int64_t ldw, int64_t n_rows,
                                  const double *thr, int64_t chunksize, int64_t row_phase, double *gene_out,
                                  int64_t ldg, void *stream);

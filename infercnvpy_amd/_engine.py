@@ -264,17 +264,23 @@ class ChainBlocks:
         return (-(-int(self.m.n_rows) // 64)) * int(self.m.n_cols)
 
 
-def chain_mean(acc, count, is_csr):
+def chain_mean(acc, count, is_csr, finite_words=False):
     """Means from the accumulators of :func:`column_chain`: ``acc / count`` in the matrix dtype for dense input
-    (numpy's ``true_divide(sum, n)``); CSR accumulators already are the means (scipy scales the entries)."""
+    (numpy's ``true_divide(sum, n)``); CSR accumulators already are the means (scipy scales the entries).
+
+    ``finite_words=True`` (dense only) returns ``(means, words)``: the same kernel also reports, in
+    ``_lib.ICV_FINITE_WORDS`` device words, whether every mean it wrote is finite (all zero) -- what
+    :func:`run_hot_path` takes as ``finite_words`` where ``acc`` chained ALL rows of the matrix."""
     if is_csr:
+        assert not finite_words
         return acc
     torch = _torch()
     lib = _lib.load()
     out = torch.empty_like(acc)
-    _lib.check(lib.icv_colchain_mean(_ptr(acc), _lib.ICV_F32 if acc.dtype == torch.float32 else _lib.ICV_F64,
-                                     acc.numel(), int(count), _ptr(out), _stream_ptr(torch)))
-    return out
+    words = torch.empty(_lib.ICV_FINITE_WORDS, dtype=torch.int32, device="cuda") if finite_words else None
+    _lib.check(lib.icv_colchain_mean_finite(_ptr(acc), _lib.ICV_F32 if acc.dtype == torch.float32 else _lib.ICV_F64,
+                                            acc.numel(), int(count), _ptr(out), _ptr(words), _stream_ptr(torch)))
+    return (out, words) if finite_words else out
 
 
 def csc_column_means(X, row_group=None, n_groups=1, counts=None, np_dtype=None, max_entries=1 << 28):
@@ -1135,8 +1141,13 @@ class CsrDrain:
 
 def run_hot_path(plan: GenePlan, dm: DeviceMatrix, ref_lo, ref_hi=None, *, lfc_clip=3.0, dynamic_threshold=1.5,
                  chunksize=5000, row_phase=0, flags=0, out=None, profile=False, row0=0, row1=None,
-                 cell_stats=False, apply=True, windows=False):
+                 cell_stats=False, apply=True, windows=False, finite_words=None):
     """Steps 1-5 of the chunk kernel for rows [row0, row1) of ``dm`` (all device-resident).
+
+    ``finite_words``: the words :func:`chain_mean` wrote when it formed ``ref_lo`` from the chains over ALL rows of
+    ``dm`` (or of all shards ``dm`` is one of) -- never for a profile from elsewhere or means over a subset of the rows.
+    All zero, they certify a finite matrix, and k_smooth_x16 runs without its per-gene NaN handling: the library launches
+    both forms and the device picks one (no synchronisation, the same bits).
 
     ``cell_stats=True`` also returns the per-cell moments (sum, sum of squares of x_res); without them the
     library forms the noise-threshold moments per chunk inside the smoothing kernel (faster).
@@ -1170,11 +1181,14 @@ def run_hot_path(plan: GenePlan, dm: DeviceMatrix, ref_lo, ref_hi=None, *, lfc_c
     m = dm.c_struct(row0, row1)
     prof = _lib.Profile() if profile else None
     win = torch.empty((rows, W), dtype=torch.float64, device="cuda") if windows else None
-    _lib.check(lib.icv_infercnv_run_windows(
+    if finite_words is not None:
+        assert finite_words.is_cuda and finite_words.dtype == torch.int32 and finite_words.is_contiguous()
+        assert finite_words.numel() == _lib.ICV_FINITE_WORDS and ref_hi is None
+    _lib.check(lib.icv_infercnv_run_finite(
         plan.handle, C.byref(m), _ptr(ref_lo), _ptr(ref_hi), float(lfc_clip), dyn, int(chunksize), int(row_phase),
         int(flags) | (0 if apply else _lib.ICV_FLAG_NO_APPLY), _ptr(out), out.stride(0), _ptr(med), _ptr(stats),
         _ptr(thr),
-        C.byref(prof) if prof is not None else None, _ptr(win), W, _stream_ptr(torch)))
+        C.byref(prof) if prof is not None else None, _ptr(win), W, _ptr(finite_words), _stream_ptr(torch)))
     res = SmoothResult(out, med, stats, thr, prof)
     res.windows = win
     return res

@@ -48,14 +48,15 @@ def ICV_COPY_POSTERIOR_STATS_MAX_WINDOWS(k, n_chr):
 
 
 (ICV_KERNEL_NONE, ICV_KERNEL_GENERIC, ICV_KERNEL_WS, ICV_KERNEL_WS_CSR, ICV_KERNEL_X16, ICV_KERNEL_SD,
- ICV_KERNEL_SPLIT) = range(7)
+ ICV_KERNEL_SPLIT, ICV_KERNEL_X16_FINITE) = range(8)
+ICV_FINITE_WORDS = 16  # uint32 words of icv_colchain_mean_finite
 
 # every symbol include/infercnv_hip.h declares
 EXPORTS = (
     "icv_plan_create", "icv_plan_destroy", "icv_plan_get_info", "icv_plan_chr_pos", "icv_plan_window_table",
-    "icv_plan_last_kernel", "icv_plan_last_handed_back", "icv_plan_se_tables", "icv_plan_gene_runs",
-    "icv_colsum", "icv_colchain", "icv_colsum_pairwise", "icv_colchain_mean", "icv_colmean_csc", "icv_infercnv_smooth", "icv_chunk_thresholds", "icv_apply_threshold", "icv_infercnv_run",
-    "icv_infercnv_run_windows", "icv_gene_values_from_windows",
+    "icv_plan_last_kernel", "icv_plan_last_route", "icv_plan_last_handed_back", "icv_plan_se_tables", "icv_plan_gene_runs",
+    "icv_colsum", "icv_colchain", "icv_colsum_pairwise", "icv_colchain_mean", "icv_colchain_mean_finite", "icv_colmean_csc", "icv_infercnv_smooth", "icv_chunk_thresholds", "icv_apply_threshold", "icv_infercnv_run",
+    "icv_infercnv_run_windows", "icv_infercnv_run_finite", "icv_gene_values_from_windows",
     "icv_colchain_blocks_workspace", "icv_colchain_blocks_sums", "icv_colchain_blocks_records", "icv_colchain_blocks_scan",
     "icv_profile_begin", "icv_profile_collect",
     "icv_gene_values", "icv_threshold_mask", "icv_csr_fill_masked", "icv_row_offsets", "icv_pack_geometry", "icv_corr_iqr",
@@ -142,6 +143,7 @@ def load():
     lib.icv_plan_chr_pos.argtypes = [vp, vp]
     lib.icv_plan_window_table.argtypes = [vp, vp, vp]
     lib.icv_plan_last_kernel.argtypes = [vp, P(i32)]
+    lib.icv_plan_last_route.argtypes = [vp, P(i32)]
     lib.icv_plan_last_handed_back.argtypes = [vp, P(i64)]
     lib.icv_plan_se_tables.argtypes = [vp, P(i32), vp, vp, vp, vp, vp]
     lib.icv_plan_gene_runs.argtypes = [vp, P(i32), vp, vp, vp, vp]
@@ -149,6 +151,7 @@ def load():
     lib.icv_colchain.argtypes = [P(Matrix), vp, i64, dbl, vp, vp]
     lib.icv_colsum_pairwise.argtypes = [vp, i32, i64, i32, i64, vp, vp]
     lib.icv_colchain_mean.argtypes = [vp, i32, i32, i64, vp, vp]
+    lib.icv_colchain_mean_finite.argtypes = [vp, i32, i32, i64, vp, vp, vp]
     lib.icv_colmean_csc.argtypes = [vp, i32, vp, vp, i32, vp, i32, dbl, vp, vp]
     lib.icv_infercnv_smooth.argtypes = [vp, P(Matrix), vp, vp, dbl, i32, vp, i64, vp, vp, vp]
     lib.icv_chunk_thresholds.argtypes = [vp, i64, i64, i64, i32, dbl, vp, vp]
@@ -157,6 +160,8 @@ def load():
                                      P(Profile), vp]
     lib.icv_infercnv_run_windows.argtypes = [vp, P(Matrix), vp, vp, dbl, dbl, i64, i64, i32, vp, i64, vp, vp, vp,
                                              P(Profile), vp, i64, vp]
+    lib.icv_infercnv_run_finite.argtypes = [vp, P(Matrix), vp, vp, dbl, dbl, i64, i64, i32, vp, i64, vp, vp, vp,
+                                            P(Profile), vp, i64, vp, vp]
     lib.icv_gene_values_from_windows.argtypes = [vp, vp, i64, i64, vp, i64, i64, vp, i64, vp]
     lib.icv_colchain_blocks_workspace.argtypes = [i64, i32, P(i64)]
     lib.icv_colchain_blocks_sums.argtypes = [P(Matrix), vp, vp, vp]

@@ -161,9 +161,18 @@ class GenePlan:
         return dict(first=first, count=count, genes=genes, col_run=col_run)
 
     def last_kernel(self) -> int:
-        """``_lib.ICV_KERNEL_*`` of the smoothing kernel the last compute call on this plan launched."""
+        """``_lib.ICV_KERNEL_*`` of the smoothing kernel the last compute call on this plan launched.  After a call that
+        passed ``finite_words`` and took k_smooth_x16, the device chose between the kernel's two forms: this reads
+        the choice back (``ICV_KERNEL_X16_FINITE`` or ``ICV_KERNEL_X16``) and so waits for that call."""
         kind = C.c_int32(0)
         _lib.check(_lib.load().icv_plan_last_kernel(self._handle, C.byref(kind)))
+        return int(kind.value)
+
+    def last_route(self) -> int:
+        """The route the host picked for the last compute call (``ICV_KERNEL_X16`` for either form of k_smooth_x16):
+        never waits for the device."""
+        kind = C.c_int32(0)
+        _lib.check(_lib.load().icv_plan_last_route(self._handle, C.byref(kind)))
         return int(kind.value)
 
     def last_handed_back(self) -> int:

@@ -103,14 +103,15 @@ bool matrix_complete(const icv_matrix* m) { return m->format == ICV_DENSE ? m->v
 // getenv per dispatch, and a production call's route must not follow an environment edited under it); a test that
 // changes them calls icv_developer_knobs_reload().
 struct Knobs {
-    bool force_generic, no_x16, no_sd, phase_profile, ward_in_place, no_mask_ring, no_fill_ring, no_chain_queues,
-         no_gene_fused;
+    bool force_generic, no_x16, no_x16_finite, no_sd, phase_profile, ward_in_place, no_mask_ring, no_fill_ring,
+         no_chain_queues, no_gene_fused;
     int chain_far;         // ICV_CHAIN_FAR: entries a buffer offset may span in k_colchain_csrq (tests: a small value)
     int chain_pieces;      // ICV_CHAIN_PIECES: lanes per row of k_colchain_csrq (2 / 4 / 8 / 16; 0 = from the density)
     double ward_compact_x; // 0 = not set
     void load() {
         force_generic = std::getenv("ICV_FORCE_GENERIC") != nullptr;
         no_x16 = std::getenv("ICV_NO_X16") != nullptr;
+        no_x16_finite = std::getenv("ICV_NO_X16_FINITE") != nullptr;  // k_smooth_x16 in its checked form only
         no_sd = std::getenv("ICV_NO_SD") != nullptr;
         phase_profile = std::getenv("ICV_PHASE_PROFILE") != nullptr;
         ward_in_place = std::getenv("ICV_WARD_IN_PLACE") != nullptr;
@@ -159,6 +160,8 @@ struct icv_plan_s {
     int gv_mult_bytes = 2;  // bytes per run length in the kernel's LDS (1 where every run has at most 255 genes)
     int64_t* d_row_list = nullptr;  // cells handed back by k_smooth_ws to the generic kernel
     int* d_row_count = nullptr;
+    int32_t* d_x16_form = nullptr;  // which form of k_smooth_x16 applied when a call launched both (1: FINITE)
+    bool x16_both = false;          // the last compute call launched both forms
     int64_t row_list_cap = 0;
     // deferred profiling (icv_profile_begin / icv_profile_collect): event quadruples of the runs since begin
     bool prof_deferred = false;
@@ -324,6 +327,7 @@ int ensure_device(icv_plan_t pl) {
     {
         const unsigned zeros[2] = {0u, 0u};
         HIP_TRY(up(zeros, sizeof(zeros), (void**)&pl->d_tie_n));
+        HIP_TRY(up(zeros, sizeof(int32_t), (void**)&pl->d_x16_form));
     }
     HIP_TRY(up(p.cov_col.data(), p.cov_col.size() * 4, (void**)&pl->d_cov_col));
     HIP_TRY(up(p.cov_j0.data(), p.cov_j0.size() * 4, (void**)&pl->d_cov_j0));
@@ -499,6 +503,7 @@ typedef void (*SmoothKernel)(const icv::KParams);
 struct SmoothRoute {
     int kind = ICV_KERNEL_NONE;   // ICV_KERNEL_*
     SmoothKernel kern = nullptr;  // (ICV_KERNEL_SPLIT: none -- the chromosome groups take the generic kernel in turn)
+    SmoothKernel kern_finite = nullptr;  // k_smooth_x16<FINITE>, launched in front of `kern` where K.fin_words is set
     int64_t grid = 0;
     int block = icv::NT, lds = 0;
     int64_t moment_slots = 0;     // per-chunk partial-moment slots the launch writes (grid x wavefronts); 0: per-cell moments
@@ -518,6 +523,7 @@ int run_kernel(const SmoothRoute& r, const icv::KParams& K, hipStream_t st) {
         HIP_TRY(hipMemset(d, 0, 32 * sizeof(unsigned long long)));
         icv::KParams K2 = K;
         K2.dbg = d;
+        K2.fin_words = nullptr;  // one launch: the checked form
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, st, K2);
         HIP_TRY(hipStreamSynchronize(st));
         unsigned long long h[32];
@@ -554,6 +560,12 @@ int run_kernel(const SmoothRoute& r, const icv::KParams& K, hipStream_t st) {
                              "A-wait, gather+L, B1-wait, S+emit, S01+B3, W+B4; [6] = selector scan cycles, [7] = fallback cells)\n",
                      (double)h[6] / (double)K.n_rows, (double)h[7] / (double)K.n_rows);
         return ICV_OK;
+    }
+    if (r.kern_finite) {
+        // both forms back to back, no host synchronisation: each reads K.fin_words first and the one that does not
+        // apply returns at once
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(r.kern_finite), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL(r.kern_finite, dim3((unsigned)grid), dim3(block), lds, st, K);
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, st, K);
     HIP_TRY(hipGetLastError());
@@ -626,14 +638,18 @@ SmoothKernel ws_kernel(const icv::Plan& p, bool csr) {
 
 // k_smooth_x16: window 100 / step 10 or window 250 / step 10 (the instantiations assume step 10: blocks between adjacent
 // windows); null for every other geometry.  `win`: the float64 windows leave the kernel as well (chunk-moment mode only)
+// FIN: the form without NaN handling, for a matrix whose reference means certify it finite (KParams::fin_words)
+template <bool FIN>
 SmoothKernel x16_kernel(const icv::Plan& p, bool chunk, bool win) {
     if (!p.x16_ok || p.step != 10) return nullptr;
     if (p.B == 10 && p.window == 100 && p.x16_fine == 4096)
-        return win ? icv::k_smooth_x16<10, 10, 1, true, 4096, true, true>
-                   : (chunk ? icv::k_smooth_x16<10, 10, 1, true, 4096, true> : icv::k_smooth_x16<10, 10, 1, false, 4096, true>);
+        return win ? icv::k_smooth_x16<10, 10, 1, true, 4096, true, true, FIN>
+                   : (chunk ? icv::k_smooth_x16<10, 10, 1, true, 4096, true, false, FIN>
+                            : icv::k_smooth_x16<10, 10, 1, false, 4096, true, false, FIN>);
     if (p.B == 5 && p.window == 250 && p.x16_fine == 1024)
-        return win ? icv::k_smooth_x16<5, 50, 2, true, 1024, false, true>
-                   : (chunk ? icv::k_smooth_x16<5, 50, 2, true, 1024, false> : icv::k_smooth_x16<5, 50, 2, false, 1024, false>);
+        return win ? icv::k_smooth_x16<5, 50, 2, true, 1024, false, true, FIN>
+                   : (chunk ? icv::k_smooth_x16<5, 50, 2, true, 1024, false, false, FIN>
+                            : icv::k_smooth_x16<5, 50, 2, false, 1024, false, false, FIN>);
     return nullptr;
 }
 
@@ -713,10 +729,12 @@ SmoothRoute pick_route(const icv_plan_t pl, const icv_matrix* m, const icv::KPar
     const bool win_ok = !want_win || want_chunk_moments;  // the x16 / se instantiations that write windows form chunk moments
     if (fast_allowed && !csr && p.ws_ok && K.vec_ok) {
         // ICV_NO_X16=1: developer knob, the previous generation
-        const SmoothKernel xk = (K.bounded || kn.no_x16) ? nullptr : x16_kernel(p, want_chunk_moments, want_win);
+        const SmoothKernel xk = (K.bounded || kn.no_x16) ? nullptr : x16_kernel<false>(p, want_chunk_moments, want_win);
         if (xk && win_ok) {  // 16 wavefronts per cell, one 1024-thread workgroup per CU
             r.kind = ICV_KERNEL_X16;
             r.kern = xk;
+            // ICV_NO_X16_FINITE=1: developer knob, the checked form whatever the means say
+            if (K.fin_words && !kn.no_x16_finite) r.kern_finite = x16_kernel<true>(p, want_chunk_moments, want_win);
             r.grid = cu_grid(pl, 1, K.n_rows);
             r.block = icv::XT;
             r.lds = p.x16_lds;
@@ -849,6 +867,11 @@ int run_route(icv_plan_t pl, const SmoothRoute& r, const icv_matrix* m, icv::KPa
             L.win_off = p.x16_s01_off;
             L.hist_off = p.x16_hist_off;
             L.scratch_off = p.x16_scratch_off;
+            if (r.kern_finite) {
+                L.x16_form = pl->d_x16_form;
+            } else {
+                L.fin_words = nullptr;  // one launch, the checked form
+            }
         }
         if ((rc = run_kernel(r, L, st))) return rc;
     }
@@ -864,6 +887,7 @@ int run_route(icv_plan_t pl, const SmoothRoute& r, const icv_matrix* m, icv::KPa
         if ((rc = launch_hand_back(pl, K, st, m->format == ICV_CSR))) return rc;
     }
     pl->last_kernel = r.kind;
+    pl->x16_both = r.kern_finite != nullptr && r.grid >= 1 && !knobs().phase_profile;  // (the profile run launches one form)
     return ICV_OK;
 }
 
@@ -969,10 +993,22 @@ __global__ void k_chain_line_tiles(int n_lines, int grid, uint16_t* line_tile) {
     for (int l = l0; l < l1; ++l) line_tile[l] = (uint16_t)t;
 }
 
+static_assert(icv::kFinWords == ICV_FINITE_WORDS, "the words the header promises");
+// icv::kFinWords workgroups take the columns in turns.  words (optional): words[workgroup] = 1 if one of the means
+// the workgroup wrote is NaN or infinite, else 0 -- written unconditionally, so the buffer needs no clearing.  A chain
+// s = fl(s + x_r) that met a NaN stays NaN and one that met an infinity stays infinite (or turns NaN at the opposite
+// one), so all-zero words over the chains of ALL rows of a matrix say that every element of it is finite.
 template <typename T>
-__global__ void k_chain_mean(const T* acc, int n, T denom, T* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = acc[i] / denom;  // IEEE division (numpy: true_divide(sum, n) in the matrix dtype)
+__global__ void __launch_bounds__(1024) k_chain_mean(const T* acc, int n, T denom, T* out, uint32_t* words) {
+    int bad = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const T q = acc[i] / denom;  // IEEE division (numpy: true_divide(sum, n) in the matrix dtype)
+        out[i] = q;
+        bad |= !__builtin_isfinite(q);
+    }
+    if (!words) return;  // (uniform)
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) words[blockIdx.x] = bad ? 1u : 0u;
 }
 
 template <typename T>
@@ -1134,6 +1170,7 @@ void icv_plan_destroy(icv_plan_t pl) {
         (void)hipFree(pl->d_gv_col16);
         (void)hipFree(pl->d_row_list);
         (void)hipFree(pl->d_row_count);
+        (void)hipFree(pl->d_x16_form);
         (void)hipFree(pl->d_cell_part);
         (void)hipFree(pl->d_chunk_part);
         (void)hipFree(pl->d_hb_stats);
@@ -1168,9 +1205,22 @@ int icv_plan_get_info(icv_plan_t pl, icv_plan_info* info) {
     return ICV_OK;
 }
 
+int icv_plan_last_route(icv_plan_t pl, int32_t* kind) {
+    if (!pl || !kind) return fail(ICV_ERR_INVALID, "null argument");
+    *kind = pl->last_kernel;
+    return ICV_OK;
+}
+
 int icv_plan_last_kernel(icv_plan_t pl, int32_t* kind) {
     if (!pl || !kind) return fail(ICV_ERR_INVALID, "null argument");
     *kind = pl->last_kernel;
+    if (pl->last_kernel == ICV_KERNEL_X16 && pl->x16_both && pl->d_x16_form) {
+        // both forms were launched and the device chose: the form that applied left its mark (waits for that call)
+        if (pl->has_last) HIP_TRY(hipStreamSynchronize(pl->last_stream));
+        int32_t form = 0;
+        HIP_TRY(hipMemcpy(&form, pl->d_x16_form, sizeof(form), hipMemcpyDeviceToHost));
+        if (form) *kind = ICV_KERNEL_X16_FINITE;
+    }
     return ICV_OK;
 }
 
@@ -1402,14 +1452,21 @@ int icv_colchain(const icv_matrix* m, const int32_t* rows, int64_t n_sel, double
 }
 
 int icv_colchain_mean(const void* acc, int32_t dtype, int32_t n_cols, int64_t count, void* mean, void* stream) {
+    return icv_colchain_mean_finite(acc, dtype, n_cols, count, mean, nullptr, stream);
+}
+
+int icv_colchain_mean_finite(const void* acc, int32_t dtype, int32_t n_cols, int64_t count, void* mean,
+                             uint32_t* finite_words, void* stream) {
     if (!acc || !mean || count < 1 || n_cols < 0) return fail(ICV_ERR_INVALID, "bad colchain_mean arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n_cols == 0) return ICV_OK;
     if (dtype != ICV_F32 && dtype != ICV_F64) return fail(ICV_ERR_INVALID, "dtype must be ICV_F32 or ICV_F64");
+    if (finite_words && (reinterpret_cast<uintptr_t>(finite_words) & 15))
+        return fail(ICV_ERR_INVALID, "icv_colchain_mean_finite: finite_words must be 16-byte aligned");
+    if (n_cols == 0 && !finite_words) return ICV_OK;  // (no column: every word 0)
     by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL(k_chain_mean<T>, dim3((n_cols + 255) / 256), dim3(256), 0, st, (const T*)acc, n_cols, (T)count,
-                           (T*)mean);
+        hipLaunchKernelGGL(k_chain_mean<T>, dim3(icv::kFinWords), dim3(1024), 0, st, (const T*)acc, n_cols, (T)count,
+                           (T*)mean, finite_words);
     });
     HIP_TRY(hipGetLastError());
     return ICV_OK;
@@ -1508,7 +1565,7 @@ int read_profile(const hipEvent_t* ev, icv_profile* prof) {
 int run_steps(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void* ref_hi, double lfc_clip,
               double dynamic_threshold, int64_t chunksize, int64_t row_phase, int32_t flags, float* out, int64_t ldo,
               double* cell_median, double* cell_stats, double* thr, icv_profile* prof, double* win_out, int64_t ldw,
-              void* stream) {
+              const uint32_t* finite_words, void* stream) {
     int rc;
     const bool do_thr = !std::isnan(dynamic_threshold);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1518,6 +1575,7 @@ int run_steps(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void
         return rc;
     K.win_out = win_out;
     K.win_ld = ldw;
+    K.fin_words = finite_words;
     // cell_stats == NULL: the caller only wants the thresholds.  The per-row moments then live in a plan-owned
     // buffer, and where k_smooth_x16 runs they are not formed per cell at all: the kernel accumulates them per
     // chunk (one wavefront reduction per chunk instead of per cell).
@@ -1639,14 +1697,25 @@ int icv_infercnv_run(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, con
                      double dynamic_threshold, int64_t chunksize, int64_t row_phase, int32_t flags, float* out,
                      int64_t ldo, double* cell_median, double* cell_stats, double* thr, icv_profile* prof,
                      void* stream) {
-    return icv_infercnv_run_windows(pl, m, ref_lo, ref_hi, lfc_clip, dynamic_threshold, chunksize, row_phase, flags, out,
-                                    ldo, cell_median, cell_stats, thr, prof, nullptr, 0, stream);
+    return icv_infercnv_run_finite(pl, m, ref_lo, ref_hi, lfc_clip, dynamic_threshold, chunksize, row_phase, flags, out,
+                                   ldo, cell_median, cell_stats, thr, prof, nullptr, 0, nullptr, stream);
 }
 
 int icv_infercnv_run_windows(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void* ref_hi,
                              double lfc_clip, double dynamic_threshold, int64_t chunksize, int64_t row_phase,
                              int32_t flags, float* out, int64_t ldo, double* cell_median, double* cell_stats,
                              double* thr, icv_profile* prof, double* win_out, int64_t ldw, void* stream) {
+    return icv_infercnv_run_finite(pl, m, ref_lo, ref_hi, lfc_clip, dynamic_threshold, chunksize, row_phase, flags, out,
+                                   ldo, cell_median, cell_stats, thr, prof, win_out, ldw, nullptr, stream);
+}
+
+int icv_infercnv_run_finite(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, const void* ref_hi,
+                            double lfc_clip, double dynamic_threshold, int64_t chunksize, int64_t row_phase,
+                            int32_t flags, float* out, int64_t ldo, double* cell_median, double* cell_stats,
+                            double* thr, icv_profile* prof, double* win_out, int64_t ldw,
+                            const uint32_t* finite_words, void* stream) {
+    if (finite_words && (reinterpret_cast<uintptr_t>(finite_words) & 15))
+        return fail(ICV_ERR_INVALID, "finite_words must be 16-byte aligned");
     int rc = check_matrix(pl, m);
     if (rc) return rc;
     PLAN_BUSY_GUARD(pl);
@@ -1659,7 +1728,7 @@ int icv_infercnv_run_windows(icv_plan_t pl, const icv_matrix* m, const void* ref
     if ((rc = ensure_device(pl))) return rc;
     PLAN_ENTER(stream);
     return run_steps(pl, m, ref_lo, ref_hi, lfc_clip, dynamic_threshold, chunksize, row_phase, flags, out, ldo,
-                     cell_median, cell_stats, thr, prof, win_out, ldw, stream);
+                     cell_median, cell_stats, thr, prof, win_out, ldw, finite_words, stream);
 }
 
 int icv_gene_values_from_windows(icv_plan_t pl, const double* win, int64_t ldw, int64_t n_rows, const double* thr,
@@ -1723,7 +1792,7 @@ int icv_gene_values(icv_plan_t pl, const icv_matrix* m, const void* ref_lo, cons
     HIP_TRY(b_win.alloc((size_t)n * W * sizeof(double), st));
     HIP_TRY(b_cmed.alloc((size_t)n * sizeof(double), st));
     if ((rc = run_steps(pl, m, ref_lo, ref_hi, lfc_clip, std::nan(""), 1, 0, flags, b_out32.as<float>(), W,
-                        b_cmed.as<double>(), nullptr, nullptr, nullptr, b_win.as<double>(), W, stream)))
+                        b_cmed.as<double>(), nullptr, nullptr, nullptr, b_win.as<double>(), W, nullptr, stream)))
         return rc;
     return gene_from_windows(pl, b_win.as<double>(), W, n, thr, chunksize, row_phase, gene_out, ldg, st);
 }

@@ -105,8 +105,12 @@ __device__ __forceinline__ int hist_bin_x(double v, float inv_bound, float c_sca
 // of every L phase (long windows need the registers for larger batches of {S0,S1} reads)
 // WIN: the float64 windows of every cell (before centring) also go to P.win_out[cell * P.win_ld + j] -- what
 // calculate_gene_values averages (reference tl/_infercnv.py:274-288); cells handed back are rewritten by k_smooth
+// FINITE: every element of the matrix is finite (and so is the reference row), so no centred value, block sum or
+// window is NaN: the kernel without its NaN handling (v_med3 drops NaNs where np.clip keeps them: the unordered tests
+// and fix-up stores of the L phase, the NaN flag of a cell's windows, the NaN-cell tests of scan, rank, gather and
+// output).  Everything else is the same code.  Who may say so: P.fin_words below.
 template <int BT, int NBW, int SB /* blocks between adjacent windows = step / BT */, bool CHUNK, int FINE, bool REFRES,
-          bool WIN = false>
+          bool WIN = false, bool FINITE = false>
 __global__ void __launch_bounds__(XT) k_smooth_x16(const KParams P) {
     constexpr int XFINE = FINE, XCOARSE = FINE / 64;
     static_assert(FINE % 1024 == 0 && XCOARSE * XREP <= XT && FINE / 4 <= XT, "histogram cleared by one store per thread");
@@ -119,6 +123,18 @@ __global__ void __launch_bounds__(XT) k_smooth_x16(const KParams P) {
     float* stage = reinterpret_cast<float*>(smem + P.scratch_off + kFastScratchBytes);  // x_res of one cell (16-byte stores)
     static_assert(BT >= 2 && NBW > 0 && NBW % 2 == 0, "compile-time block size, even number of blocks per window");
 
+    // P.fin_words != null: the call launches this kernel in BOTH forms, back to back, and the words (written by
+    // k_chain_mean when it formed the reference row: non-zero = a mean that is not finite) say which one applies; the
+    // other returns here, before it touches LDS or the matrix.  Uniform address: the words come through the scalar cache.
+    if (FINITE || P.fin_words) {
+        const uint4* fw = reinterpret_cast<const uint4*>(P.fin_words);
+        static_assert(kFinWords == 16, "four 16-byte loads");
+        const uint4 fa = fw[0], fb = fw[1], fc = fw[2], fd = fw[3];
+        const unsigned bad = ((fa.x | fa.y) | (fa.z | fa.w)) | ((fb.x | fb.y) | (fb.z | fb.w)) |
+                             ((fc.x | fc.y) | (fc.z | fc.w)) | ((fd.x | fd.y) | (fd.z | fd.w));
+        if ((bad != 0u) == FINITE) return;
+        if (blockIdx.x == 0 && threadIdx.x == 0) *P.x16_form = FINITE ? 1 : 0;  // (icv_plan_last_kernel)
+    }
 
     const int t = threadIdx.x;
     const int W = P.W, NB = P.NB;
@@ -228,12 +244,13 @@ __global__ void __launch_bounds__(XT) k_smooth_x16(const KParams P) {
                              f32x2{__uint_as_float(rv.z), __uint_as_float(rv.w)};
             const float y0 = ya.x, y1 = ya.y, y2 = yb.x, y3 = yb.y;
             // v_med3 drops NaNs, np.clip keeps them: unordered pairs take the (never taken on real data) fix-up
-            const bool un = __builtin_isunordered(y0, y1) | __builtin_isunordered(y2, y3);
+            bool un = false;
+            if constexpr (!FINITE) un = __builtin_isunordered(y0, y1) | __builtin_isunordered(y2, y3);
             ICV_LDS_F32_AT(laddr[u][0]) = __builtin_amdgcn_fmed3f(y0, -cap, cap);
             ICV_LDS_F32_AT(laddr[u][1]) = __builtin_amdgcn_fmed3f(y1, -cap, cap);
             ICV_LDS_F32_AT(laddr[u][2]) = __builtin_amdgcn_fmed3f(y2, -cap, cap);
             ICV_LDS_F32_AT(laddr[u][3]) = __builtin_amdgcn_fmed3f(y3, -cap, cap);
-            if (__builtin_expect(un, 0)) {
+            if (!FINITE && __builtin_expect(un, 0)) {
                 if (y0 != y0) ICV_LDS_F32_AT(laddr[u][0]) = y0;
                 if (y1 != y1) ICV_LDS_F32_AT(laddr[u][1]) = y1;
                 if (y2 != y2) ICV_LDS_F32_AT(laddr[u][2]) = y2;
@@ -327,9 +344,9 @@ __global__ void __launch_bounds__(XT) k_smooth_x16(const KParams P) {
             const unsigned* cz = coarse + p1 * (XREP * XCOARSE);
             const unsigned* fz = hist + p1 * XFINE;
             const uint4* c4 = reinterpret_cast<const uint4*>(cz + (tl < XCOARSE ? tl : 0) * XREP);
-            const int nanf = sc->nanflag[p1];
+            const int nanf = FINITE ? 0 : sc->nanflag[p1];
             const uint4 ca = c4[0], cb = c4[1], cc = c4[2], cd = c4[3];
-            if (nanf) {
+            if (!FINITE && nanf) {
                 if (tl == 0) {
                     sc->nanflag[p1] = 0;
                     sc->sel[p1][5] = 1;
@@ -371,7 +388,7 @@ __global__ void __launch_bounds__(XT) k_smooth_x16(const KParams P) {
             const double mine_raw = sc->cand[p0][lane];  // unconditional: one LDS round trip for all four reads
             const int nin = s.w + (s.y != s.x ? s2.x : 0);
             double ma = 0.0, mb = 0.0;  // handed-back cell: placeholder, rewritten by k_smooth
-            if (s2.y) {
+            if (!FINITE && s2.y) {
                 ma = mb = __builtin_nan("");
             } else if (nin <= 64) {
                 const int n = ncr < 64 ? ncr : 64;
@@ -484,7 +501,7 @@ __global__ void __launch_bounds__(XT) k_smooth_x16(const KParams P) {
                     // a cell handed back to k_smooth (more than 64 windows in the median bins) is accounted there
                     const int4 s = *reinterpret_cast<const int4*>(sc->sel[p0]);
                     const int2 s2 = *reinterpret_cast<const int2*>(sc->sel[p0] + 4);
-                    const bool handed = !s2.y && s.w + (s.y != s.x ? s2.x : 0) > 64;
+                    const bool handed = (FINITE || !s2.y) && s.w + (s.y != s.x ? s2.x : 0) > 64;
                     if (!handed) {
                         if (v0) {
                             accS = accS + y0;
@@ -523,7 +540,7 @@ __global__ void __launch_bounds__(XT) k_smooth_x16(const KParams P) {
             const int4 s = *reinterpret_cast<const int4*>(sc->sel[p1]);
             const int2 s2 = *reinterpret_cast<const int2*>(sc->sel[p1] + 4);
             const int nin = s.w + (s.y != s.x ? s2.x : 0);
-            if (!s2.y) {
+            if (FINITE || !s2.y) {
                 if (nin <= 64) {
                     const unsigned span = (unsigned)(s.y - s.x);
                     const bool hA = (wbB & 0xffffu) - (unsigned)s.x <= span, hB = (wbB >> 16) - (unsigned)s.x <= span;
@@ -638,8 +655,10 @@ __global__ void __launch_bounds__(XT) k_smooth_x16(const KParams P) {
                 atomicAdd(fz + h1, 1u);
                 atomicAdd(cz + (h1 >> 6) * XREP, 1u);
             }
-            const double vs = w1 ? v0 + v1 : v0;  // NaN in either window (|window| is bounded: no inf - inf)
-            if (w0 && vs != vs) sc->nanflag[p0] = 1;  // benign race: every writer stores 1
+            if constexpr (!FINITE) {
+                const double vs = w1 ? v0 + v1 : v0;  // NaN in either window (|window| is bounded: no inf - inf)
+                if (w0 && vs != vs) sc->nanflag[p0] = 1;  // benign race: every writer stores 1
+            }
         }
         ICV_XPH(5)
         const int64_t nxt = cell + gridDim.x;

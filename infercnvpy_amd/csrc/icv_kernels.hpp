@@ -22,6 +22,8 @@ namespace icv {
 
 constexpr int NT = 512;
 constexpr int NWAVE = NT / 64;
+// workgroups of k_chain_mean = words of its finite-means report (KParams::fin_words): what one 64-byte scalar load reads
+constexpr int kFinWords = 16;
 
 struct KParams {
     // input matrix
@@ -89,6 +91,10 @@ struct KParams {
     // block count | gene count << 16
     const uint32_t* x16_wdesc;
     int32_t x16_half, _pad4;  // k_smooth_x16: slots of the even-block {S0,S1} array
+    // k_smooth_x16, optional: the kFinWords words k_chain_mean wrote next to the reference row (non-zero = a mean that
+    // is not finite), and where the form of the kernel that applied records itself (1: FINITE, 0: checked)
+    const uint32_t* fin_words;
+    int32_t* x16_form;
     // k_smooth_se (CSR float32, stored entries only).  Per block the gene offset of its first gene inside its
     // chromosome; per input column {LDS address of the block's bins, ref_lo, in-block offset * 2^k1, clip(0 - ref)}
     // (k_se_table), ref_hi per column (bounded references); per window {w0, w1, zero-row sum} (k_se_wtab); per block

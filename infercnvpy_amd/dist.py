@@ -141,7 +141,30 @@ def chain_column_groups(n_cols: int, esz: int, n_groups: int):
     return out
 
 
-def reference_means_chained(dm_local, counts_global, local_rows=None, group=None, n_col_groups=2):
+def _broadcast_from_last(t, group=None):
+    """``t`` of the last rank of the group on every rank (through the host unless the backend is nccl)."""
+    dist = _dist()
+    _, size, peers = _group_ranks(group)
+    if size > 1:
+        if t.is_cuda and dist.get_backend(group) != "nccl":
+            h = t.cpu()
+            dist.broadcast(h, peers[size - 1], group=group)
+            t.copy_(h)
+        else:
+            dist.broadcast(t, peers[size - 1], group=group)
+    return t
+
+
+def _chain_mean_words(acc, count, group=None):
+    """``(means, words)`` of ``_engine.chain_mean(..., finite_words=True)`` on dense all-cell accumulators, the words
+    being those of the LAST rank (its accumulators are the chains over all ranks' rows) on every rank."""
+    from . import _engine
+
+    mean, words = _engine.chain_mean(acc, count, False, finite_words=True)
+    return mean, _broadcast_from_last(words, group)
+
+
+def reference_means_chained(dm_local, counts_global, local_rows=None, group=None, n_col_groups=2, finite_words=False):
     """The reference profile in the REFERENCE'S OWN evaluation order over row-sharded ranks (bit-equal to
     ``np.mean(X, axis=0)`` / scipy's CSR mean of the whole matrix, reference :385, :400): a float32 column sum is a
     sequential chain, so rank k continues the accumulators of rank k - 1 (``icv_colchain``) and hands them to rank
@@ -158,16 +181,21 @@ def reference_means_chained(dm_local, counts_global, local_rows=None, group=None
 
     ``dm_local``: this rank's rows (``_engine.DeviceMatrix``); ``counts_global``: rows per category over ALL ranks;
     ``local_rows``: per category the ascending local row indices (None: one category, all rows).  Returns the
-    ``[R, G]`` means as a device tensor of the matrix dtype, identical on every rank."""
+    ``[R, G]`` means as a device tensor of the matrix dtype, identical on every rank.
+
+    ``finite_words=True`` (dense float32, one category of all rows): returns ``(means, words)`` -- the finite-means
+    words of the last rank's ``chain_mean``, identical on every rank: what :func:`run_shard` takes as ``finite_words``
+    (the chains ran over the rows of ALL ranks, so all-zero words certify every shard finite)."""
     import torch
 
     from . import _engine, _lib
 
-    dist = _dist()
     rank, size, peers = _group_ranks(group)
     n_groups = len(counts_global)
     n_cols = dm_local.shape[1]
     is_csr = dm_local.format == _lib.ICV_CSR
+    if finite_words and (is_csr or dm_local.dtype != torch.float32 or n_groups != 1 or local_rows is not None):
+        raise ValueError("reference_means_chained: finite_words are for the all-cell means of dense float32 shards")
     esz = 4 if dm_local.dtype == torch.float32 else 8
     col_groups = [(0, n_cols)] if (is_csr or size == 1) else chain_column_groups(n_cols, esz, n_col_groups)
     device = getattr(dm_local, "device", "cuda")
@@ -185,18 +213,17 @@ def reference_means_chained(dm_local, counts_global, local_rows=None, group=None
                 _engine.column_chain(dm_local, accs[g], rows, int(counts_global[g]), cols=None if whole else (c0, c1))
         if size > 1 and rank < size - 1:
             _p2p(accs if whole else accs[:, c0:c1].contiguous(), peers[rank + 1], send=True, group=group)
-    means = torch.stack([_engine.chain_mean(accs[g], int(counts_global[g]), is_csr) for g in range(n_groups)])
-    if size > 1:
-        if means.is_cuda and dist.get_backend(group) != "nccl":
-            h = means.cpu()
-            dist.broadcast(h, peers[size - 1], group=group)
-            means.copy_(h)
-        else:
-            dist.broadcast(means, peers[size - 1], group=group)
-    return means
+    words = None
+    if finite_words:
+        mean, words = _chain_mean_words(accs[0], int(counts_global[0]), group)
+        means = mean[None, :]
+    else:
+        means = torch.stack([_engine.chain_mean(accs[g], int(counts_global[g]), is_csr) for g in range(n_groups)])
+    means = _broadcast_from_last(means, group)
+    return (means, words) if finite_words else means
 
 
-def reference_means_blocks(dm_local, n_total, group=None, n_col_groups=4, stats=None):
+def reference_means_blocks(dm_local, n_total, group=None, n_col_groups=4, stats=None, finite_words=False):
     """The all-cell reference profile of a row-sharded DENSE float32 matrix in the reference's own evaluation order
     (bit-equal to ``np.mean(X, axis=0)`` of the whole matrix, reference :385, and to :func:`reference_means_chained`)
     WITHOUT the ranks taking turns on their rows (``csrc/icv_kernel_blocks.hpp``; proofs: ``tests/exact_chain_proto.py``).
@@ -213,7 +240,7 @@ def reference_means_blocks(dm_local, n_total, group=None, n_col_groups=4, stats=
 
     Two passes over the shard instead of one, but both concurrent on all ranks: at 8 ranks the means cost ~2 passes of one
     rank's rows + a scan, where the chained form costs (T + R - 1) / T = 4.5 passes.  Other inputs (CSR,
-    float64, categories) keep :func:`reference_means_chained`."""
+    float64, categories) keep :func:`reference_means_chained`.  ``finite_words=True``: ``(means, words)`` as there."""
     import torch
 
     from . import _engine, _lib
@@ -251,36 +278,36 @@ def reference_means_blocks(dm_local, n_total, group=None, n_col_groups=4, stats=
             cb.scan(acc, cols=(c0, c1))
         if size > 1 and rank < size - 1:
             _p2p(acc[c0:c1].contiguous(), peers[rank + 1], send=True, group=group)
-    means = _engine.chain_mean(acc, int(n_total), False)[None, :]
-    if size > 1:
-        if means.is_cuda and dist.get_backend(group) != "nccl":
-            h = means.cpu()
-            dist.broadcast(h, peers[size - 1], group=group)
-            means = h.to(device)
-        else:
-            dist.broadcast(means, peers[size - 1], group=group)
+    words = None
+    if finite_words:
+        mean, words = _chain_mean_words(acc, int(n_total), group)
+        means = mean[None, :]
+    else:
+        means = _engine.chain_mean(acc, int(n_total), False)[None, :]
+    means = _broadcast_from_last(means, group)
     if stats is not None and have_rows:
         stats["blocks"] = cb.n_blocks()
         stats["replayed"] = int(cb.replayed.item())
-    return means
+    return (means, words) if finite_words else means
 
 
-def reference_means_exact(dm_local, n_total, group=None, stats=None):
+def reference_means_exact(dm_local, n_total, group=None, stats=None, finite_words=False):
     """The all-cell reference profile in the reference's own evaluation order (numpy's / scipy's bits) over a row-sharded
     matrix, by whichever exact form is faster at this group size: the chain by integer blocks
     (:func:`reference_means_blocks`: two concurrent passes + a scan that travels) from 4 ranks on for dense float32 shards,
     the chained accumulators (:func:`reference_means_chained`: one pass, the ranks take turns, pipelined over two column
     groups) below that and for every other input.  With R ranks and T = 2 column groups the chained form costs
     (T + R - 1) / T passes of one rank's rows -- 1.5 at R = 2, 2.5 at R = 4, 4.5 at R = 8 -- against ~2.2 for the blocks
-    (DESIGN.md 6).  Same bits either way; returns ``[1, G]`` means of the matrix's dtype on every rank."""
+    (DESIGN.md 6).  Same bits either way; returns ``[1, G]`` means of the matrix's dtype on every rank
+    (``finite_words=True``, dense float32 shards: ``(means, words)`` for :func:`run_shard`)."""
     import torch
 
     from . import _lib
 
     _, size, _ = _group_ranks(group)
     if size >= 4 and dm_local.format == _lib.ICV_DENSE and dm_local.dtype == torch.float32:
-        return reference_means_blocks(dm_local, n_total, group=group, stats=stats)
-    return reference_means_chained(dm_local, [n_total], group=group)
+        return reference_means_blocks(dm_local, n_total, group=group, stats=stats, finite_words=finite_words)
+    return reference_means_chained(dm_local, [n_total], group=group, finite_words=finite_words)
 
 
 def chunk_moments(cell_stats, global_row0: int, chunksize: int, n_chunks_global: int):
@@ -349,7 +376,8 @@ def agree_aligned(local_aligned: bool, device="cpu", group=None) -> bool:
 
 
 def run_shard(plan, dm_local, ref_lo, ref_hi=None, *, global_row0=0, n_obs_global=None, lfc_clip=3.0,
-              dynamic_threshold=1.5, chunksize=5000, flags=0, group=None, all_bounds=None, out=None, pack=False):
+              dynamic_threshold=1.5, chunksize=5000, flags=0, group=None, all_bounds=None, out=None, pack=False,
+              finite_words=None):
     """Hot path for this rank's rows of a row-sharded matrix (device resident).
 
     Whether the noise threshold needs communication is a property of the WHOLE partition, and every rank must
@@ -361,6 +389,9 @@ def run_shard(plan, dm_local, ref_lo, ref_hi=None, *, global_row0=0, n_obs_globa
     Returns the local :class:`infercnvpy_amd._engine.SmoothResult`; with ``pack=True`` ``(result, PackedCsr)``: the
     thresholds are applied while ``X_cnv`` is packed to CSR on the device (``_engine.threshold_csr``; ``result.out``
     stays un-thresholded), as the public call does.
+
+    ``finite_words``: only the words that came with ``ref_lo`` from ``reference_means_*(..., finite_words=True)``, i.e.
+    from chains over the rows of ALL ranks (``_engine.run_hot_path``); never with a profile from elsewhere.
     """
     import ctypes as C
 
@@ -377,7 +408,7 @@ def run_shard(plan, dm_local, ref_lo, ref_hi=None, *, global_row0=0, n_obs_globa
     if dynamic_threshold is None or aligned:
         res = _engine.run_hot_path(plan, dm_local, ref_lo, ref_hi, lfc_clip=lfc_clip,
                                    dynamic_threshold=dynamic_threshold, chunksize=chunksize, flags=flags, out=out,
-                                   apply=not pack)
+                                   apply=not pack, finite_words=finite_words)
         if not pack:
             return res
         return res, _engine.threshold_csr(plan, dm_local, ref_lo, ref_hi, res, lfc_clip=lfc_clip, chunksize=chunksize,
@@ -385,7 +416,7 @@ def run_shard(plan, dm_local, ref_lo, ref_hi=None, *, global_row0=0, n_obs_globa
     torch = _engine._torch()
     lib = _lib.load()
     res = _engine.run_hot_path(plan, dm_local, ref_lo, ref_hi, lfc_clip=lfc_clip, dynamic_threshold=None,
-                               chunksize=chunksize, flags=flags, cell_stats=True, out=out)
+                               chunksize=chunksize, flags=flags, cell_stats=True, out=out, finite_words=finite_words)
     thr_all = global_thresholds(res.cell_stats, global_row0, n_obs_global, chunksize, plan.n_windows,
                                 float(dynamic_threshold), group)
     if rows == 0:

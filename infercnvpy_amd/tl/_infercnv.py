@@ -236,15 +236,16 @@ def _warn_skipped(plan):
         log.warning(f"Skipped {plan.n_without_position} genes because they don't have a genomic position annotated. ")
 
 
-def _piece_step(call, plan, dm, ref_lo, ref_hi, flags, r0, r1, emit, gene_out=None):
+def _piece_step(call, plan, dm, ref_lo, ref_hi, flags, r0, r1, emit, gene_out=None, finite_words=None):
     """Rows [r0, r1) of the device matrix ``dm`` (whole chunks): one smoothing launch -- with
     ``calculate_gene_values`` it also writes its float64 windows, as the reference's ``_infercnv_chunk`` returns both
     from one pass (:438-457) --, then step 5b + ``csr_matrix(x_res)`` on the device (keep-mask, row offsets, fill), whose
     ``PackedCsr`` goes to ``emit``, then the gene layer of the piece from the windows in one kernel (the piece's
-    thresholds are those of its rows' chunks): into ``gene_out``, or a new tensor.  Returns the gene values (None without)."""
+    thresholds are those of its rows' chunks): into ``gene_out``, or a new tensor.  Returns the gene values (None without).
+    ``finite_words``: see :func:`_means_certify_finite`."""
     tail = dict(lfc_clip=call.lfc_clip, chunksize=call.chunksize, flags=flags, row0=r0, row1=r1)
     res = _engine.run_hot_path(plan, dm, ref_lo, ref_hi, dynamic_threshold=call.dynamic_threshold, apply=False,
-                               windows=call.calculate_gene_values, **tail)
+                               windows=call.calculate_gene_values, finite_words=finite_words, **tail)
     emit(_engine.threshold_csr(plan, dm, ref_lo, ref_hi, res, **tail))
     if call.calculate_gene_values and r1 > r0:
         return _engine.gene_values_from_windows(plan, res.windows, thr=res.thr, chunksize=call.chunksize,
@@ -381,7 +382,7 @@ class _Shard:
         self.tm["reference_pass"] = _time.perf_counter() - t0
         return call.ref_box["ref"]
 
-    def _smooth(self, call, plan, ref_lo, ref_hi):
+    def _smooth(self, call, plan, ref_lo, ref_hi, finite_words=None):
         """X_cnv of the shard's rows, piece by piece behind the uploads; the drain packs and copies back finished pieces
         behind the kernels (only the row offsets and the packed entries are read back)."""
         t0 = _time.perf_counter()
@@ -389,7 +390,8 @@ class _Shard:
         for i in range(len(self.slabs)):
             ss = self._slab_stream(call, i)  # a single slab that a reference pass has already brought in is not uploaded again
             for r0, r1 in ss.pieces():
-                gv = _piece_step(call, plan, ss.dm, ref_lo, ref_hi, call.flags, r0, r1, self.drain.submit)
+                gv = _piece_step(call, plan, ss.dm, ref_lo, ref_hi, call.flags, r0, r1, self.drain.submit,
+                                 finite_words=finite_words)
                 if gv is not None:
                     self.gene_pieces.append(gv.cpu().numpy())
                     del gv
@@ -415,7 +417,15 @@ class _Shard:
         try:
             ref = call.given if call.given is not None else self._reference_pass(call)
             ref_lo, ref_hi = _ref_lo_hi(ref, call.compute)
-            self._smooth(call, plan, ref_lo, ref_hi)
+            finite_words = None
+            if call.given is None and _means_certify_finite(call, call.means_of[0],
+                                                            call.compute == np.float32 and not sp.issparse(X)):
+                # the means pass chained the uploads of ALL shards' rows and its quotients are on the host: the
+                # words k_chain_mean would have written (a piece uploaded as CSR takes another kernel, which ignores them)
+                torch = _engine._torch()
+                finite_words = torch.full((_lib.ICV_FINITE_WORDS,), int(not np.isfinite(ref).all()), dtype=torch.int32,
+                                          device="cuda")
+            self._smooth(call, plan, ref_lo, ref_hi, finite_words)
             # (kernel: _lib.ICV_KERNEL_*, which smoothing kernel the last piece took)
             self.tm.update(rows=n_rows, device=self.device, kernel=plan.last_kernel(),
                            total=_time.perf_counter() - t_sh)
@@ -570,9 +580,23 @@ def _is_real_anndata(adata):
     return mod == "anndata" or mod.startswith("anndata.")
 
 
+def _means_certify_finite(call, groups, dense_f32):
+    """May the smoothing kernel take the finite-means words of this call's reference pass (``_engine.chain_mean``)?
+
+    Only where the library itself formed the profile as the float32 chains s = fl(s + x) over ALL rows it is about to
+    smooth (``reference=None`` without categories, ``mean_order="reference"``, dense float32).  A NaN in a column makes
+    its chain NaN for good; an infinity makes it infinite, or NaN once the opposite infinity follows; so finite means
+    say that every element of the matrix is finite.  Then ``x - ref`` is finite or an infinity and never NaN, ``v_med3``
+    equals ``np.clip`` on it, and sums of clipped values are finite: the NaN handling of k_smooth_x16 has nothing to
+    find.  A given profile, means over a subset of the rows (``reference_cat``: the other rows may hold anything),
+    float64 column sums (not a chain), CSR and float64 input prove nothing of the kind and keep the checked kernel."""
+    return (call.reference is None and groups is None and call.mean_order == "reference" and dense_f32)
+
+
 def _resident_profile(torch, dm, obs, call):
-    """The R x G profile of a resident matrix as a device tensor of its dtype: the given one, or means over cells
-    formed where the matrix lies."""
+    """``(profile, finite words | None)``: the R x G profile of a resident matrix as a device tensor of its dtype -- the
+    given one, or means over cells formed where the matrix lies -- and, where :func:`_means_certify_finite` allows, the
+    words that say whether those means are all finite."""
     n_obs, n_vars = dm.shape
     np_dtype = np.float32 if dm.dtype == torch.float32 else np.float64
     given, groups, counts, cats = _reference_request(call.reference, call.reference_key, call.reference_cat, obs, n_obs,
@@ -581,7 +605,8 @@ def _resident_profile(torch, dm, obs, call):
         if np.result_type(np_dtype, given.dtype) != np_dtype:
             raise ValueError("a device-resident matrix needs a reference of its own (or a narrower) dtype: "
                              "numpy would promote the subtraction (pass the matrix as float64)")
-        return torch.from_numpy(np.ascontiguousarray(given.astype(np_dtype))).cuda()
+        return torch.from_numpy(np.ascontiguousarray(given.astype(np_dtype))).cuda(), None
+    words = None
     if call.mean_order == "float64":
         # opt-in: float64 column sums (one concurrent pass, correctly rounded means -- not numpy's order)
         sums = _engine.column_sums(dm, groups, len(counts))
@@ -592,8 +617,12 @@ def _resident_profile(torch, dm, obs, call):
         for gi, n_g in enumerate(counts):
             sel = None if groups is None else np.nonzero(groups == gi)[0]
             acc = _engine.column_chain(dm, None, sel, int(n_g))
-            rows.append(_engine.chain_mean(acc, int(n_g), dm.format == _lib.ICV_CSR))
-    return torch.stack(_repeat_rows(rows, cats))
+            if _means_certify_finite(call, groups, dm.format == _lib.ICV_DENSE and dm.dtype == torch.float32):
+                mean, words = _engine.chain_mean(acc, int(n_g), False, finite_words=True)
+                rows.append(mean)
+            else:
+                rows.append(_engine.chain_mean(acc, int(n_g), dm.format == _lib.ICV_CSR))
+    return torch.stack(_repeat_rows(rows, cats)), words
 
 
 def _infercnv_resident(var, obs, dm, call, tm):
@@ -610,7 +639,8 @@ def _infercnv_resident(var, obs, dm, call, tm):
                                    call.exclude_chromosomes, dev)
         try:
             _warn_skipped(plan)
-            ref_lo, ref_hi = _ref_lo_hi(_resident_profile(torch, dm, obs, call))
+            profile, finite_words = _resident_profile(torch, dm, obs, call)
+            ref_lo, ref_hi = _ref_lo_hi(profile)
             piece = _resident_piece_rows(n_obs, n_vars, plan.n_windows, _engine.free_hbm_bytes(), call.chunksize,
                                          call.calculate_gene_values)
             parts = []
@@ -619,10 +649,11 @@ def _infercnv_resident(var, obs, dm, call, tm):
                 r1 = min(n_obs, r0 + piece)
                 # (no kernel flags: the matrix is float32 / float64 and its profile never wider than it)
                 _piece_step(call, plan, dm, ref_lo, ref_hi, 0, r0, r1, parts.append,
-                            None if genes is None else genes[r0:r1])
+                            None if genes is None else genes[r0:r1], finite_words=finite_words)
             x_cnv = parts[0] if len(parts) == 1 else _engine.concat_packed(parts)
             # (total: host time only, nothing has been waited for)
-            tm.update(kernel=plan.last_kernel(), devices=[dev], pieces=len(parts), total=_time.perf_counter() - t_start)
+            # (last_route: plan.last_kernel() would wait for the device to say which form of k_smooth_x16 applied)
+            tm.update(kernel=plan.last_route(), devices=[dev], pieces=len(parts), total=_time.perf_counter() - t_start)
             chr_pos = dict(plan.chr_pos)
         finally:
             _checkin_plan(ent, plan)
