@@ -920,6 +920,57 @@ int icv_copy_posterior_stats(const icv_matrix *m, const int32_t *chr_start, int3
                              int32_t n_levels, int32_t neutral, double h, double ps, double pw, double *stats,
                              void *stream);
 
+/* ---- tl.cnv_copy_segments: level-aware segment tables of the int8 levels of tl.cnv_copy_states ---------------
+ * states (device int8, n_rows x n_cols row-major, no padding, any alignment) holds levels in [lo, hi], 0 neutral, with
+ * -ICV_LEVEL_MAX <= lo <= 0 <= hi <= ICV_LEVEL_MAX; chr_start as for icv_segments_count.  A run is that of
+ * icv_copy_states_filter: window t starts one iff states[i,t] != 0 and (t is a chromosome start or states[i,t-1] differs), it
+ * ends one iff states[i,t] != 0 and (t + 1 == n_cols or t + 1 is a chromosome start or states[i,t+1] differs): +1 +1 +2 is
+ * two runs.  Integer arithmetic: the results are a pure function of the arguments.
+ * icv_level_segments_count / icv_level_segments_fill: icv_segments_count / icv_segments_fill for levels: *bad (device int32)
+ * is set to 0 and then to 1 where a value lies outside [lo, hi]; seg_level (int8) is the byte of states at the run's start.
+ * With lo = -1, hi = 1 they are the two three-state entries.  n_cols has no limit below int32.
+ * icv_level_votes: rows and group_ptr as for icv_state_votes; counts (device int32, n_groups x (hi - lo + 1) x n_cols) is
+ * zeroed and counts[g,p,w] receives the number of listed rows of group g with level lo + p at window w, the neutral plane
+ * (p = -lo) included (integer atomic adds).  A row number outside [0, n_rows) is skipped; *bad as above, for the rows that
+ * are listed.
+ * icv_level_consensus: loss[g,w] / gain[g,w] (device int32, n_groups x n_cols) = the sums of the planes below / above the
+ * neutral one.  The sign of consensus[g,w] (device int8) is that of icv_state_consensus on them (+ iff gain >= need[g] and
+ * gain > loss, - iff loss >= need[g] and loss > gain, else 0), its magnitude the d in 1 .. hi (1 .. -lo) whose plane
+ * sign d holds the largest count, the smallest such d on a tie.
+ * icv_level_segments_support: for every segment of the consensus matrix (seg_row = the group) cells_min (int32) /
+ * cells_sum (int64) = the minimum / the sum over its windows of loss or gain, by the sign of seg_level; level_min /
+ * level_sum the same of the plane of seg_level.  A segment outside the tables, or with a level that is 0 or outside
+ * [lo, hi], gets 0 in all four.
+ * icv_segments_psum: for every segment k of the per-row tables (seg_row = the row of p_neutral, device float64 n_rows x
+ * n_cols row-major without padding) psum[k] (device int64) = the sum over [seg_start, seg_end) of
+ * q_t = int64(rint(p_neutral[i,t] 2^40)): double(psum) / (double(seg_end - seg_start) 2^40) is the mean of
+ * icv_copy_states_filter, bit for bit.  *bad is set to 0 and then to 1 where a posterior INSIDE a segment is not a number
+ * in [0, 1] (it adds 0).  Windows outside the segments are not read and are not validated.  A segment outside the plane
+ * gets 0.  A run has no other limit than n_cols <= ICV_FILTER_MAX_WINDOWS, which keeps its sum inside int64
+ * (ICV_ERR_UNSUPPORTED beyond).
+ * All six: ICV_ERR_INVALID, with the rule in icv_last_error and before anything is launched, for a null pointer (the
+ * tables of no segments and of no groups may be null), n_rows < 0 or another negative count, n_cols < 1, n_chr outside
+ * [1, n_cols] and a level range that breaks -7 <= lo <= 0 <= hi <= 7.  No rows, no groups or no segments: ICV_OK, nothing
+ * is launched.  No synchronisation. */
+#define ICV_LEVEL_MAX 7
+int icv_level_segments_count(const int8_t *states, int64_t n_rows, int32_t n_cols, const int32_t *chr_start, int32_t n_chr,
+                             int32_t lo, int32_t hi, int64_t *counts, int32_t *bad, void *stream);
+int icv_level_segments_fill(const int8_t *states, int64_t n_rows, int32_t n_cols, const int32_t *chr_start, int32_t n_chr,
+                            const int64_t *offsets, int64_t n_segments, int64_t *seg_row, int32_t *seg_start,
+                            int32_t *seg_end, int8_t *seg_level, void *stream);
+int icv_level_votes(const int8_t *states, int64_t n_rows, int32_t n_cols, const int64_t *rows, int64_t n_listed,
+                    const int64_t *group_ptr, int64_t n_groups, int32_t lo, int32_t hi, int32_t *counts, int32_t *bad,
+                    void *stream);
+int icv_level_consensus(const int32_t *counts, const int32_t *need, int64_t n_groups, int32_t n_cols, int32_t lo, int32_t hi,
+                        int32_t *loss, int32_t *gain, int8_t *consensus, void *stream);
+int icv_level_segments_support(const int64_t *seg_row, const int32_t *seg_start, const int32_t *seg_end,
+                               const int8_t *seg_level, int64_t n_segments, const int32_t *counts, const int32_t *loss,
+                               const int32_t *gain, int64_t n_groups, int32_t n_cols, int32_t lo, int32_t hi,
+                               int32_t *cells_min, int64_t *cells_sum, int32_t *level_min, int64_t *level_sum, void *stream);
+int icv_segments_psum(const double *p_neutral, int64_t n_rows, int32_t n_cols, const int64_t *seg_row,
+                      const int32_t *seg_start, const int32_t *seg_end, int64_t n_segments, int64_t *psum, int32_t *bad,
+                      void *stream);
+
 /* ---- upload path of a mostly-zero DENSE host matrix (reference tl/_infercnv.py:115-116, :422-423: a dense adata.X of
  * log-counts is ~80 % zeros; PCIe is what a host-input call waits for) -- HOST functions (h_ pointers), no GPU needed:
  * icv_host_dense_row_nnz counts the stored entries (bit pattern != 0: NaN and -0.0 count) of every row of a row-major

@@ -2058,6 +2058,98 @@ def segments_support(row, start, end, state, loss, gain):
     return cells_min, cells_sum
 
 
+# ---- tl.cnv_copy_segments: the same for levels in [lo, hi], and the posterior sums of the runs (icv_level_*) --
+def level_segments_tables(states, chr_start, lo, hi):
+    """:func:`segments_tables` for levels: ``(counts, offsets, row, start, end, level int8, bad int32 flag)``, ``bad`` set
+    where a value lies outside ``[lo, hi]``.  One scalar (the number of segments) is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
+    n, w = int(states.shape[0]), int(states.shape[1])
+    with torch.cuda.device(states.device):
+        st = _stream_ptr(torch)
+        cs, n_chr = _chr_start_upload(torch, chr_start)
+        counts = _empty(torch, n, torch.int64)
+        bad = torch.empty(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.icv_level_segments_count(_ptr(states), n, w, _ptr(cs), n_chr, int(lo), int(hi), _ptr(counts),
+                                                _ptr(bad), st))
+        offsets = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+        _lib.check(lib.icv_row_offsets(_ptr(counts), n, _ptr(offsets), st))
+        n_seg = int(offsets[-1].item())
+        row, start, end, level = (_empty(torch, n_seg, t) for t in (torch.int64, torch.int32, torch.int32, torch.int8))
+        _lib.check(lib.icv_level_segments_fill(_ptr(states), n, w, _ptr(cs), n_chr, _ptr(offsets), n_seg, _ptr(row),
+                                               _ptr(start), _ptr(end), _ptr(level), st))
+    return counts, offsets, row, start, end, level, bad
+
+
+def level_votes(states, rows, group_ptr, lo, hi):
+    """(counts, bad): device int32 ``G x (hi - lo + 1) x W`` counts of the listed rows of every group with level ``lo + p``
+    at each window (rule 4) and the device int32 flag of a value outside ``[lo, hi]``.  ``rows`` / ``group_ptr`` as for
+    :func:`state_votes`.  Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    assert states.is_cuda and states.dtype == torch.int8 and states.dim() == 2 and states.is_contiguous()
+    n, w = int(states.shape[0]), int(states.shape[1])
+    assert int(group_ptr[0]) == 0 and int(group_ptr[-1]) == len(rows)
+    with torch.cuda.device(states.device):
+        d_rows, d_ptr, g = _group_lists_upload(torch, rows, group_ptr)
+        counts = torch.empty((g, int(hi) - int(lo) + 1, w), dtype=torch.int32, device="cuda")
+        bad = torch.empty(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.icv_level_votes(_ptr(states), n, w, _ptr(d_rows), int(d_rows.shape[0]), _ptr(d_ptr), g, int(lo),
+                                       int(hi), _ptr(counts), _ptr(bad), _stream_ptr(torch)))
+    return counts, bad
+
+
+def level_consensus(counts, need, lo, hi):
+    """(loss int32 G x W, gain int32 G x W, consensus int8 G x W) of rule 5, device tensors; ``need``: host int32 per
+    group."""
+    torch = _torch()
+    lib = _lib.load()
+    g, w = int(counts.shape[0]), int(counts.shape[2])
+    need = np.ascontiguousarray(need, dtype=np.int32)
+    assert need.shape == (g,) and counts.dtype == torch.int32 and int(counts.shape[1]) == int(hi) - int(lo) + 1
+    with torch.cuda.device(counts.device):
+        d_need = torch.from_numpy(need).cuda()
+        loss = torch.empty((g, w), dtype=torch.int32, device="cuda")
+        gain = torch.empty((g, w), dtype=torch.int32, device="cuda")
+        consensus = torch.empty((g, w), dtype=torch.int8, device="cuda")
+        _lib.check(lib.icv_level_consensus(_ptr(counts), _ptr(d_need), g, w, int(lo), int(hi), _ptr(loss), _ptr(gain),
+                                           _ptr(consensus), _stream_ptr(torch)))
+    return loss, gain, consensus
+
+
+def level_segments_support(row, start, end, level, counts, loss, gain, lo, hi):
+    """(cells_min int32, cells_sum int64, level_min int32, level_sum int64) of rule 6 for the segments of the consensus
+    matrix, device tensors."""
+    torch = _torch()
+    lib = _lib.load()
+    n_seg = int(row.shape[0])
+    g, w = int(loss.shape[0]), int(loss.shape[1])
+    with torch.cuda.device(loss.device):
+        cells_min, level_min = _empty(torch, n_seg, torch.int32), _empty(torch, n_seg, torch.int32)
+        cells_sum, level_sum = _empty(torch, n_seg, torch.int64), _empty(torch, n_seg, torch.int64)
+        _lib.check(lib.icv_level_segments_support(_ptr(row), _ptr(start), _ptr(end), _ptr(level), n_seg, _ptr(counts),
+                                                  _ptr(loss), _ptr(gain), g, w, int(lo), int(hi), _ptr(cells_min),
+                                                  _ptr(cells_sum), _ptr(level_min), _ptr(level_sum), _stream_ptr(torch)))
+    return cells_min, cells_sum, level_min, level_sum
+
+
+def segments_psum(p_neutral, row, start, end):
+    """(psum int64 per segment, bad int32 flag), device tensors: the sum of ``rint(P 2^40)`` over every segment of the
+    per-cell tables (rule 3); ``p_neutral``: device float64 ``n x W``.  Nothing is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    assert p_neutral.is_cuda and p_neutral.dtype == torch.float64 and p_neutral.dim() == 2 and p_neutral.is_contiguous()
+    n, w = int(p_neutral.shape[0]), int(p_neutral.shape[1])
+    n_seg = int(row.shape[0])
+    with torch.cuda.device(p_neutral.device):
+        psum = _empty(torch, n_seg, torch.int64)
+        bad = torch.empty(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.icv_segments_psum(_ptr(p_neutral), n, w, _ptr(row), _ptr(start), _ptr(end), n_seg, _ptr(psum),
+                                         _ptr(bad), _stream_ptr(torch)))
+    return psum, bad
+
+
 # ---- tl.cnv_pseudobulk: exact per-group mean profiles on the device (icv_group_profiles*, DESIGN.md 4.17) ------------------
 def group_profiles(dm: DeviceMatrix, rows, group_ptr, shift):
     """(sum, stored, flags): device int64 / int32 ``G x W`` tables of rule 4 over the listed rows of every group and the

@@ -26,6 +26,7 @@ ICV_COPY_STATES_MAX_WINDOWS = 16384  # windows icv_copy_states_viterbi keeps in 
 ICV_POSTERIOR_MAX_WINDOWS = 4096  # windows icv_posterior_chains keeps in LDS per cell (include/infercnv_hip.h)
 ICV_CHANGEPOINT_MAX_CHR_WINDOWS = 4096  # windows of one chromosome icv_changepoint_levels keeps in LDS (include/infercnv_hip.h)
 ICV_RANK_MAX_CELLS = 1 << 21  # cells icv_rank_sums ranks against each other: N^3 in an int64 (include/infercnv_hip.h)
+ICV_LEVEL_MAX = 7  # levels of tl.cnv_copy_states lie in [-7, 7] (include/infercnv_hip.h)
 ICV_FILTER_MAX_WINDOWS = 1 << 22  # windows per row of icv_states_filter: a run's int64 sum (include/infercnv_hip.h)
 ICV_COPY_POSTERIOR_LDS_BYTES = 163840  # LDS of one cell of icv_copy_posterior_chains (include/infercnv_hip.h)
 
@@ -82,6 +83,8 @@ EXPORTS = (
     "icv_copy_states_viterbi",
     "icv_copy_posterior_chains", "icv_copy_states_filter",
     "icv_copy_posterior_stats",
+    "icv_level_segments_count", "icv_level_segments_fill", "icv_level_votes", "icv_level_consensus",
+    "icv_level_segments_support", "icv_segments_psum",
 )
 
 
@@ -250,6 +253,12 @@ def load():
     lib.icv_copy_posterior_chains.argtypes = [P(Matrix), vp, i32, P(dbl), i32, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.icv_copy_states_filter.argtypes = [vp, vp, i64, i32, vp, i32, dbl, vp, vp, vp, vp, vp, vp]
     lib.icv_copy_posterior_stats.argtypes = [P(Matrix), vp, i32, P(dbl), i32, i32, dbl, dbl, dbl, vp, vp]
+    lib.icv_level_segments_count.argtypes = [vp, i64, i32, vp, i32, i32, i32, vp, vp, vp]
+    lib.icv_level_segments_fill.argtypes = [vp, i64, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp]
+    lib.icv_level_votes.argtypes = [vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, vp, vp]
+    lib.icv_level_consensus.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp]
+    lib.icv_level_segments_support.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.icv_segments_psum.argtypes = [vp, i64, i32, vp, vp, vp, i64, vp, vp, vp]
     lib.icv_developer_knobs_reload.restype = None
     lib.icv_developer_knobs_reload.argtypes = []
     lib.icv_last_error.restype = C.c_char_p

@@ -49,6 +49,7 @@
 #include "icv_copy_posterior.hpp"
 #include "icv_copy_hmmfit.hpp"
 #include "icv_segments.hpp"
+#include "icv_copy_segments.hpp"
 #include "icv_hmmfit.hpp"
 #include "icv_posterior.hpp"
 #include "icv_pseudobulk.hpp"
@@ -4084,16 +4085,19 @@ int filter_launch(const char* who, const int8_t* states, const double* p_neutral
     return ICV_OK;
 }
 
-// k_seg_rows<fill> over all rows with the chromosome mask of the call; who: the entry point without icv_
+// k_seg_rows<fill> over all rows with the chromosome mask of the call; who: the entry point without icv_.  levels: the
+// count flags what lies outside [lo, hi] instead of what is not -1 / 0 / +1 (the fill validates nothing: one kernel)
 int seg_rows_launch(bool fill, const char* who, const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start,
                     int32_t n_chr, hipStream_t st, int64_t* counts, int32_t* bad, const int64_t* offsets, int64_t n_segments,
-                    int64_t* seg_row, int32_t* seg_start, int32_t* seg_end, int8_t* seg_state) {
+                    int64_t* seg_row, int32_t* seg_start, int32_t* seg_end, int8_t* seg_state, bool levels = false,
+                    int32_t lo = -1, int32_t hi = 1) {
     const int64_t blocks = (n_rows + icv::kSegRowsPerBlock - 1) / icv::kSegRowsPerBlock;
     if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, std::string(who) + ": too many rows for one call");
     AsyncBuf mask;
     ICV_TRY(seg_chr_mask(chr_start, n_chr, n_cols, mask, st));
-    hipLaunchKernelGGL(fill ? icv::k_seg_rows<true> : icv::k_seg_rows<false>, dim3((unsigned)blocks), dim3(64 * icv::kSegRowsPerBlock), 0, st, states, n_rows,
-                       n_cols, mask.as<uint32_t>(), counts, bad, offsets, n_segments, seg_row, seg_start, seg_end, seg_state);
+    const auto kernel = fill ? icv::k_seg_rows<true> : levels ? icv::k_seg_rows<false, true> : icv::k_seg_rows<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * icv::kSegRowsPerBlock), 0, st, states, n_rows, n_cols,
+                       mask.as<uint32_t>(), counts, bad, offsets, n_segments, seg_row, seg_start, seg_end, seg_state, lo, hi);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
@@ -4168,6 +4172,129 @@ int icv_segments_support(const int64_t* seg_row, const int32_t* seg_start, const
     if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "segments_support: too many segments for one call");
     hipLaunchKernelGGL(icv::k_seg_support, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), seg_row,
                        seg_start, seg_end, seg_state, n_segments, loss, gain, n_groups, n_cols, cells_min, cells_sum);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_copy_segments --------------------------------------------------------------------------------
+static_assert(icv::kLevelMax == ICV_LEVEL_MAX, "the header's level bound is the kernels'");
+namespace {
+
+// the rule a level range breaks, or null
+const char* level_range_rule(int32_t lo, int32_t hi) {
+    return (lo < -ICV_LEVEL_MAX || lo > 0 || hi < 0 || hi > ICV_LEVEL_MAX) ? "-7 <= lo <= 0 <= hi <= 7" : nullptr;
+}
+
+int level_range_fail(const char* who, int32_t lo, int32_t hi) {
+    return fail(ICV_ERR_INVALID, std::string(who) + ": the level range (" + std::to_string(lo) + ", " + std::to_string(hi) +
+                                     ") breaks " + level_range_rule(lo, hi));
+}
+
+}  // namespace
+
+int icv_level_segments_count(const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start, int32_t n_chr,
+                             int32_t lo, int32_t hi, int64_t* counts, int32_t* bad, void* stream) {
+    if (!states || !chr_start || !counts || !bad) return fail(ICV_ERR_INVALID, "level_segments_count: a null pointer");
+    if (n_rows < 0 || n_cols < 1) return fail(ICV_ERR_INVALID, "level_segments_count: n_rows >= 0 and n_cols >= 1");
+    if (n_chr < 1 || n_chr > n_cols) return fail(ICV_ERR_INVALID, "level_segments_count: 1 <= n_chr <= n_cols");
+    if (level_range_rule(lo, hi)) return level_range_fail("level_segments_count", lo, hi);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return ICV_OK;
+    return seg_rows_launch(false, "level_segments_count", states, n_rows, n_cols, chr_start, n_chr, st, counts, bad, nullptr, 0,
+                           nullptr, nullptr, nullptr, nullptr, true, lo, hi);
+}
+
+int icv_level_segments_fill(const int8_t* states, int64_t n_rows, int32_t n_cols, const int32_t* chr_start, int32_t n_chr,
+                            const int64_t* offsets, int64_t n_segments, int64_t* seg_row, int32_t* seg_start,
+                            int32_t* seg_end, int8_t* seg_level, void* stream) {
+    if (!states || !chr_start || !offsets || (n_segments > 0 && (!seg_row || !seg_start || !seg_end || !seg_level)))
+        return fail(ICV_ERR_INVALID, "level_segments_fill: a null pointer");
+    if (n_rows < 0 || n_cols < 1 || n_segments < 0)
+        return fail(ICV_ERR_INVALID, "level_segments_fill: n_rows >= 0, n_cols >= 1 and n_segments >= 0");
+    if (n_chr < 1 || n_chr > n_cols) return fail(ICV_ERR_INVALID, "level_segments_fill: 1 <= n_chr <= n_cols");
+    if (n_rows == 0 || n_segments == 0) return ICV_OK;
+    return seg_rows_launch(true, "level_segments_fill", states, n_rows, n_cols, chr_start, n_chr,
+                           static_cast<hipStream_t>(stream), nullptr, nullptr, offsets, n_segments, seg_row, seg_start, seg_end,
+                           seg_level);
+}
+
+int icv_level_votes(const int8_t* states, int64_t n_rows, int32_t n_cols, const int64_t* rows, int64_t n_listed,
+                    const int64_t* group_ptr, int64_t n_groups, int32_t lo, int32_t hi, int32_t* counts, int32_t* bad,
+                    void* stream) {
+    if (!states || (n_listed > 0 && !rows) || !group_ptr || (n_groups > 0 && !counts) || !bad)
+        return fail(ICV_ERR_INVALID, "level_votes: a null pointer");
+    if (n_rows < 0 || n_cols < 1 || n_listed < 0 || n_groups < 0)
+        return fail(ICV_ERR_INVALID, "level_votes: n_rows >= 0, n_cols >= 1, n_listed >= 0 and n_groups >= 0");
+    if (level_range_rule(lo, hi)) return level_range_fail("level_votes", lo, hi);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    if (n_groups == 0) return ICV_OK;
+    const int planes = hi - lo + 1;
+    HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_groups * (size_t)planes * (size_t)n_cols * sizeof(int32_t), st));
+    if (n_listed == 0 || n_rows == 0) return ICV_OK;
+    const int64_t n_tiles = ((int64_t)n_cols + icv::kVoteTile - 1) / icv::kVoteTile;
+    const int64_t blocks = (n_listed + icv::kVoteRows - 1) / icv::kVoteRows * n_tiles;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "level_votes: too many rows x windows for one call");
+    icv::level_votes_launch<1>(planes, dim3((unsigned)blocks), st, states, n_rows, n_cols, rows, n_listed, group_ptr, n_groups,
+                          (uint32_t)n_tiles, lo, counts, bad);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_level_consensus(const int32_t* counts, const int32_t* need, int64_t n_groups, int32_t n_cols, int32_t lo, int32_t hi,
+                        int32_t* loss, int32_t* gain, int8_t* consensus, void* stream) {
+    if (n_groups > 0 && (!counts || !need || !loss || !gain || !consensus))
+        return fail(ICV_ERR_INVALID, "level_consensus: a null pointer");
+    if (n_groups < 0 || n_cols < 1) return fail(ICV_ERR_INVALID, "level_consensus: n_groups >= 0 and n_cols >= 1");
+    if (level_range_rule(lo, hi)) return level_range_fail("level_consensus", lo, hi);
+    if (n_groups == 0) return ICV_OK;
+    const int64_t blocks = (n_groups * (int64_t)n_cols + 255) / 256;
+    if (n_groups > kSegMaxBlocks || blocks > kSegMaxBlocks)
+        return fail(ICV_ERR_UNSUPPORTED, "level_consensus: too many groups x windows for one call");
+    hipLaunchKernelGGL(icv::k_level_consensus, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), counts,
+                       need, n_groups, n_cols, lo, hi, loss, gain, consensus);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_level_segments_support(const int64_t* seg_row, const int32_t* seg_start, const int32_t* seg_end,
+                               const int8_t* seg_level, int64_t n_segments, const int32_t* counts, const int32_t* loss,
+                               const int32_t* gain, int64_t n_groups, int32_t n_cols, int32_t lo, int32_t hi,
+                               int32_t* cells_min, int64_t* cells_sum, int32_t* level_min, int64_t* level_sum, void* stream) {
+    if (n_segments > 0 && (!seg_row || !seg_start || !seg_end || !seg_level || !counts || !loss || !gain || !cells_min ||
+                           !cells_sum || !level_min || !level_sum))
+        return fail(ICV_ERR_INVALID, "level_segments_support: a null pointer");
+    if (n_segments < 0 || n_groups < 0 || n_cols < 1)
+        return fail(ICV_ERR_INVALID, "level_segments_support: n_segments >= 0, n_groups >= 0 and n_cols >= 1");
+    if (level_range_rule(lo, hi)) return level_range_fail("level_segments_support", lo, hi);
+    if (n_segments == 0) return ICV_OK;
+    const int64_t blocks = (n_segments + 255) / 256;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "level_segments_support: too many segments for one call");
+    hipLaunchKernelGGL(icv::k_level_seg_support, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       seg_row, seg_start, seg_end, seg_level, n_segments, counts, loss, gain, n_groups, n_cols, lo, hi,
+                       cells_min, cells_sum, level_min, level_sum);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_segments_psum(const double* p_neutral, int64_t n_rows, int32_t n_cols, const int64_t* seg_row,
+                      const int32_t* seg_start, const int32_t* seg_end, int64_t n_segments, int64_t* psum, int32_t* bad,
+                      void* stream) {
+    if (!p_neutral || !bad || (n_segments > 0 && (!seg_row || !seg_start || !seg_end || !psum)))
+        return fail(ICV_ERR_INVALID, "segments_psum: a null pointer");
+    if (n_rows < 0 || n_cols < 1 || n_segments < 0)
+        return fail(ICV_ERR_INVALID, "segments_psum: n_rows >= 0, n_cols >= 1 and n_segments >= 0");
+    if (n_cols > ICV_FILTER_MAX_WINDOWS)
+        return fail(ICV_ERR_UNSUPPORTED, "segments_psum: n_cols = " + std::to_string(n_cols) + " is above " +
+                                             std::to_string(ICV_FILTER_MAX_WINDOWS) + " (the int64 sum of a run)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    if (n_rows == 0 || n_segments == 0) return ICV_OK;
+    const int64_t blocks = (n_segments + 255) / 256;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "segments_psum: too many segments for one call");
+    hipLaunchKernelGGL(icv::k_seg_psum, dim3((unsigned)blocks), dim3(256), 0, st, p_neutral, n_rows, n_cols, seg_row,
+                       seg_start, seg_end, n_segments, psum, bad);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }

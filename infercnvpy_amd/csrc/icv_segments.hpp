@@ -51,17 +51,20 @@ __global__ __launch_bounds__(256) void k_seg_chr_mask(const int32_t* __restrict_
     atomicOr(&mask[q >> 5], 1u << (q & 31));
 }
 
-// rules 1-2.  FILL = false: counts[row] = the row's segments, *bad |= 1 where a value is not -1 / 0 / +1.
+// rules 1-2.  FILL = false: counts[row] = the row's segments, *bad |= 1 where a value is not -1 / 0 / +1 (LEVELS: where
+// it lies outside [lo, hi], the level range of tl.cnv_copy_segments; starts and ends are decided by equality, so the
+// rest is the same code, and without LEVELS lo and hi are not read).
 // FILL = true: segment offsets[row] + k of the row gets seg_row / seg_start / seg_state from its k-th start and seg_end
 // from its k-th end; a position outside [0, n_seg) is not written (offsets that do not belong to S cannot leave the
-// tables).
-template <bool FILL>
+// tables).  seg_state is the raw byte of S at the start: the fill of level runs is this instantiation.
+template <bool FILL, bool LEVELS = false>
 __global__ __launch_bounds__(64 * kSegRowsPerBlock) void k_seg_rows(
     const int8_t* __restrict__ S, int64_t n_rows, int32_t W, const uint32_t* __restrict__ mask,
     int64_t* __restrict__ counts, int32_t* __restrict__ bad, const int64_t* __restrict__ offsets, int64_t n_seg,
     int64_t* __restrict__ seg_row, int32_t* __restrict__ seg_start, int32_t* __restrict__ seg_end,
-    int8_t* __restrict__ seg_state) {
+    int8_t* __restrict__ seg_state, int32_t lo, int32_t hi) {
     const int lane = threadIdx.x & 63;
+    const int vlo = LEVELS ? lo : -1, vhi = LEVELS ? hi : 1;
     const int64_t row = (int64_t)blockIdx.x * kSegRowsPerBlock + (threadIdx.x >> 6);
     if (row >= n_rows) return;  // (whole wavefronts leave; there is no barrier below)
     const int8_t* p = S + row * (int64_t)W;
@@ -113,7 +116,7 @@ __global__ __launch_bounds__(64 * kSegRowsPerBlock) void k_seg_rows(
             const int after = j + 1 < kSegStrip
                                   ? (int)(int8_t)((j + 1 < 8 ? lo >> (8 * (j + 1)) : hi >> (8 * (j + 1 - 8))) & 0xff)
                                   : next;
-            invalid |= s < -1 || s > 1;
+            invalid |= s < vlo || s > vhi;
             if (s != 0) {
                 if (((cs >> j) & 1) || before != s) sf |= 1u << j;
                 if (((cs >> (j + 1)) & 1) || after != s) ef |= 1u << j;
