@@ -753,6 +753,44 @@ int icv_profile_corr(const icv_matrix *m, const double *profiles_t, const double
 int icv_profile_corr_best(const double *r, int64_t n_rows, int64_t n_profiles, double *best_r, int32_t *best_g,
                           void *stream);
 
+/* ---- tl.cnv_silhouette: exact silhouette widths of the labelled cells ---------------------------------------
+ * The labelled cells are numbered by position: sorted by group, ascending row inside a group.  rows (device int64,
+ * n_listed) maps a position to its row of x, a device row-major n_rows x n_comp matrix of dtype ICV_F32 / ICV_F64 with
+ * ld elements between rows, 1 <= n_comp <= ICV_SILHOUETTE_MAX_COMPONENTS; values are used as float64.  A row number
+ * outside [0, n_rows) is never read: its position counts as a cell at the origin.
+ * icv_silhouette_sums: for the positions i in [i0, i1) (i0 a multiple of ICV_SILHOUETTE_TILE_I, i1 <= n_listed) and every
+ * group g, sums[(i - i0) n_groups + g] (device int64; the entry clears it) = the int64 sum over the positions j of the
+ * tiles of group g of rint(d_ij 2^shift), ties to even, where d_ij = sqrt(acc) and acc starts at +0.0 and takes
+ * acc = acc + t t, t = x_ic - x_jc, over the components in ascending order (float64, every product rounded before its
+ * add, the square root correctly rounded).  tiles (device int64, 3 x n_tiles row-major): first position, number of
+ * positions (1 .. ICV_SILHOUETTE_TILE_J) and group of every tile; a tile that names a group outside [0, n_groups) or
+ * positions outside [0, n_listed) is passed over.  chunk_ptr (device int32, n_chunks + 1 ascending tile numbers from 0 to
+ * n_tiles): a workgroup takes ICV_SILHOUETTE_TILE_I positions i and the tiles of one chunk and adds one 64-bit integer
+ * atomic per (i, run of tiles of one group), so the sums do not depend on the cut into tiles and chunks.  The components
+ * pass through LDS in stages of ICV_SILHOUETTE_TILE_C.  0 <= shift <= ICV_SILHOUETTE_MAX_SHIFT; dist_exp: every d_ij is
+ * below 2^dist_exp (the caller's bound; with shift + dist_exp <= 51 the rounding is one float64 addition, otherwise rint
+ * and a conversion: the same integers).  The caller keeps every group sum below 2^62.  *flags (device int32) is NOT
+ * cleared, so that the calls for the row slabs of one table share it: bit 0 is set where a value that was read is not
+ * finite.  n_chunks <= 65535 (ICV_ERR_UNSUPPORTED beyond).  No synchronisation.
+ * icv_silhouette_finish: group_ptr (device int64, n_groups + 1) holds the first position of every group.  For the
+ * positions p in [i0, i1), with the sums of the same slab: mean(p, g) = double(sum) / (double(cnt) 2^shift), cnt =
+ * n_g - 1 for p's own group and n_g otherwise (the conversion rounds to nearest even, the divisor is exact, the division
+ * correctly rounded); a[p] = the own-group mean, 0.0 where the group is p alone; b[p] = the smallest mean over the other
+ * groups that have cells and nearest[p] (device int32) the lowest group that attains it (0.0 and -1 where there is
+ * none); s[p] = (b - a) / max(a, b), 0.0 where the own group is p alone or max(a, b) == 0.  s, a, b (device float64)
+ * and nearest are indexed by position. */
+#define ICV_SILHOUETTE_TILE_I 64
+#define ICV_SILHOUETTE_TILE_J 64
+#define ICV_SILHOUETTE_TILE_C 32
+#define ICV_SILHOUETTE_MAX_COMPONENTS 256
+#define ICV_SILHOUETTE_MAX_SHIFT 40
+int icv_silhouette_sums(const void *x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const int64_t *rows,
+                        int64_t n_listed, int64_t i0, int64_t i1, const int64_t *tiles, int64_t n_tiles,
+                        const int32_t *chunk_ptr, int32_t n_chunks, int64_t n_groups, int32_t shift, int32_t dist_exp,
+                        int64_t *sums, int32_t *flags, void *stream);
+int icv_silhouette_finish(const int64_t *sums, int64_t i0, int64_t i1, const int64_t *group_ptr, int64_t n_groups,
+                          int32_t shift, double *s, double *a, double *b, int32_t *nearest, void *stream);
+
 /* ---- tl.cnv_changepoints: exact penalised least-squares segmentation of every chromosome of every row ---
  * icv_changepoint_levels: m and chr_start as for icv_states_viterbi (stored values are used as float64, an entry that is
  * not stored is 0.0; CSR columns need not be sorted; a column outside [0, n_cols) is passed over), except that n_cols has

@@ -2276,6 +2276,100 @@ def profile_corr_best(r):
     return best_r, best_g
 
 
+# ---- tl.cnv_silhouette: int64 sums of rounded distances and the widths on the device (icv_silhouette_*) -------
+SILHOUETTE_TILE_I = _lib.ICV_SILHOUETTE_TILE_I  # positions i of a workgroup; the row slabs of S are multiples of it
+SILHOUETTE_TILE_J = _lib.ICV_SILHOUETTE_TILE_J  # positions of a j-tile; a tile never straddles a group
+SILHOUETTE_TILE_C = _lib.ICV_SILHOUETTE_TILE_C  # components per LDS stage
+SILHOUETTE_MAX_COMPONENTS = _lib.ICV_SILHOUETTE_MAX_COMPONENTS
+SILHOUETTE_MAX_SHIFT = _lib.ICV_SILHOUETTE_MAX_SHIFT
+SILHOUETTE_S_BUDGET = 1 << 30  # bytes of the int64 table S above which it is formed in row slabs
+SILHOUETTE_TARGET_BLOCKS = 2048  # workgroups a launch aims for (8 per CU of 256): the j-tiles are cut into chunks for it
+SILHOUETTE_STAGES = ("sums", "finish")
+
+
+def silhouette_tiles(group_ptr, n_chunks):
+    """(tiles, chunk_ptr) for ``group_ptr`` (host int64, G + 1): the int64 ``3 x T`` table of the j-tiles -- first
+    position, number of positions, group; at most ``SILHOUETTE_TILE_J`` positions each, none straddling a group, in
+    position order -- and the int32 ``n + 1`` tile numbers that cut them into ``n = min(max(n_chunks, 1), T, 65535)``
+    consecutive chunks of as equal a number of tiles as possible."""
+    group_ptr = np.asarray(group_ptr, dtype=np.int64)
+    sizes = np.diff(group_ptr)
+    per_group = -(-sizes // SILHOUETTE_TILE_J)
+    group = np.repeat(np.arange(sizes.shape[0], dtype=np.int64), per_group)
+    n_tiles = int(group.shape[0])
+    first_tile = np.concatenate([[0], np.cumsum(per_group)])[:-1]
+    k = np.arange(n_tiles, dtype=np.int64) - first_tile[group]  # the tile's number inside its group
+    start = group_ptr[group] + k * SILHOUETTE_TILE_J
+    count = np.minimum(group_ptr[group + 1] - start, SILHOUETTE_TILE_J)
+    n = min(max(int(n_chunks), 1), max(n_tiles, 1), 65535)
+    chunk_ptr = (np.arange(n + 1, dtype=np.int64) * n_tiles // n).astype(np.int32)
+    return np.ascontiguousarray(np.stack([start, count, group])), chunk_ptr
+
+
+def silhouette(dm: DeviceMatrix, rows, group_ptr, shift, dist_exp, *, s_budget=None, n_chunks=None, stage_ms=None):
+    """(s, a, b, nearest, flags): device float64 / int32 vectors of DESIGN.md 4.26 rules 3-5 for the labelled cells BY
+    POSITION (``rows``, host int64: the rows of ``dm`` sorted by group, ascending inside a group; ``group_ptr``, host
+    int64 G + 1: the first position of every group) and the device int32 flag word (bit 0: a non-finite value).
+    ``shift``: rule 2's e; ``dist_exp``: every distance is below 2^dist_exp.  ``s_budget``: bytes of the int64 table S
+    (default ``SILHOUETTE_S_BUDGET``): above it S is formed and used in slabs of rows, a multiple of
+    ``SILHOUETTE_TILE_I`` each (never fewer: a budget below one tile's rows gives slabs of one tile).  ``n_chunks``: the
+    chunks the j-tiles are cut into (default: what gives ``SILHOUETTE_TARGET_BLOCKS`` workgroups per launch).  Neither
+    changes a bit of the result.  ``stage_ms``: a dict that receives the device-event milliseconds of
+    ``SILHOUETTE_STAGES`` (one synchronisation at the end).  Nothing else is read back."""
+    torch = _torch()
+    lib = _lib.load()
+    assert dm.format == _lib.ICV_DENSE
+    n, c = int(dm.shape[0]), int(dm.shape[1])
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    group_ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
+    m, g = int(rows.shape[0]), int(group_ptr.shape[0]) - 1
+    assert g >= 1 and int(group_ptr[0]) == 0 and int(group_ptr[-1]) == m and (np.diff(group_ptr) >= 0).all()
+    assert m == 0 or (0 <= int(rows.min()) and int(rows.max()) < n)
+    budget = SILHOUETTE_S_BUDGET if s_budget is None else int(s_budget)
+    slab = max(budget // (8 * g) // SILHOUETTE_TILE_I, 1) * SILHOUETTE_TILE_I
+    slab = min(slab, -(-max(m, 1) // SILHOUETTE_TILE_I) * SILHOUETTE_TILE_I)
+    if n_chunks is None:
+        n_chunks = -(-SILHOUETTE_TARGET_BLOCKS // (min(slab, max(m, 1)) // SILHOUETTE_TILE_I + 1))
+    tiles, chunk_ptr = silhouette_tiles(group_ptr, n_chunks)
+    marks = []
+
+    def mark(name):
+        if stage_ms is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            marks.append((name, ev))
+
+    with torch.cuda.device(dm.device):
+        st = _stream_ptr(torch)
+        d_rows = torch.from_numpy(rows).cuda() if m else torch.zeros(1, dtype=torch.int64, device="cuda")
+        d_ptr = torch.from_numpy(group_ptr).cuda()
+        d_tiles = torch.from_numpy(tiles).cuda() if tiles.shape[1] else torch.zeros(3, dtype=torch.int64, device="cuda")
+        d_chunks = torch.from_numpy(chunk_ptr).cuda()
+        sums = torch.empty(max(min(slab, m), 1) * g, dtype=torch.int64, device="cuda")
+        s, a, b = (_empty(torch, m, torch.float64) for _ in range(3))
+        nearest = _empty(torch, m, torch.int32)
+        flags = torch.zeros(1, dtype=torch.int32, device="cuda")
+        x = dm.dense
+        dtype = _lib.ICV_F32 if x.dtype == torch.float32 else _lib.ICV_F64
+        for i0 in range(0, m, slab):
+            i1 = min(i0 + slab, m)
+            mark(None)
+            _lib.check(lib.icv_silhouette_sums(_ptr(x), dtype, n, c, int(x.stride(0)) if n > 1 else c, _ptr(d_rows), m, i0,
+                                               i1, _ptr(d_tiles), int(tiles.shape[1]), _ptr(d_chunks),
+                                               int(chunk_ptr.shape[0]) - 1, g, int(shift), int(dist_exp), _ptr(sums),
+                                               _ptr(flags), st))
+            mark("sums")
+            _lib.check(lib.icv_silhouette_finish(_ptr(sums), i0, i1, _ptr(d_ptr), g, int(shift), _ptr(s), _ptr(a), _ptr(b),
+                                                 _ptr(nearest), st))
+            mark("finish")
+        if stage_ms is not None:
+            torch.cuda.current_stream().synchronize()
+            for (_, e0), (name, e1) in zip(marks, marks[1:]):
+                if name is not None:
+                    stage_ms[name] = stage_ms.get(name, 0.0) + float(e0.elapsed_time(e1))
+    return s, a, b, nearest, flags
+
+
 # ---- tl.cnv_rank_groups: exact doubled mid-rank sums on the device (icv_rank_*, DESIGN.md 4.20) ---------------------------
 RANK_STAGES = ("count", "scatter", "sort", "rank_sums", "finish")
 

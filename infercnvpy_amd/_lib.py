@@ -28,6 +28,11 @@ ICV_CHANGEPOINT_MAX_CHR_WINDOWS = 4096  # windows of one chromosome icv_changepo
 ICV_RANK_MAX_CELLS = 1 << 21  # cells icv_rank_sums ranks against each other: N^3 in an int64 (include/infercnv_hip.h)
 ICV_LEVEL_MAX = 7  # levels of tl.cnv_copy_states lie in [-7, 7] (include/infercnv_hip.h)
 ICV_FILTER_MAX_WINDOWS = 1 << 22  # windows per row of icv_states_filter: a run's int64 sum (include/infercnv_hip.h)
+ICV_SILHOUETTE_TILE_I = 64  # positions i of a workgroup of icv_silhouette_sums (include/infercnv_hip.h)
+ICV_SILHOUETTE_TILE_J = 64  # positions of a j-tile of icv_silhouette_sums (include/infercnv_hip.h)
+ICV_SILHOUETTE_TILE_C = 32  # components per LDS stage of icv_silhouette_sums (include/infercnv_hip.h)
+ICV_SILHOUETTE_MAX_COMPONENTS = 256  # components icv_silhouette_sums takes (include/infercnv_hip.h)
+ICV_SILHOUETTE_MAX_SHIFT = 40  # binary places of a rounded distance (include/infercnv_hip.h)
 ICV_COPY_POSTERIOR_LDS_BYTES = 163840  # LDS of one cell of icv_copy_posterior_chains (include/infercnv_hip.h)
 
 
@@ -77,6 +82,7 @@ EXPORTS = (
     "icv_posterior_stats",
     "icv_group_profiles", "icv_group_profiles_finish",
     "icv_profile_corr", "icv_profile_corr_best",
+    "icv_silhouette_sums", "icv_silhouette_finish",
     "icv_changepoint_levels", "icv_changepoint_diffsq",
     "icv_rank_count", "icv_rank_scatter", "icv_rank_sort", "icv_rank_sums", "icv_rank_finish",
     "icv_neighbor_pool_sizes", "icv_neighbor_pool",
@@ -240,6 +246,8 @@ def load():
     lib.icv_group_profiles_finish.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
     lib.icv_profile_corr.argtypes = [P(Matrix), vp, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.icv_profile_corr_best.argtypes = [vp, i64, i64, vp, vp, vp]
+    lib.icv_silhouette_sums.argtypes = [vp, i32, i64, i32, i64, vp, i64, i64, i64, vp, i64, vp, i32, i64, i32, i32, vp, vp, vp]
+    lib.icv_silhouette_finish.argtypes = [vp, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp]
     lib.icv_changepoint_levels.argtypes = [P(Matrix), vp, i32, dbl, i32, vp, vp, vp]
     lib.icv_changepoint_diffsq.argtypes = [P(Matrix), vp, i32, vp, vp]
     lib.icv_rank_count.argtypes = [P(Matrix), vp, vp, vp, vp]

@@ -54,6 +54,7 @@
 #include "icv_posterior.hpp"
 #include "icv_pseudobulk.hpp"
 #include "icv_profile_corr.hpp"
+#include "icv_silhouette.hpp"
 #include "icv_changepoint.hpp"
 #include "icv_rank.hpp"
 #include "icv_pool.hpp"
@@ -4430,6 +4431,60 @@ int icv_profile_corr_best(const double* r, int64_t n_rows, int64_t n_profiles, d
     if ((n_rows + 255) / 256 > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "profile_corr_best: too many rows for one call");
     hipLaunchKernelGGL(icv::k_profile_corr_best, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), r, n_rows, n_profiles, best_r, best_g);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_silhouette: exact silhouette widths from int64 sums of rounded distances ------------------------
+static_assert(icv::kSilTileI == ICV_SILHOUETTE_TILE_I && icv::kSilTileJ == ICV_SILHOUETTE_TILE_J &&
+                  icv::kSilTileC == ICV_SILHOUETTE_TILE_C && icv::kSilMaxC == ICV_SILHOUETTE_MAX_COMPONENTS &&
+                  icv::kSilMaxShift == ICV_SILHOUETTE_MAX_SHIFT,
+              "the header's silhouette constants are the kernel's");
+
+int icv_silhouette_sums(const void* x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const int64_t* rows,
+                        int64_t n_listed, int64_t i0, int64_t i1, const int64_t* tiles, int64_t n_tiles,
+                        const int32_t* chunk_ptr, int32_t n_chunks, int64_t n_groups, int32_t shift, int32_t dist_exp,
+                        int64_t* sums, int32_t* flags, void* stream) {
+    if ((dtype != ICV_F32 && dtype != ICV_F64) || n_rows < 0 || n_comp < 1 || n_comp > icv::kSilMaxC || ld < n_comp ||
+        n_listed < 0 || i0 < 0 || i1 < i0 || i1 > n_listed || i0 % icv::kSilTileI != 0 || n_tiles < 0 ||
+        n_tiles > 0x7fffffffLL || n_chunks < 0 || n_groups < 1 || shift < 0 || shift > icv::kSilMaxShift || !flags ||
+        (i1 > i0 && (!x || !rows || !sums)) || (n_tiles > 0 && !tiles) || (n_chunks > 0 && !chunk_ptr))
+        return fail(ICV_ERR_INVALID, "bad silhouette_sums arguments");
+    if (i1 == i0) return ICV_OK;
+    if (i1 - i0 > 0x7fffffffffffffffLL / 8 / n_groups) return fail(ICV_ERR_INVALID, "silhouette_sums: the table of sums overflows");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)(i1 - i0) * (size_t)n_groups * sizeof(int64_t), st));
+    if (n_tiles == 0 || n_chunks == 0) return ICV_OK;
+    const int64_t blocks = (i1 - i0 + icv::kSilTileI - 1) / icv::kSilTileI;
+    if (blocks > kSegMaxBlocks || n_chunks > 65535)
+        return fail(ICV_ERR_UNSUPPORTED, "silhouette_sums: too many positions or chunks for one call");
+    const dim3 grid((unsigned)blocks, (unsigned)n_chunks), block(icv::kSilThreads);
+    const double scale = std::ldexp(1.0, shift);
+    const bool magic = (int64_t)shift + dist_exp <= icv::kSilMagicBits;
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        auto launch = [&](auto m) {
+            hipLaunchKernelGGL((icv::k_sil_sums<T, decltype(m)::value>), grid, block, 0, st, (const T*)x, ld, n_rows,
+                               (int)n_comp, rows, n_listed, i0, i1, tiles, n_tiles, chunk_ptr, n_groups, scale,
+                               (unsigned long long*)sums, flags);
+        };
+        if (magic) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_silhouette_finish(const int64_t* sums, int64_t i0, int64_t i1, const int64_t* group_ptr, int64_t n_groups,
+                          int32_t shift, double* s, double* a, double* b, int32_t* nearest, void* stream) {
+    if (i0 < 0 || i1 < i0 || n_groups < 1 || n_groups > 0x7fffffffLL || shift < 0 || shift > icv::kSilMaxShift ||
+        (i1 > i0 && (!sums || !group_ptr || !s || !a || !b || !nearest)))
+        return fail(ICV_ERR_INVALID, "bad silhouette_finish arguments");
+    if (i1 == i0) return ICV_OK;
+    const int64_t blocks = (i1 - i0 + 255) / 256;
+    if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "silhouette_finish: too many positions for one call");
+    hipLaunchKernelGGL(icv::k_sil_finish, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (const long long*)sums, i0, i1, group_ptr, n_groups, std::ldexp(1.0, shift), s, a, b, nearest);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
