@@ -791,6 +791,54 @@ int icv_silhouette_sums(const void *x, int32_t dtype, int64_t n_rows, int32_t n_
 int icv_silhouette_finish(const int64_t *sums, int64_t i0, int64_t i1, const int64_t *group_ptr, int64_t n_groups,
                           int32_t shift, double *s, double *a, double *b, int32_t *nearest, void *stream);
 
+/* ---- tl.cnv_kmeans: deterministic exact k-means of the representation -----------------------------------------
+ * x is a device row-major n_rows x n_comp matrix of dtype ICV_F32 / ICV_F64 with ld elements between rows, n_rows >= 1,
+ * 1 <= n_comp <= ICV_KMEANS_MAX_COMPONENTS; values are used as float64.  centres is a device float64 n_clusters x n_comp
+ * table, 1 <= n_clusters <= ICV_KMEANS_MAX_CLUSTERS.  D(i, g) starts at +0.0 and takes acc = acc + t t, t = x_ic - c_gc,
+ * over the components in ascending order (every product rounded before its add).  Shifts lie in
+ * [0, ICV_KMEANS_MAX_SHIFT]; the caller chooses them so that no integer sum leaves int64 (DESIGN.md 4.27 rule 2).  *flags
+ * (device int32) is never cleared: bit 0 is set where a value that was read is not finite, bit 1 where the seeding
+ * weights of a draw add up to 0.  Every entry refuses a null pointer or an argument out of range with ICV_ERR_INVALID
+ * before any GPU work.  No synchronisation.
+ * icv_kmeans_seed_dist: for every row, mind[i] = D(i, centre) when first, otherwise the smaller of that and mind[i];
+ * w[i] = rint(mind[i] 2^shift_f) as int64, ties to even; partials[j] = the sum of w over the rows
+ * [j ICV_KMEANS_SEED_ROWS, + ICV_KMEANS_SEED_ROWS) (device int64, ceil(n_rows / ICV_KMEANS_SEED_ROWS) of them).  No atomics.
+ * icv_kmeans_seed_pick: one workgroup.  t == 0: the row is z mod n_rows.  t > 0: W = the sum of partials, theta = z mod W
+ * (unsigned 64-bit), the row is the first whose inclusive prefix sum of w in row order exceeds theta.  The row's values
+ * become centres[t n_comp ..] and picks[t] (device int64) its number; W == 0 sets bit 1 of *flags and picks[t] = -1 and
+ * leaves the centre as it is.
+ * icv_kmeans_assign: labels[i] (device int32) = the lowest g that attains the smallest D(i, g), sqdist[i] that D;
+ * stats (device int64, 2; the entry clears it): stats[0] = the int64 sum of rint(sqdist[i] 2^shift_f), stats[1] = the
+ * number of rows whose label differs from the one found in labels before the call.
+ * icv_kmeans_update: sums (device int64, n_clusters (n_comp + 1); the entry clears it): sums[g n_comp + c] = the int64 sum
+ * of rint(x_ic 2^shift_e) over the rows with label g, sums[n_clusters n_comp + g] = their number.  A label outside
+ * [0, n_clusters) is in no sum.  One workgroup per (ICV_KMEANS_UPDATE_ROWS rows, ICV_KMEANS_UPDATE_TILE_C components) sums
+ * in LDS and adds one 64-bit atomic per non-zero sum, so the sums do not depend on the cut.
+ * icv_kmeans_centres: centres[g, c] = double(sum) / (double(n_g) 2^shift_e) for every g with n_g > 0 (the conversions
+ * round to nearest even, the divisor is exact, the division correctly rounded); the other centres stay. */
+#define ICV_KMEANS_TILE_CELLS 256
+#define ICV_KMEANS_TILE_CENTRES 16
+#define ICV_KMEANS_TILE_C 32
+#define ICV_KMEANS_MAX_COMPONENTS 256
+#define ICV_KMEANS_MAX_CLUSTERS 256
+#define ICV_KMEANS_MAX_SHIFT 40
+#define ICV_KMEANS_SEED_ROWS 256
+#define ICV_KMEANS_UPDATE_ROWS 1024
+#define ICV_KMEANS_UPDATE_TILE_C 16
+int icv_kmeans_seed_dist(const void *x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const double *centre,
+                         int32_t first, int32_t shift_f, double *mind, int64_t *w, int64_t *partials, int32_t *flags,
+                         void *stream);
+int icv_kmeans_seed_pick(const void *x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const int64_t *w,
+                         const int64_t *partials, int32_t t, int32_t n_clusters, uint64_t z, double *centres,
+                         int64_t *picks, int32_t *flags, void *stream);
+int icv_kmeans_assign(const void *x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const double *centres,
+                      int32_t n_clusters, int32_t shift_f, int32_t *labels, double *sqdist, int64_t *stats, int32_t *flags,
+                      void *stream);
+int icv_kmeans_update(const void *x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const int32_t *labels,
+                      int32_t n_clusters, int32_t shift_e, int64_t *sums, void *stream);
+int icv_kmeans_centres(const int64_t *sums, int32_t n_clusters, int32_t n_comp, int32_t shift_e, double *centres,
+                       void *stream);
+
 /* ---- tl.cnv_changepoints: exact penalised least-squares segmentation of every chromosome of every row ---
  * icv_changepoint_levels: m and chr_start as for icv_states_viterbi (stored values are used as float64, an entry that is
  * not stored is 0.0; CSR columns need not be sorted; a column outside [0, n_cols) is passed over), except that n_cols has

@@ -2370,6 +2370,99 @@ def silhouette(dm: DeviceMatrix, rows, group_ptr, shift, dist_exp, *, s_budget=N
     return s, a, b, nearest, flags
 
 
+# ---- tl.cnv_kmeans: seeding, assignment and integer update on the device (icv_kmeans_*) -------------------
+KMEANS_MAX_COMPONENTS = _lib.ICV_KMEANS_MAX_COMPONENTS
+KMEANS_MAX_CLUSTERS = _lib.ICV_KMEANS_MAX_CLUSTERS
+KMEANS_MAX_SHIFT = _lib.ICV_KMEANS_MAX_SHIFT
+KMEANS_FLAG_NONFINITE, KMEANS_FLAG_NO_MASS = 1, 2
+KMEANS_STAGES = ("seed", "lloyd")
+
+
+def kmeans(dm: DeviceMatrix, k, shift_e, shift_f, max_iter, *, draws=None, init=None, stage_ms=None):
+    """The runs of DESIGN.md 4.27 rules 4-8 on ``dm`` (dense n x C).  ``draws``: per run the k hash values ``z_0 .. z_{k-1}``
+    of rule 3 (Python ints below 2^64); or ``init``, a host float64 k x C table of starting centres, for one run without
+    seeding.  Returns a dict: ``labels`` (device int32 n), ``sqdist`` (device float64 n: D(i, label_i)) and ``centres``
+    (device float64 k x C) of the run of lowest integer inertia (ties: the first), in the raw cluster order;
+    ``best``, ``n_iter``, ``converged`` and ``inertia_q`` (per run) of the host; ``history`` (per run, the
+    (inertia, n_changed) of every iteration) and ``picks`` (per run the k seeded rows, None with ``init``).  One copy of
+    three words (inertia, n_changed, flag word) comes back per iteration, as the Baum-Welch fits read their sums; the
+    picks come back once at the end.  ``ValueError`` for a non-finite value that a kernel read and for seeding weights that
+    add up to 0 (fewer distinct points than clusters).  ``stage_ms``: a dict that receives host-clock milliseconds of
+    ``KMEANS_STAGES`` (``seed`` only enqueues; ``lloyd`` ends in the read-backs)."""
+    torch = _torch()
+    lib = _lib.load()
+    assert dm.format == _lib.ICV_DENSE and (draws is None) != (init is None)
+    n, c = int(dm.shape[0]), int(dm.shape[1])
+    k = int(k)
+    x = dm.dense
+    dtype = _lib.ICV_F32 if x.dtype == torch.float32 else _lib.ICV_F64
+    ld = int(x.stride(0)) if n > 1 else c
+    n_runs = 1 if draws is None else len(draws)
+    seed_blocks = -(-n // _lib.ICV_KMEANS_SEED_ROWS)
+    clock = {name: 0.0 for name in KMEANS_STAGES}
+
+    with torch.cuda.device(dm.device):
+        st = _stream_ptr(torch)
+        head = (_ptr(x), dtype, n, c, ld)
+        # words 0, 1: the inertia and n_changed of the last assignment; the low half of word 2: the flag word
+        state = torch.zeros(3, dtype=torch.int64, device="cuda")
+        flags = state[2:].view(torch.int32)
+        sums = torch.empty(k * (c + 1), dtype=torch.int64, device="cuda")
+        picks = torch.full((n_runs, k), -1, dtype=torch.int64, device="cuda")
+        if draws is not None:
+            mind = torch.empty(n, dtype=torch.float64, device="cuda")
+            w = torch.empty(n, dtype=torch.int64, device="cuda")
+            partials = torch.empty(seed_blocks, dtype=torch.int64, device="cuda")
+        best, kept = -1, None
+        inertia_q, n_iters, converged, history = [], [], [], []
+        for r in range(n_runs):
+            t0 = _time.perf_counter()
+            labels = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+            sqdist = torch.empty(n, dtype=torch.float64, device="cuda")
+            if draws is None:
+                centres = torch.from_numpy(np.ascontiguousarray(init, dtype=np.float64)).cuda()
+            else:
+                centres = torch.zeros((k, c), dtype=torch.float64, device="cuda")
+                for t in range(k):
+                    if t:
+                        _lib.check(lib.icv_kmeans_seed_dist(*head, C.c_void_p(centres.data_ptr() + 8 * c * (t - 1)), int(t == 1),
+                                                            int(shift_f), _ptr(mind), _ptr(w), _ptr(partials), _ptr(flags), st))
+                    _lib.check(lib.icv_kmeans_seed_pick(*head, _ptr(w) if t else None, _ptr(partials) if t else None, t, k,
+                                                        int(draws[r][t]), _ptr(centres), _ptr(picks[r]), _ptr(flags), st))
+            t1 = _time.perf_counter()
+            clock["seed"] += t1 - t0
+            trace = []
+            it = 0
+            while True:
+                it += 1
+                _lib.check(lib.icv_kmeans_assign(*head, _ptr(centres), k, int(shift_f), _ptr(labels), _ptr(sqdist),
+                                                 _ptr(state), _ptr(flags), st))
+                inertia, changed, flag = (int(v) for v in state.cpu().tolist())
+                if flag & KMEANS_FLAG_NO_MASS:
+                    raise ValueError(f"the rows hold fewer than {k} distinct points")
+                if flag & KMEANS_FLAG_NONFINITE:
+                    raise ValueError("non-finite values")
+                trace.append((inertia, changed))
+                if changed == 0 or it == max_iter:
+                    break
+                _lib.check(lib.icv_kmeans_update(*head, _ptr(labels), k, int(shift_e), _ptr(sums), st))
+                _lib.check(lib.icv_kmeans_centres(_ptr(sums), k, c, int(shift_e), _ptr(centres), st))
+            clock["lloyd"] += _time.perf_counter() - t1
+            history.append(trace)
+            inertia_q.append(trace[-1][0])
+            n_iters.append(it)
+            converged.append(trace[-1][1] == 0)
+            if best < 0 or inertia_q[r] < inertia_q[best]:
+                best, kept = r, (labels, sqdist, centres)
+        host_picks = picks.cpu().numpy() if draws is not None else None
+    if stage_ms is not None:
+        for name in KMEANS_STAGES:
+            stage_ms[name] = stage_ms.get(name, 0.0) + clock[name] * 1e3
+    return {"labels": kept[0], "sqdist": kept[1], "centres": kept[2], "best": best, "n_iter": n_iters,
+            "converged": converged, "inertia_q": inertia_q, "history": history,
+            "picks": None if host_picks is None else [row.tolist() for row in host_picks]}
+
+
 # ---- tl.cnv_rank_groups: exact doubled mid-rank sums on the device (icv_rank_*, DESIGN.md 4.20) ---------------------------
 RANK_STAGES = ("count", "scatter", "sort", "rank_sums", "finish")
 

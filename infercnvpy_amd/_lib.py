@@ -33,6 +33,15 @@ ICV_SILHOUETTE_TILE_J = 64  # positions of a j-tile of icv_silhouette_sums (incl
 ICV_SILHOUETTE_TILE_C = 32  # components per LDS stage of icv_silhouette_sums (include/infercnv_hip.h)
 ICV_SILHOUETTE_MAX_COMPONENTS = 256  # components icv_silhouette_sums takes (include/infercnv_hip.h)
 ICV_SILHOUETTE_MAX_SHIFT = 40  # binary places of a rounded distance (include/infercnv_hip.h)
+ICV_KMEANS_TILE_CELLS = 256  # cells of a workgroup of icv_kmeans_assign (include/infercnv_hip.h)
+ICV_KMEANS_TILE_CENTRES = 16  # centres per tile of icv_kmeans_assign (include/infercnv_hip.h)
+ICV_KMEANS_TILE_C = 32  # components per LDS stage of icv_kmeans_assign (include/infercnv_hip.h)
+ICV_KMEANS_MAX_COMPONENTS = 256  # components the icv_kmeans_* entries take (include/infercnv_hip.h)
+ICV_KMEANS_MAX_CLUSTERS = 256  # clusters the icv_kmeans_* entries take (include/infercnv_hip.h)
+ICV_KMEANS_MAX_SHIFT = 40  # binary places of a rounded coordinate or squared distance (include/infercnv_hip.h)
+ICV_KMEANS_SEED_ROWS = 256  # rows per partial sum of icv_kmeans_seed_dist (include/infercnv_hip.h)
+ICV_KMEANS_UPDATE_ROWS = 1024  # rows per workgroup of icv_kmeans_update (include/infercnv_hip.h)
+ICV_KMEANS_UPDATE_TILE_C = 16  # components per workgroup of icv_kmeans_update (include/infercnv_hip.h)
 ICV_COPY_POSTERIOR_LDS_BYTES = 163840  # LDS of one cell of icv_copy_posterior_chains (include/infercnv_hip.h)
 
 
@@ -83,6 +92,7 @@ EXPORTS = (
     "icv_group_profiles", "icv_group_profiles_finish",
     "icv_profile_corr", "icv_profile_corr_best",
     "icv_silhouette_sums", "icv_silhouette_finish",
+    "icv_kmeans_seed_dist", "icv_kmeans_seed_pick", "icv_kmeans_assign", "icv_kmeans_update", "icv_kmeans_centres",
     "icv_changepoint_levels", "icv_changepoint_diffsq",
     "icv_rank_count", "icv_rank_scatter", "icv_rank_sort", "icv_rank_sums", "icv_rank_finish",
     "icv_neighbor_pool_sizes", "icv_neighbor_pool",
@@ -248,6 +258,11 @@ def load():
     lib.icv_profile_corr_best.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.icv_silhouette_sums.argtypes = [vp, i32, i64, i32, i64, vp, i64, i64, i64, vp, i64, vp, i32, i64, i32, i32, vp, vp, vp]
     lib.icv_silhouette_finish.argtypes = [vp, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp]
+    lib.icv_kmeans_seed_dist.argtypes = [vp, i32, i64, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.icv_kmeans_seed_pick.argtypes = [vp, i32, i64, i32, i64, vp, vp, i32, i32, C.c_uint64, vp, vp, vp, vp]
+    lib.icv_kmeans_assign.argtypes = [vp, i32, i64, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.icv_kmeans_update.argtypes = [vp, i32, i64, i32, i64, vp, i32, i32, vp, vp]
+    lib.icv_kmeans_centres.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.icv_changepoint_levels.argtypes = [P(Matrix), vp, i32, dbl, i32, vp, vp, vp]
     lib.icv_changepoint_diffsq.argtypes = [P(Matrix), vp, i32, vp, vp]
     lib.icv_rank_count.argtypes = [P(Matrix), vp, vp, vp, vp]

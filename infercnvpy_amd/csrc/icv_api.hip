@@ -55,6 +55,7 @@
 #include "icv_pseudobulk.hpp"
 #include "icv_profile_corr.hpp"
 #include "icv_silhouette.hpp"
+#include "icv_kmeans.hpp"
 #include "icv_changepoint.hpp"
 #include "icv_rank.hpp"
 #include "icv_pool.hpp"
@@ -4485,6 +4486,108 @@ int icv_silhouette_finish(const int64_t* sums, int64_t i0, int64_t i1, const int
     if (blocks > kSegMaxBlocks) return fail(ICV_ERR_UNSUPPORTED, "silhouette_finish: too many positions for one call");
     hipLaunchKernelGGL(icv::k_sil_finish, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        (const long long*)sums, i0, i1, group_ptr, n_groups, std::ldexp(1.0, shift), s, a, b, nearest);
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+// ---- tl.cnv_kmeans: deterministic exact k-means from integer sums ----------------------------------------
+static_assert(icv::kKmTileCells == ICV_KMEANS_TILE_CELLS && icv::kKmTileCentres == ICV_KMEANS_TILE_CENTRES &&
+                  icv::kKmTileC == ICV_KMEANS_TILE_C && icv::kKmMaxC == ICV_KMEANS_MAX_COMPONENTS &&
+                  icv::kKmMaxK == ICV_KMEANS_MAX_CLUSTERS && icv::kKmMaxShift == ICV_KMEANS_MAX_SHIFT &&
+                  icv::kKmSeedRows == ICV_KMEANS_SEED_ROWS && icv::kKmUpdRows == ICV_KMEANS_UPDATE_ROWS &&
+                  icv::kKmUpdTileC == ICV_KMEANS_UPDATE_TILE_C,
+              "the header's k-means constants are the kernel's");
+
+namespace {
+// what every k-means entry checks of the representation
+bool kmeans_matrix_ok(const void* x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld) {
+    return x && (dtype == ICV_F32 || dtype == ICV_F64) && n_rows >= 1 &&
+           n_rows <= kSegMaxBlocks * (int64_t)icv::kKmSeedRows && n_comp >= 1 && n_comp <= icv::kKmMaxC && ld >= n_comp;
+}
+bool kmeans_shift_ok(int32_t shift) { return shift >= 0 && shift <= icv::kKmMaxShift; }
+}  // namespace
+
+int icv_kmeans_seed_dist(const void* x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const double* centre,
+                         int32_t first, int32_t shift_f, double* mind, int64_t* w, int64_t* partials, int32_t* flags,
+                         void* stream) {
+    if (!kmeans_matrix_ok(x, dtype, n_rows, n_comp, ld) || !kmeans_shift_ok(shift_f) || !centre || !mind || !w ||
+        !partials || !flags)
+        return fail(ICV_ERR_INVALID, "bad kmeans_seed_dist arguments");
+    const int64_t blocks = (n_rows + icv::kKmSeedRows - 1) / icv::kKmSeedRows;
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_km_seed_dist<T>, dim3((unsigned)blocks), dim3(icv::kKmThreads), 0,
+                           static_cast<hipStream_t>(stream), (const T*)x, ld, n_rows, (int)n_comp, centre, (int)(first != 0),
+                           std::ldexp(1.0, shift_f), mind, (long long*)w, (unsigned long long*)partials, flags);
+    });
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_kmeans_seed_pick(const void* x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const int64_t* w,
+                         const int64_t* partials, int32_t t, int32_t n_clusters, uint64_t z, double* centres,
+                         int64_t* picks, int32_t* flags, void* stream) {
+    if (!kmeans_matrix_ok(x, dtype, n_rows, n_comp, ld) || n_clusters < 1 || n_clusters > icv::kKmMaxK || t < 0 ||
+        t >= n_clusters || (t > 0 && (!w || !partials)) || !centres || !picks || !flags)
+        return fail(ICV_ERR_INVALID, "bad kmeans_seed_pick arguments");
+    const int64_t blocks = (n_rows + icv::kKmSeedRows - 1) / icv::kKmSeedRows;
+    by_dtype(dtype, [&](auto tt) {
+        using T = decltype(tt);
+        hipLaunchKernelGGL(icv::k_km_seed_pick<T>, dim3(1), dim3(icv::kKmThreads), 0, static_cast<hipStream_t>(stream),
+                           (const T*)x, ld, n_rows, (int)n_comp, (const long long*)w, (const unsigned long long*)partials,
+                           blocks, (int)t, (unsigned long long)z, centres, picks, flags);
+    });
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_kmeans_assign(const void* x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const double* centres,
+                      int32_t n_clusters, int32_t shift_f, int32_t* labels, double* sqdist, int64_t* stats, int32_t* flags,
+                      void* stream) {
+    if (!kmeans_matrix_ok(x, dtype, n_rows, n_comp, ld) || n_clusters < 1 || n_clusters > icv::kKmMaxK ||
+        !kmeans_shift_ok(shift_f) || !centres || !labels || !sqdist || !stats || !flags)
+        return fail(ICV_ERR_INVALID, "bad kmeans_assign arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(stats, 0, 2 * sizeof(int64_t), st));
+    const int64_t blocks = (n_rows + icv::kKmTileCells - 1) / icv::kKmTileCells;
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_km_assign<T>, dim3((unsigned)blocks), dim3(icv::kKmThreads), 0, st, (const T*)x, ld, n_rows,
+                           (int)n_comp, centres, (int)n_clusters, std::ldexp(1.0, shift_f), labels, sqdist,
+                           (unsigned long long*)stats, flags);
+    });
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_kmeans_update(const void* x, int32_t dtype, int64_t n_rows, int32_t n_comp, int64_t ld, const int32_t* labels,
+                      int32_t n_clusters, int32_t shift_e, int64_t* sums, void* stream) {
+    if (!kmeans_matrix_ok(x, dtype, n_rows, n_comp, ld) || n_clusters < 1 || n_clusters > icv::kKmMaxK ||
+        !kmeans_shift_ok(shift_e) || !labels || !sums)
+        return fail(ICV_ERR_INVALID, "bad kmeans_update arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)n_clusters * (size_t)(n_comp + 1) * sizeof(int64_t), st));
+    const int64_t slabs = (n_rows + icv::kKmUpdRows - 1) / icv::kKmUpdRows;
+    const dim3 grid((unsigned)slabs, (unsigned)((n_comp + icv::kKmUpdTileC - 1) / icv::kKmUpdTileC));
+    unsigned long long* q = (unsigned long long*)sums;
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(icv::k_km_update<T>, grid, dim3(icv::kKmThreads), 0, st, (const T*)x, ld, n_rows, (int)n_comp,
+                           labels, (int)n_clusters, std::ldexp(1.0, shift_e), q, q + (size_t)n_clusters * (size_t)n_comp);
+    });
+    HIP_TRY(hipGetLastError());
+    return ICV_OK;
+}
+
+int icv_kmeans_centres(const int64_t* sums, int32_t n_clusters, int32_t n_comp, int32_t shift_e, double* centres,
+                       void* stream) {
+    if (n_clusters < 1 || n_clusters > icv::kKmMaxK || n_comp < 1 || n_comp > icv::kKmMaxC || !kmeans_shift_ok(shift_e) ||
+        !sums || !centres)
+        return fail(ICV_ERR_INVALID, "bad kmeans_centres arguments");
+    const int cells = n_clusters * n_comp;
+    hipLaunchKernelGGL(icv::k_km_centres, dim3((unsigned)((cells + icv::kKmThreads - 1) / icv::kKmThreads)),
+                       dim3(icv::kKmThreads), 0, static_cast<hipStream_t>(stream), (const long long*)sums,
+                       (const long long*)sums + cells, (int)n_clusters, (int)n_comp, std::ldexp(1.0, shift_e), centres);
     HIP_TRY(hipGetLastError());
     return ICV_OK;
 }
